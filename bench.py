@@ -2,13 +2,20 @@
 """Headline benchmark: Mpaths/s of Integrator::PathTraceBlock on MI355X.
 
   python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cornell|interior|dr|dr_interior|spectral|film|spectral_interior] [--spp S]
+                  [--full] [--dump-outputs DIR]
 
 A *step* is one PathTraceBlock call over the whole frame (W*H pixels x spp passes, MIS path tracing) with the framebuffer,
-RNG states and scene resident in HBM. N = 1 runs BASELINE.json configs[1] (scenes/test_035 Cornell box, 1024 x 1024, 1024 spp)
-and appends ("also") the other configurations AT THEIR STATED SIZES: configs[2] (1M-triangle interior, 1920 x 1080 @ 1024 spp, wavefront
-schedule, one step), configs[3] (PathTraceDR + Adam on the test_228 class, 512^2 @ 256 spp), configs[4] (1M triangles, 4096^2 x 4 albedo,
-1920 x 1080 @ 512 spp, fwd + bwd + Adam, one step), the reference's spectral fixture, a thin-film fixture and the 1M-triangle interior under
-spectral mode - each with its own roofline.
+RNG states and scene resident in HBM. N = 1 runs BASELINE.json configs[1] (scenes/test_035 Cornell box, 1024 x 1024, 1024 spp).
+A plain run sets up, warms up, times the K steps and prints the line; everything else is measured with --full only:
+`cpu_baseline`, the `roofline` (an instrumented probe launch of its own; a plain run reports the timed kernel's `kernel_ms` there),
+the check of sharded frames (N > 1) and, appended under "also", the other configurations AT THEIR STATED SIZES: configs[2] (1M-triangle
+interior, 1920 x 1080 @ 1024 spp, wavefront schedule, one step), configs[3] (PathTraceDR + Adam on the test_228 class, 512^2 @ 256 spp),
+configs[4] (1M triangles, 4096^2 x 4 albedo, 1920 x 1080 @ 512 spp, fwd + bwd + Adam, one step), the reference's spectral fixture, a
+thin-film fixture and the 1M-triangle interior under spectral mode - each with its own roofline.
+
+--dump-outputs DIR: after the timed steps, writes what the last timed step returned to its caller as DIR/<name>.npy (float32): `frame`
+(the accumulated framebuffer) and, for dr / dr_interior, `loss`, `grad` (a_dataGrad) and `params` (the texture after the Adam step).
+Arrays above the 64 MB budget are cut to a fixed, seeded sample of their elements. Inputs are seeded: the same arguments give the same inputs.
 
 N > 1: one rank per GPU (the scene is replicated, no data-path collective but ONE RCCL reduce(SUM) of the framebuffer per step).
 Started plainly (`python bench.py --gpus N`, WORLD_SIZE unset) the script spawns its N ranks itself through
@@ -25,11 +32,12 @@ Started plainly (`python bench.py --gpus N`, WORLD_SIZE unset) the script spawns
         The JSON line's `value` is the pixels split; the samples split is timed as well and reported under "also".
   --scaling weak              every rank renders the whole frame at the full --spp (N x the samples in the same time): per-GPU work fixed.
 
-Sharded frames are verified on rank 0 after the timed region (at 8 spp; --no-verify skips it).
+With --full, sharded frames are verified on rank 0 after the timed region (at 8 spp; --no-verify skips it).
 
-Prints ONE JSON line on rank 0 (contract in the task description). `roofline` names the ceiling that binds the dominant kernel: the
-Cornell megakernel is VALU-issue bound (profiles/pmc_cornell.json), the wavefront trace kernel of the 1M-triangle scene is priced
-against HBM both by ALGORITHMIC bytes and by the rocprofv3 counters. `cpu_baseline` times the CPU oracle (a restated
+Prints ONE JSON line on rank 0: `value` (`unit`, `higher_is_better`) over the timed steps and `ms_per_step`, the milliseconds one timed
+step took. `roofline` names the ceiling that binds the dominant kernel: the Cornell megakernel is VALU-issue bound
+(profiles/pmc_cornell.json), the wavefront trace kernel of the 1M-triangle scene is priced against HBM both by ALGORITHMIC bytes
+ and by the rocprofv3 counters. `cpu_baseline` times the CPU oracle (a restated
 port, not the original binary) in a child process on the box's usable cores.
 """
 import argparse
@@ -122,6 +130,27 @@ def cpu_baseline(workload, width, height, target_s=20.0):
     return None
 
 
+# ---- --dump-outputs ---------------------------------------------------------------------------------------------------------------------
+DUMP_BUDGET = 64 * 2 ** 20      # bytes over all arrays of one run
+DUMP_SEED = 20240601
+
+
+def dump_outputs(outdir, arrays):
+    """Writes {name: host array} as outdir/<name>.npy in float32. The budget is shared out smallest array first; an array that does not fit
+    its share is written as a fixed, seeded sample of its elements (flattened, ascending index order: the same elements in every run)."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    items = sorted(arrays.items(), key=lambda kv: kv[1].size)
+    left = DUMP_BUDGET // 4
+    for i, (name, a) in enumerate(items):
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        cap = left // (len(items) - i)
+        if a.size > cap:
+            a = a.reshape(-1)[np.unique(np.random.default_rng(DUMP_SEED).integers(0, a.size, cap))]
+        np.save(os.path.join(outdir, name + ".npy"), a)
+        left -= a.size
+
+
 # ---- roofline pieces -------------------------------------------------------------------------------------------------------------------
 def algorithmic_bytes(counters, paths, spp):
     """bytes a path has to touch, from the traversal / shading counters of an instrumented launch."""
@@ -201,8 +230,8 @@ def make_roofline(workload, integ, torch, dev, stream, N, W, H, spp, t_count, ke
 
 
 # ---- forward workloads ------------------------------------------------------------------------------------------------------------------
-def run_forward(args, workload, rank, world, dev, dist, backend, steps, warmup, spp, shard, with_roofline=True, warmup_spp=None):
-    """Times `steps` PathTraceBlock calls; returns the result dict (rank 0) or None."""
+def run_forward(args, workload, rank, world, dev, dist, backend, steps, warmup, spp, shard, with_roofline=True, warmup_spp=None, dump=None):
+    """Times `steps` PathTraceBlock calls; returns the result dict (rank 0) or None. `dump`: directory for the last step's frame."""
     import numpy as np
     import torch
     from hydracore3_amd.api import HipIntegrator
@@ -279,10 +308,12 @@ def run_forward(args, workload, rank, world, dev, dist, backend, steps, warmup, 
     paths_per_step = float(N) * spp * (world if weak else 1)      # (with --emulate-share K: the K ranks together would have finished the frame in this time)
     value = paths_per_step * steps / elapsed / 1e6
     mean_lum = float(frame[..., :3].mean().item()) / (spp * (world if weak else 1)) if rank == 0 else 0.0
+    if dump and rank == 0:
+        dump_outputs(dump, {"frame": frame.cpu().numpy()})
 
     # ---- verification of the sharded frame (rank 0 re-renders the ranks' shares alone, at a few passes) ----
     verified = None
-    if world > 1 and not args.no_verify and args.emulate_share == 1:
+    if world > 1 and args.full and not args.no_verify and args.emulate_share == 1:
         vspp = min(8 * world, spp)
         vint = HipIntegrator(sc, device=dev.index, accel_layout=args.accel_layout)
         vf = torch.zeros_like(frame)
@@ -322,6 +353,8 @@ def run_forward(args, workload, rank, world, dev, dist, backend, steps, warmup, 
     roofline = None
     if rank == 0 and with_roofline:
         roofline = make_roofline(workload, integ, torch, dev, stream, N, W, H, my_spp if not weak else spp, t_count, kernel_ms)
+    elif rank == 0:
+        roofline = {"kernel_ms": round(float(np.mean(kernel_ms)), 3)}
     if rank != 0:
         return None
     if world == 1:
@@ -362,7 +395,7 @@ def dr_algorithmic_bytes(c, d, paths, spp, shade_records):
             "records_per_path": d["records"] / paths}
 
 
-def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_arg, warmup_spp=None):
+def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_arg, warmup_spp=None, dump=None):
     """IntegratorDR fwd+bwd + Adam.  dr: BASELINE.json configs[3] (test_228-class scene, 256 x 256 x 4 albedo, 512^2 @ 256 spp);
     dr_interior: configs[4] (1M-triangle interior, tex_size^2 x 4 fp32 albedo bound to its 32 gltf materials, 1920x1080).
     One step = memset(grad) + PathTraceDR (record, replay and adjoint fused, gradient atomics into HBM) [+ all_reduce(SUM) of the
@@ -465,6 +498,8 @@ def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_a
         kms = [integ.last_kernel_ms()]
     paths_per_step = N * spp * (world if weak else 1)
     value = float(paths_per_step) * steps / elapsed / 1e6
+    if dump and rank == 0:                                         # (before the counting probe below overwrites frame, grad and loss)
+        dump_outputs(dump, {"frame": frame.cpu().numpy(), "loss": loss.cpu().numpy(), "grad": grad.cpu().numpy(), "params": data.cpu().numpy()})
     if rank != 0:
         return None
     what = (f"synthetic 1M-triangle interior + {tw}x{tw}x4 differentiable albedo, {W}x{H} @ {spp} spp" if big
@@ -475,7 +510,7 @@ def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_a
     wl = "dr_interior" if big else "dr"
     roof = {"kernel": {1: "pathTraceKernel<DR>", 3: "pathTraceBlockKernel<DR> (megakernel, block-local ray repacking)"}.get(sched_used, f"wavefront DR: {wf_rounds} x (wfShadeKernel<DR> + wfTraceKernel)"),
             "kernel_ms": round(k_ms, 3)}
-    if world == 1:
+    if world == 1 and args.full:
         # the counting probe: the instrumented PathTraceDR megakernel on the same frame at a few passes (it walks the tree the timed call walked)
         probe_spp = min(spp, 8)
         integ.set_schedule(1); integ.set_option("stats_wide", 1 if launch["wide_nodes"] else 0); integ.set_instrumentation(True)
@@ -515,7 +550,7 @@ def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_a
             roof["hbm_algorithmic"] = dict(hbm, note="SURVEY 8d algorithmic bytes incl. the adjoint term; the scene and the 1 MB gradient live in L2, the records in L2 / Infinity Cache")
             roof.update(detail)
             roof["note"] = "forward walk + reverse sweep + gradient scatter in one kernel; float atomics execute at the memory side and are not VALU work"
-    else:
+    elif world > 1:
         roof.update({"bound": "valu" if sched_used == 1 else "hbm", "achieved": None, "peak": None, "unit": None, "frac": None, "traffic": None, "note": "priced on the single-GPU run only"})
     return {"metric": "Mpaths/s (fwd+bwd grad, IntegratorDR::PathTraceDR + Adam)", "value": round(value, 2), "unit": "Mpaths/s", "n_gpus": world,
             "steps": steps, "warmup": warmup, "ms_per_step": round(elapsed / steps * 1e3, 3), "higher_is_better": True,
@@ -526,7 +561,7 @@ def run_dr(args, workload, rank, world, dev, dist, backend, steps, warmup, spp_a
             "roofline": roof}
 
 
-def run_fixture(dev, scene_name, spectral, steps=3, size=1024, spp=64, profile=None, warmup=1, warmup_spp=4):
+def run_fixture(dev, scene_name, spectral, steps=3, size=1024, spp=64, profile=None, warmup=1, warmup_spp=4, dump=None):
     """An `also` entry for a fixture scene of the reference's feature branches (spectral rendering, thin films): `steps` PathTraceBlock calls on a
     device-resident frame, timed with HIP events around each launch (HipIntegrator.last_kernel_ms). `profile`: name of the committed PMC
     profile (profiles/pmc_<profile>.json, collected with `bench.py --workload <profile>` under rocprofv3) that prices the VALU roofline."""
@@ -550,6 +585,8 @@ def run_fixture(dev, scene_name, spectral, steps=3, size=1024, spp=64, profile=N
         integ.path_trace_block_dev(frame.ptr, spp)
         ms.append(integ.last_kernel_ms())
     mean_ms = sum(ms) / len(ms)
+    if dump:
+        dump_outputs(dump, {"frame": frame.download()})
     paths = float(W) * H * spp
     roof = None
     pmc = load_profile(f"pmc_{profile}.json") if profile else None
@@ -603,10 +640,13 @@ def main():
     ap.add_argument("--width", type=int, default=0)
     ap.add_argument("--height", type=int, default=0)
     ap.add_argument("--spp", type=int, default=1024)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="N = 1: skip the secondary workloads (configs[2], configs[3]) appended under \"also\"")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: cpu_baseline, the roofline probe, "
+                                                       "the check of sharded frames and the secondary workloads under \"also\"")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the last step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-also", action="store_true", help="with --full: skip the secondary workloads (configs[2], configs[3]) appended under \"also\"")
     ap.add_argument("--no-build", action="store_true", help="never compile (profiler runs: build first, `python __graft_entry__.py`); fail if the library is missing")
-    ap.add_argument("--no-verify", action="store_true", help="N > 1: skip the check of the sharded frame against single-GPU renderings of the same shares")
+    ap.add_argument("--no-verify", action="store_true", help="N > 1 with --full: skip the check of the sharded frame against single-GPU renderings of the same shares")
     ap.add_argument("--blocks-per-cu", type=int, default=0)
     ap.add_argument("--schedule", type=int, default=0, help="0 automatic, 1 persistent megakernel, 2 wavefront (shade + trace kernels), 3 megakernel with block-local ray repacking, 4 wavefront in one launch (block-owned slots)")
     ap.add_argument("--refill-below", type=int, default=0, help="wavefront: refill a trace wave when fewer lanes than this hold a ray")
@@ -654,7 +694,7 @@ def main():
     if no_build and not os.path.exists(g.LIB):
         raise SystemExit(f"{g.LIB} is missing and --no-build was given: run `python __graft_entry__.py` first")
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("cornell", "interior"):
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and args.workload in ("cornell", "interior"):
         W0 = args.width or (1024 if args.workload == "cornell" else 1920)
         H0 = args.height or (1024 if args.workload == "cornell" else 1080)
         cpu = cpu_baseline(args.workload, W0, H0)
@@ -680,7 +720,8 @@ def main():
     if args.workload in FIXTURES:                                 # a feature-branch fixture on its own (the form the PMC profiles are collected on)
         name, spectral = FIXTURES[args.workload]
         fspp = args.spp if args.spp != 1024 else 64
-        r = run_fixture(dev, name, spectral, steps=args.steps, spp=fspp, profile=args.workload, warmup=args.warmup, warmup_spp=fspp) if rank == 0 else None   # (equal launches: what profiles/summarize.py divides by)
+        r = run_fixture(dev, name, spectral, steps=args.steps, spp=fspp, profile=args.workload, warmup=args.warmup, warmup_spp=fspp,
+                        dump=args.dump_outputs) if rank == 0 else None   # (equal launches: what profiles/summarize.py divides by)
         out = None
         if r is not None:
             out = {"metric": r["metric"], "value": r["value"], "unit": "Mpaths/s", "n_gpus": 1, "steps": r["steps"], "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
@@ -688,19 +729,21 @@ def main():
                    "config": {"workload": r["workload"], "paths_per_step": r["paths_per_step"], "sharding": "single GPU"},
                    "roofline": r["roofline"] or {"kernel_ms": r["ms_per_step"]}, "cpu_baseline": None}
     elif args.workload in ("dr", "dr_interior"):
-        out = run_dr(args, args.workload, rank, world, dev, dist, backend, args.steps, args.warmup, args.spp)
+        out = run_dr(args, args.workload, rank, world, dev, dist, backend, args.steps, args.warmup, args.spp, dump=args.dump_outputs)
         if out is not None:
             out["cpu_baseline"] = None
     else:
-        out = run_forward(args, args.workload, rank, world, dev, dist, backend, args.steps, args.warmup, args.spp, args.shard)
+        out = run_forward(args, args.workload, rank, world, dev, dist, backend, args.steps, args.warmup, args.spp, args.shard,
+                          with_roofline=args.full, dump=args.dump_outputs)
         if out is not None:
             out["cpu_baseline"] = cpu
         also = []
-        if world > 1 and args.scaling == "strong" and args.shard == "pixels" and not args.no_also:
+        with_also = args.full and not args.no_also
+        if world > 1 and args.scaling == "strong" and args.shard == "pixels" and with_also:
             # the sample split of the same fixed work (an equivalent frame from other RNG sub-streams), timed beside the north-star split
             r = run_forward(args, args.workload, rank, world, dev, dist, backend, args.steps, args.warmup, args.spp, "samples", with_roofline=False)
             also.append(compact(r))
-        if world == 1 and args.workload == "cornell" and not args.no_also and not (args.width or args.height):
+        if world == 1 and args.workload == "cornell" and with_also and not (args.width or args.height):
             # BASELINE's other configurations at their stated sizes, timed by whoever runs this line (one long step each, warmed up at a few passes)
             r = run_forward(args, "interior", rank, world, dev, dist, backend, 1, 1, 1024, args.shard, warmup_spp=16)     # configs[2]: 1920 x 1080 @ 1024 spp
             also.append(compact(r))

@@ -13,8 +13,8 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 rm -rf $OUT && mkdir -p $OUT        # a re-collection under the same tag must not mix with the previous one
 python3 __graft_entry__.py > $OUT/build.log 2>&1 || { echo "build failed"; exit 1; }
-CMD="python3 bench.py --workload $WL --steps 2 --warmup 1 --spp $SPP --no-cpu-baseline --no-also --no-build"
-SQ="python3 bench.py --workload $WL --steps 1 --warmup 0 --spp $SQSPP --no-cpu-baseline --no-also --no-build"
+CMD="python3 bench.py --workload $WL --steps 2 --warmup 1 --spp $SPP --no-cpu-baseline --no-also --no-build --full"
+SQ="python3 bench.py --workload $WL --steps 1 --warmup 0 --spp $SQSPP --no-cpu-baseline --no-also --no-build --full"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- $CMD > $OUT/stats.log 2>&1 && \
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $OUT/pmc_fetch -- $CMD > $OUT/pmc_fetch.log 2>&1 && \
 rocprofv3 --kernel-trace --pmc WRITE_SIZE TCC_HIT_sum TCC_MISS_sum --output-format csv -d $OUT/pmc_write -- $CMD > $OUT/pmc_write.log 2>&1 && \

@@ -1,7 +1,7 @@
 #!/bin/bash
 # SQ / TCP counters of the wavefront kernels on the 1M-triangle scene (each pass its own run, --kernel-trace only)
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-CMD="python3 bench.py --workload interior --steps 1 --warmup 0 --spp 4 --no-cpu-baseline"
+CMD="python3 bench.py --workload interior --steps 1 --warmup 0 --spp 4 --no-cpu-baseline --full"
 timeout -k 5 200 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_INSTS_VMEM_RD --output-format csv -d gpurun_out/pmcw1 -- $CMD > gpurun_out/pmcw1.log 2>&1 && \
 timeout -k 5 200 rocprofv3 --kernel-trace --pmc SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_SCA SQ_WAIT_INST_LDS SQ_INST_CYCLES_VMEM --output-format csv -d gpurun_out/pmcw2 -- $CMD > gpurun_out/pmcw2.log 2>&1 && \
 timeout -k 5 200 rocprofv3 --kernel-trace --pmc SQ_THREAD_CYCLES_VALU SQ_WAVES SQ_INSTS_VALU SQ_ACTIVE_INST_VALU --output-format csv -d gpurun_out/pmcw3 -- $CMD > gpurun_out/pmcw3.log 2>&1

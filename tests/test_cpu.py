@@ -217,8 +217,12 @@ def test_library_exports_every_declared_symbol():
 
 
 def test_no_gpu_means_loud_failure_not_fallback():
-    import torch
-    if torch.cuda.is_available():
+    # torch is asked in a child process: imported here, after the session fixture has loaded libhydra_hip.so (bound to the system's
+    # libamdhip64.so.7), torch would load its own bundled HIP runtime into this process, and on a GPU box every GPU test after this one
+    # in the same session would find no device
+    r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.is_available())"], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    if r.stdout.split()[-1] == "True":
         pytest.skip("a GPU is visible")
     from hydracore3_amd.api import HipIntegrator, HydraHipError
     with pytest.raises(HydraHipError):
@@ -232,6 +236,21 @@ def test_product_never_imports_the_oracle():
                 txt = open(os.path.join(dirpath, f), errors="ignore").read()
                 assert "oracle" not in txt.replace("# oracle", "").lower() or f in ("scene.py",), f
     assert "import oracle" not in open(os.path.join(ROOT, "hydracore3_amd", "scene.py")).read()
+
+
+def test_bench_dump_keeps_its_budget_with_a_fixed_sample(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays are written as float32; past the byte budget the largest array is cut to a seeded sample of its
+    elements, the same elements in every run, and the arrays together stay within the budget."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 4000)
+    arrays = {"big": np.arange(5000, dtype=np.float64).reshape(50, 100), "small": np.ones((2, 3), np.float32)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    small, big = np.load(tmp_path / "a" / "small.npy"), np.load(tmp_path / "a" / "big.npy")
+    assert small.dtype == big.dtype == np.float32 and small.shape == (2, 3) and np.all(small == 1)
+    assert big.ndim == 1 and 500 < big.size and (small.size + big.size) * 4 <= 4000
+    assert np.all(np.diff(big) > 0) and np.all(big == np.round(big)) and big.max() < 5000          # distinct elements of the array, in order
+    assert np.array_equal(big, np.load(tmp_path / "b" / "big.npy"))
 
 
 # ---- sharding ---------------------------------------------------------------------------------------------------------------

@@ -992,13 +992,44 @@ def test_bench_under_torch_distributed_run_exits_cleanly():
     from conftest import ROOT
     env = dict(os.environ, HYDRA_BENCH_FORCE_DIST="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29533",
-           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--spp", "16", "--no-cpu-baseline", "--no-also", "--no-build"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--spp", "16", "--no-cpu-baseline", "--no-also", "--no-build", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, cwd=ROOT, env=env, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{\"metric\"")]
     assert len(lines) == 1
     out = json.loads(lines[0])
     assert out["n_gpus"] == 1 and out["value"] > 0 and out["roofline"]["frac"] > 0 and out["unit"] == "Mpaths/s"
+
+
+def test_bench_dumps_what_the_last_timed_step_computed(tmp_path):
+    """bench.py --dump-outputs DIR: a plain run times --steps steps, measures nothing else and writes the last step's frame as DIR/frame.npy
+    (float32); two runs with the same arguments write the same frame (seeded inputs, one thread per pixel). The DR path writes the frame, the
+    loss, the gradient and the parameters after the Adam step."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+
+    def bench(d, extra):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--width", "128", "--height", "128",
+                            "--no-build", "--dump-outputs", str(d)] + extra, capture_output=True, text=True, cwd=ROOT, timeout=600)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{\"metric\"")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+
+    a = bench(tmp_path / "a", ["--spp", "8"])
+    b = bench(tmp_path / "b", ["--spp", "8"])
+    assert a["steps"] == 2 and a["ms_per_step"] > 0 and a["cpu_baseline"] is None and "also" not in a
+    fa, fb = np.load(tmp_path / "a" / "frame.npy"), np.load(tmp_path / "b" / "frame.npy")
+    assert fa.dtype == np.float32 and fa.shape == (128, 128, 4) and np.isfinite(fa).all() and fa[..., :3].mean() > 0
+    assert np.array_equal(fa, fb)
+    assert abs(float(fa[..., :3].mean()) / 8 - a["config"]["mean_radiance"]) < 1e-4
+    bench(tmp_path / "dr", ["--workload", "dr", "--spp", "4"])
+    out = {n: np.load(tmp_path / "dr" / f"{n}.npy") for n in ("frame", "loss", "grad", "params")}
+    assert out["frame"].shape == (128, 128, 4) and out["loss"].shape == (1,) and out["grad"].shape == out["params"].shape
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in out.values())
+    assert np.any(out["grad"] != 0) and np.any(out["params"] != 0.5)
 
 
 def _bench_two_ranks(extra, timeout=900):
@@ -1021,13 +1052,13 @@ def test_two_ranks_of_the_hip_path_reassemble_the_single_gpu_frame():
     the RCCL run): plain `python bench.py --gpus 2` spawns the ranks itself; fixed total work split by PIXELS (the default and the line's value:
     interleaved tid chunks, bit-identical to the single-GPU frame) and by SAMPLES (all pixels x spp / 2 per rank, RNG sub-streams, frames
     summed; under "also") - both verified by rank 0 against single-rank renderings of the same shares inside the run; weak scaling likewise."""
-    out = _bench_two_ranks(["--spp", "32"])
+    out = _bench_two_ranks(["--spp", "32", "--full"])
     assert out["n_gpus"] == 2 and out["scaling"] == "strong" and out["value"] > 0
     assert out["config"]["sharded_frame_verified"] is True and "pixel sharding" in out["config"]["sharding"]      # the north-star split is the headline
     assert out["config"]["paths_per_step"] == 1024 * 1024 * 32                      # fixed total work: not N x the samples
     also = out["also"][0]
     assert also["sharded_frame_verified"] is True and "sample sharding" in also["sharding"] and also["paths_per_step"] == 1024 * 1024 * 32
-    weak = _bench_two_ranks(["--spp", "16", "--scaling", "weak", "--no-also"])
+    weak = _bench_two_ranks(["--spp", "16", "--scaling", "weak", "--no-also", "--full"])
     assert weak["scaling"] == "weak" and weak["config"]["sharded_frame_verified"] is True and weak["config"]["paths_per_step"] == 2 * 1024 * 1024 * 16
 
 
