@@ -1065,7 +1065,7 @@ HPT_DEV uint remapMaterialId(const DevScene& S, uint a_mId, uint a_instId)
 // Closest hit = min t with ties broken by (instId, primId): independent of tree shape and traversal order.
 struct HitRec { float t; uint prim, inst; float u, v; uint slot = 0xFFFFFFFFu; };   // inst == 0xFFFFFFFF: miss; slot: the hit's triangle record (single-level layout), for DevScene::shadeTris
 
-struct TravStats { uint nodes, tris, insts, waveNodeIters, waveTriIters; };   // wave*: counted by the first active lane of each trip
+struct TravStats { uint nodes, tris, insts, waveNodeIters, waveTriIters; uint wavePairTrips[2] = { 0u, 0u }, wavePairSkips[2] = { 0u, 0u }; };   // wave*: counted by the first active lane of each trip; [0] closest-hit sweep, [1] occlusion sweep
 HPT_DEV bool firstActiveLane() { const uint l = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)); return l == (uint)__builtin_amdgcn_readfirstlane((int)l); }
 
 // Loop shape ("while-while"): every lane first walks inner nodes in a tight loop until it holds a leaf reference, and only
@@ -1428,6 +1428,9 @@ HPT_DEV bool triangleOccludes(const float4 a, const float4 b, const float4 c, co
   return (det != 0.0f) & (uu >= 0.0f) & (vv >= 0.0f) & (uu + vv <= 1.0f) & (tt >= tnear) & (tt <= tfar);
 }
 
+#ifndef HPT_SWEEP_CULL_CLOSEST
+#define HPT_SWEEP_CULL_CLOSEST 0
+#endif
 template <bool ANY, bool STATS>
 HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float tnear, const float tfar, HitRec& hit, TravStats& st)
 {
@@ -1436,6 +1439,11 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
   const cfloat4* insts = (const cfloat4*)S.sweepInsts;
   const cfloat4* tris = (const cfloat4*)S.sweepTris;
   const cfloat4* boxes = (const cfloat4*)S.sweepBoxes;
+  const cfloat4* planes = (const cfloat4*)S.sweepPlanes;
+  // The pair cull pays in the occlusion sweep only (Cornell: 47.5 % of its pair trips skipped, +5 %); the closest-hit sweep skipped 1.6 % and lost
+  // 5 %, and even switched off at run time its code cost 3.7 %: it is compiled in with HPT_SWEEP_CULL_CLOSEST=1 only.
+  const bool cull = (ANY || HPT_SWEEP_CULL_CLOSEST) && S.sweepCull != 0u;
+  const float limNaN = tnear >= 0.0f ? 0.0f : __builtin_nanf("");      // the pair cull assumes tnear >= 0 (ray queries may pass less): NaN never culls
   const V3 id = rcp3(wd);
   const uint ni = S.numInsts;
   for (uint i = 0; i < ni; i++) {
@@ -1459,10 +1467,22 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
     if (STATS) st.insts++;
     const uint first = r3.x, pairs = r3.w;                                 // records come in pairs (the host pads an odd mesh with a record that cannot be hit)
     const cfloat4* tp = tris + 3u * first;
-    for (uint k = 0; k < pairs; k++, tp += 6) {
+    const cfloat4* pp = planes + 3u * (first >> 1);                       // (an instance's records start at an even index: meshes are padded to pairs)
+    for (uint k = 0; k < pairs; k++, tp += 6, pp += 3) {
+      if (cull) {
+        // Wave-uniform pair cull: skip the pair when no lane's ray can cross its plane within [0, lim] (sweepPairPlane: the margins keep it
+        // conservative against the exact float test, so hits stay bit-identical). In a convex room a shadow ray crosses none of the walls.
+        const float4 p0 = ldc4(pp), p1 = ldc4(pp + 1), p2 = ldc4(pp + 2);
+        const float lim = (ANY ? tfar : hit.t) + limNaN;
+        const bool reach = sweepPairMayReach(p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, o.x, o.y, o.z, d.x, d.y, d.z, lim);
+        if (__ballot(reach & !(ANY & found)) == 0ull) {
+          if (STATS && firstActiveLane()) st.wavePairSkips[ANY ? 1 : 0]++;
+          continue;
+        }
+      }
       // six scalar loads, one wait: two triangles per trip
       const float4 a0 = ldc4(tp), b0 = ldc4(tp + 1), c0 = ldc4(tp + 2), a1 = ldc4(tp + 3), b1 = ldc4(tp + 4), c1 = ldc4(tp + 5);
-      if (STATS) { st.tris += 2; if (firstActiveLane()) st.waveTriIters += 2; }
+      if (STATS) { st.tris += 2; if (firstActiveLane()) { st.waveTriIters += 2; st.wavePairTrips[ANY ? 1 : 0]++; } }
       if (ANY) {
         found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar);
         found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar);

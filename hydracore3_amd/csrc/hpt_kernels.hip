@@ -231,6 +231,12 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     { unsigned long long a = st.waveNodeIters, b = st.waveTriIters;
       for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o); b += __shfl_down(b, o); }
       if ((threadIdx.x & 63) == 0) { atomicAdd(&job.counters->v[14], a); atomicAdd(&job.counters->v[15], b); } }
+    // sweep scenes: wave trips through a record pair, wave-uniform pair skips (traceSweep's cull), closest-hit then occlusion sweep: [25..28]
+    for (int i = 0; i < 4; i++) {
+      unsigned long long x = i < 2 ? st.wavePairTrips[i] : st.wavePairSkips[i - 2];
+      for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
+      if ((threadIdx.x & 63) == 0 && x) atomicAdd(&job.counters->v[25 + i], x);
+    }
     if ((threadIdx.x & 63) == 0) { for (int i = 0; i < 5; i++) atomicAdd(&job.counters->v[8 + i], tPh[i]); atomicAdd(&job.counters->v[13], tTrips); }
     if (DR) {
       if ((threadIdx.x & 63) == 0) { atomicAdd(&job.counters->v[18], tPh[5]); atomicAdd(&job.counters->v[19], tPh[6]); }

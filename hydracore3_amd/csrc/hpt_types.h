@@ -118,6 +118,102 @@ static_assert(sizeof(BvhTri) == 48, "triangle record must be 48 bytes");
 struct BvhInst { float row0[4], row1[4], row2[4]; uint root, geomId, pad0, pad1; };   // pad0 = 1: a moving instance (DevScene::instMotion)
 static_assert(sizeof(BvhInst) == 64, "instance record must be 64 bytes");
 
+// ---- sweep pair planes (traceSweep's per-pair cull) -----------------------------------------------------------------------------------------
+// One record per record PAIR of DevScene::sweepTris, in the instance's object space: the pair's plane n.(x - ctr) = c (n unit, c ~ 0), and the
+// margins of the cull test below. m0 = +inf is the "may not cull" flag (padding-only pairs, pairs whose triangles are not coplanar).
+struct SweepPlane { float n[3], c; float ctr[3], m0; float q[3], pad; };
+static_assert(sizeof(SweepPlane) == 48, "pair plane must be three float4");
+
+// The cull must never skip a triangle that the exact test (hpt_device.h: triangleOccludes / triangleTestInOrder, Moeller-Trumbore in float)
+// would accept, so its margins bound the rounding of BOTH computations. u = 2^-24. For triangle j of the pair (stored v0 = a, e1, e2; N = e1 x e2,
+// n^ = N / |N|, in exact arithmetic the ray meets the plane at t* = -f / g with f = n^.(o - a), g = n^.d), the float test computes
+// t = (|N| f + E1) / (-|N| g + E2) (1 + r), |r| <= 2u, where - expanding tvec = o - a, qvec = tvec x e1, dot(e2, qvec) term by term - every
+// product e2_i t_j e1_k carries at most 6 roundings: |E1| <= 8u sum_k W_k |t_k| with W_x = |e1_y e2_z| + |e1_z e2_y| (and cyclic), and in the same
+// way |E2| <= 8u sum_k W_k |d_k|. The weights are per axis, so an axis-aligned quad (the Cornell walls) leaves only the error of its normal
+// component, which is a rounding of f itself: the wall a shadow ray leaves is culled although its origin sits a mere 5e-6 * max(maxcomp(p), 1)
+// above it. The cull's own s0 = fma(n, o - ctr, -c), sd = n.d differ from f, g by the fma chains' 3-4u, by |n - n^| (per axis) and by the plane
+// residual |n^.(a - ctr) - c|. q collects the per-axis factors (taken over both triangles, 2 % added for the roundings of the margin itself), m0
+// the constant ones, and the tests are
+//   away:  s0 > m  and  s0 + lim (sd - md) > m + 8u |s0|      below:  s0 < -m  and  s0 + lim (sd + md) < -(m + 8u |s0|)
+// with m = q.|o - ctr| + m0, md = q.|d|: the first part gives |N| f + E1 the sign of s0, the second puts the float t beyond lim (the slack 8u |s0|
+// covers r and the rounding of the fma). Moving away (t < 0) is out of reach as long as tnear >= 0: the caller passes lim = NaN otherwise.
+HPT_HD void sweepPairPlane(const BvhTri& t0, const BvhTri& t1, SweepPlane& p)
+{
+  const double u = 1.0 / 16777216.0;
+  const BvhTri* t[2] = { &t0, &t1 };
+  p.n[0] = p.n[1] = p.n[2] = p.c = p.ctr[0] = p.ctr[1] = p.ctr[2] = p.q[0] = p.q[1] = p.q[2] = p.pad = 0.0f;
+  p.m0 = INFINITY;
+  double N[2][3], len[2], nh[2][3], lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 };
+  bool live[2];
+  int first = -1;
+  for (int j = 0; j < 2; j++) {
+    const float* e1 = t[j]->e1; const float* e2 = t[j]->e2; const float* a = t[j]->v0;
+    N[j][0] = (double)e1[1] * e2[2] - (double)e1[2] * e2[1]; N[j][1] = (double)e1[2] * e2[0] - (double)e1[0] * e2[2]; N[j][2] = (double)e1[0] * e2[1] - (double)e1[1] * e2[0];
+    len[j] = sqrt(N[j][0] * N[j][0] + N[j][1] * N[j][1] + N[j][2] * N[j][2]);
+    live[j] = len[j] > 0.0 && len[j] < 1e300;                // (the padding record is all zero: det == 0, never hit)
+    for (int k = 0; k < 3 && live[j]; k++) live[j] = isfinite(a[k]) && isfinite(e1[k]) && isfinite(e2[k]);
+    if (!live[j]) continue;
+    if (first < 0) first = j;
+    for (int k = 0; k < 3; k++) {
+      const double v[3] = { (double)a[k], (double)a[k] + e1[k], (double)a[k] + e2[k] };
+      for (int w = 0; w < 3; w++) { lo[k] = fmin(lo[k], v[w]); hi[k] = fmax(hi[k], v[w]); }
+    }
+  }
+  if (first < 0) return;
+  double n[3] = { 0, 0, 0 };
+  for (int j = 0; j < 2; j++) {
+    if (!live[j]) continue;
+    const double s = (N[j][0] * N[first][0] + N[j][1] * N[first][1] + N[j][2] * N[first][2]) < 0.0 ? -1.0 : 1.0;   // orient like the first one
+    for (int k = 0; k < 3; k++) { nh[j][k] = s * N[j][k] / len[j]; n[k] += nh[j][k]; }
+  }
+  if (live[0] && live[1] && nh[0][0] * nh[1][0] + nh[0][1] * nh[1][1] + nh[0][2] * nh[1][2] < 1.0 - 1e-9) return;   // not coplanar: no cull
+  const double nl = sqrt(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+  float nf[3], cf[3];
+  double ext = 0.0;
+  for (int k = 0; k < 3; k++) { nf[k] = (float)(n[k] / nl); cf[k] = (float)(0.5 * (lo[k] + hi[k])); ext = fmax(ext, hi[k] - lo[k]); }
+  double c = 0.0;
+  for (int k = 0; k < 3; k++) c += (double)nf[k] * ((double)t[first]->v0[k] - cf[k]);
+  const float ccf = (float)c;
+  double R = 0.0, dn[3] = { 0, 0, 0 }, q[3] = { 0, 0, 0 }, m0 = 0.0;
+  for (int j = 0; j < 2; j++) {
+    if (!live[j]) continue;
+    const float* e1 = t[j]->e1; const float* e2 = t[j]->e2; const float* a = t[j]->v0;
+    double r = -(double)ccf, sa = 0.0;
+    for (int k = 0; k < 3; k++) { r += nh[j][k] * ((double)a[k] - cf[k]); sa += fabs((double)a[k]) + fabs((double)cf[k]); }
+    R = fmax(R, fabs(r) + 1e-14 * sa);                          // (+ the double arithmetic's own rounding, generously)
+    const double W[3] = { fabs((double)e1[1] * e2[2]) + fabs((double)e1[2] * e2[1]), fabs((double)e1[2] * e2[0]) + fabs((double)e1[0] * e2[2]),
+                          fabs((double)e1[0] * e2[1]) + fabs((double)e1[1] * e2[0]) };
+    double w0 = 0.0;
+    for (int k = 0; k < 3; k++) {
+      dn[k] = fmax(dn[k], fabs((double)nf[k] - nh[j][k]) + 1e-15);
+      q[k] = fmax(q[k], 8.0 * u * W[k] / len[j]);
+      w0 += 8.0 * u * W[k] * fabs((double)cf[k] - a[k]) / len[j];
+    }
+    m0 = fmax(m0, w0);
+  }
+  if (R > 1e-6 * ext + 1e-30) return;                           // the two triangles do not share a plane: no cull
+  for (int k = 0; k < 3; k++) { p.n[k] = nf[k]; p.ctr[k] = cf[k]; p.q[k] = (float)(1.02 * (q[k] + 8.0 * u * fabs((double)nf[k]) + dn[k])); }
+  p.c = ccf;
+  p.m0 = (float)(1.02 * (m0 + 4.0 * u * fabs((double)ccf) + R) + 1e-30);
+}
+
+// May the ray (o, d: the instance's object space) meet the pair at a t in [0, lim]? false only when the exact test provably rejects both
+// triangles (see sweepPairPlane). 24 VALU instructions: traceSweep's closest-hit pair costs ~136, the occlusion pair ~126.
+HPT_HD bool sweepPairMayReach(const float n0, const float n1, const float n2, const float c, const float c0, const float c1, const float c2, const float m0,
+                              const float q0, const float q1, const float q2, const float ox, const float oy, const float oz,
+                              const float dx, const float dy, const float dz, const float lim)
+{
+  const float x = ox - c0, y = oy - c1, z = oz - c2;
+  const float s0 = __builtin_fmaf(n0, x, __builtin_fmaf(n1, y, __builtin_fmaf(n2, z, -c)));
+  const float m = __builtin_fmaf(q0, fabsf(x), __builtin_fmaf(q1, fabsf(y), __builtin_fmaf(q2, fabsf(z), m0)));
+  const float sd = __builtin_fmaf(n0, dx, __builtin_fmaf(n1, dy, n2 * dz));
+  const float md = __builtin_fmaf(q0, fabsf(dx), __builtin_fmaf(q1, fabsf(dy), q2 * fabsf(dz)));
+  const float mh = __builtin_fmaf(4.76837158203125e-7f, fabsf(s0), m);   // 8u |s0|
+  const bool away = (s0 > m) & (__builtin_fmaf(lim, sd - md, s0) > mh);
+  const bool below = (s0 < -m) & (__builtin_fmaf(lim, sd + md, s0) < -mh);
+  return !(away | below);
+}
+
 struct TexRec
 {
   uint w, h, format, flags, addrU, addrV, filter, pad;
@@ -196,6 +292,9 @@ struct DevScene
   const uint*        specTexOffsetSz;
   // sweep scenes: the instances' padded world boxes, {lo.xyz, -} {hi.xyz, -} per instance: a wave skips an instance none of its rays can reach (traceSweep)
   const float4*      sweepBoxes;
+  // sweep scenes: one SweepPlane per record pair of sweepTris (same pair index): traceSweep skips a pair none of the wave's rays can reach
+  const float4*      sweepPlanes;
+  uint               sweepCull;   // 1: traceSweep uses sweepPlanes (hpt_set_option("sweep_cull", 0 / 1)); the occlusion sweep, and the closest-hit one if built with HPT_SWEEP_CULL_CLOSEST=1
 };
 
 struct Counters { unsigned long long v[32]; };  // rays, nodes, tris, surfaceHits, shadowRays, paths, instEnter, texFetch,
