@@ -1387,7 +1387,7 @@ HPT_DEV bool traceRayFlat(const DevScene& S, const V3 wo, const V3 wd, float tne
 // every lane tests its own ray against the wave's triangle - 100 % of the lanes on every instruction. The ray is taken to each
 // instance's object space with the rows the two-level path uses and the triangle test is the shared one, so every hit (t, u, v, ids) is
 // bit-identical to the other layouts: the closest hit does not depend on the order of the tests (ties go to the lower (instId, primId)).
-// DevScene::sweepInsts: per instance {world->object rows, first triangle record, geomId, 0, triangle count}; DevScene::sweepTris: the triangle
+// DevScene::sweepInsts: per instance {world->object rows, first triangle record, geomId, per-lane flag (word 14), number of record pairs}; DevScene::sweepTris: the triangle
 // records per MESH in primitive order, padded to an even count with a degenerate record (det = 0: never hit). The two-level structure stays valid beside them (the wavefront schedule and forced layouts use it).
 typedef float f32x4n __attribute__((ext_vector_type(4)));
 typedef uint  u32x4n __attribute__((ext_vector_type(4)));
@@ -1431,6 +1431,12 @@ HPT_DEV bool triangleOccludes(const float4 a, const float4 b, const float4 c, co
 #ifndef HPT_SWEEP_CULL_CLOSEST
 #define HPT_SWEEP_CULL_CLOSEST 0
 #endif
+#ifndef HPT_SWEEP_LANES_BUILD
+#define HPT_SWEEP_LANES_BUILD 1           // 0: traceSweep's per-lane pass is compiled out (DevScene::sweepLanes is ignored)
+#endif
+#ifndef HPT_SWEEP_LANES_PLANE_CLOSEST
+#define HPT_SWEEP_LANES_PLANE_CLOSEST 0   // 1: the closest-hit sweep's per-lane pass 1 also asks the plane test (sweep_cull on): 3270 against 3343 Mpaths/s without
+#endif
 template <bool ANY, bool STATS>
 HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float tnear, const float tfar, HitRec& hit, TravStats& st)
 {
@@ -1466,6 +1472,50 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
     const V3 d = v3(r0.x * wd.x + r0.y * wd.y + r0.z * wd.z, r1.x * wd.x + r1.y * wd.y + r1.z * wd.z, r2.x * wd.x + r2.y * wd.y + r2.z * wd.z);
     if (STATS) st.insts++;
     const uint first = r3.x, pairs = r3.w;                                 // records come in pairs (the host pads an odd mesh with a record that cannot be hit)
+    if (HPT_SWEEP_LANES_BUILD && S.sweepLanes != 0u && r3.z != 0u) {
+      // Per-lane pass (instances of 2 .. 32 pairs, flagged by the host). The wave's lanes rarely agree that a pair is not needed (bounce rays go
+      // every way), but each needs one or two: pass 1 walks the pairs wave-uniformly as above, scalar loads of each pair's box (and plane), and
+      // every lane keeps a bit for each pair its ray may hit within [tnear, lim] - the widened box test (sweepBoxMayHit) AND, in the occlusion
+      // sweep with the cull on, the plane test (HPT_SWEEP_LANES_PLANE_CLOSEST: in the closest-hit sweep too). Both only drop pairs the exact test rejects (tests/cpp/sweep_lane_box_test.cpp, sweep_cull_test.cpp), and a pair that
+      // cannot hit within [tnear, lim] cannot hit later either (lim only shrinks). Pass 2: each lane fetches and tests its own pairs, in
+      // ascending order, so the tie rule of triangleTestInOrder ("the first one found stays") holds as in the wave-uniform loop.
+      const cfloat4* bp = (const cfloat4*)S.sweepPairBoxes + 2u * (first >> 1);
+      const cfloat4* pp = planes + 3u * (first >> 1);
+      V3 lid, loid; slabRay(o, d, lid, loid);
+      const float oSum = fabsf(o.x) + fabsf(o.y) + fabsf(o.z), dSum = fabsf(d.x) + fabsf(d.y) + fabsf(d.z);
+      const float lim = ANY ? tfar : hit.t;
+      const bool laneCull = (ANY || HPT_SWEEP_LANES_PLANE_CLOSEST) && S.sweepCull != 0u;
+      uint mask = 0u;
+      for (uint k = 0; k < pairs; k++) {
+        const float4 b0 = ldc4(bp + 2u * k), b1 = ldc4(bp + 2u * k + 1u), p0 = ldc4(pp + 3u * k);
+        bool may = sweepBoxMayHit(b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, p0.x, p0.y, p0.z, o.x, o.y, o.z, d.x, d.y, d.z, lid.x, lid.y, lid.z, oSum, dSum, tnear, lim);
+        if (laneCull) {
+          const float4 p1 = ldc4(pp + 3u * k + 1u), p2 = ldc4(pp + 3u * k + 2u);
+          may &= sweepPairMayReach(p0.x, p0.y, p0.z, p0.w, p1.x, p1.y, p1.z, p1.w, p2.x, p2.y, p2.z, o.x, o.y, o.z, d.x, d.y, d.z, lim + limNaN);
+        }
+        mask |= may ? (1u << k) : 0u;
+      }
+      if (!(tnear >= 0.0f)) mask = pairs >= 32u ? 0xFFFFFFFFu : (1u << pairs) - 1u;   // (the box test assumes tnear >= 0: such a lane takes every pair)
+      if (ANY && found) mask = 0u;
+      const float4* tv = (const float4*)S.sweepTris + 3u * first;
+      while (mask != 0u) {
+        const uint k = __builtin_ctz(mask);
+        mask &= mask - 1u;
+        const float4* tp = tv + 6u * k;
+        const float4 a0 = tp[0], b0 = tp[1], c0 = tp[2], a1 = tp[3], b1 = tp[4], c1 = tp[5];
+        if (STATS) { st.tris += 2; if (firstActiveLane()) { st.waveTriIters += 2; st.wavePairTrips[ANY ? 1 : 0]++; } }
+        if (ANY) {
+          found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar);
+          found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar);
+          if (found) mask = 0u;
+        } else {
+          triangleTestInOrder(a0, b0, c0, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+          triangleTestInOrder(a1, b1, c1, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+        }
+      }
+      if (ANY && __ballot(!found) == 0ull) return true;                    // every lane of the wave that traces a ray has its occluder
+      continue;
+    }
     const cfloat4* tp = tris + 3u * first;
     const cfloat4* pp = planes + 3u * (first >> 1);                       // (an instance's records start at an even index: meshes are padded to pairs)
     for (uint k = 0; k < pairs; k++, tp += 6, pp += 3) {

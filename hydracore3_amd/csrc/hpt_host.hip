@@ -50,6 +50,10 @@ static const size_t SWEEP_MAX_TRIS = 32, SWEEP_MAX_INSTS = 8;
 #ifndef HPT_SWEEP_CULL
 #define HPT_SWEEP_CULL 1
 #endif
+// Per-lane pair pass of the sweep (hpt_types.h: sweepPairBox, hpt_device.h: traceSweep): on by default, hpt_set_option("sweep_lanes", 0) for A/B.
+#ifndef HPT_SWEEP_LANES
+#define HPT_SWEEP_LANES 1
+#endif
 static const size_t MANY_INSTANCES = 6;                      // instances from which the single-level layout is chosen for light scenes too (see hpt_commit_scene)
 
 namespace {
@@ -98,7 +102,7 @@ struct hpt_ctx
   uint stackNeeded = 0;
 
   // device buffers
-  DevBuf<BvhNode> dNodes; DevBuf<BvhTri> dTris; DevBuf<BvhInst> dInsts, dSweepInsts; DevBuf<BvhTri> dSweepTris; DevBuf<float> dSweepBoxes; DevBuf<SweepPlane> dSweepPlanes;
+  DevBuf<BvhNode> dNodes; DevBuf<BvhTri> dTris; DevBuf<BvhInst> dInsts, dSweepInsts; DevBuf<BvhTri> dSweepTris; DevBuf<float> dSweepBoxes; DevBuf<SweepPlane> dSweepPlanes; DevBuf<SweepPairBox> dSweepPairBoxes;
   DevBuf<uint> dTriIndices, dMatIdByPrim, dMatVertOffset, dPackedXY;
   DevBuf<float> dVData, dNormMat;
   DevBuf<int> dRemapInst, dRemapLists;
@@ -123,6 +127,7 @@ struct hpt_ctx
   bool shadeTrisDirty = true, shadeTrisEnabled = true;   // (hpt_set_option("shade_records", 0): the kernels gather vertex data through the index chain)
   int  buildThreads = 0;                                 // hpt_set_option("build_threads", n): host threads of CommitScene (0: automatic)
   uint sweepCull = HPT_SWEEP_CULL;                       // hpt_set_option("sweep_cull", 0 / 1): the sweep skips the record pairs no ray of the wave can reach (DevScene::sweepCull)
+  uint sweepLanes = HPT_SWEEP_LANES;                     // hpt_set_option("sweep_lanes", 0 / 1): the sweep tests each lane's candidate pairs only (DevScene::sweepLanes)
   bool statsWide = false;                                // hpt_set_option("stats_wide", 1): the instrumented probe walks the 4-wide tree (what a wavefront call on this scene does)
   bool wideEnabled = true;                               // hpt_set_option("wide_nodes", 0): the trace kernel walks the BVH2
   std::vector<uint> levelOffsets;                        // nodes of level l = dLevelNodes[levelOffsets[l] .. levelOffsets[l + 1])
@@ -244,7 +249,7 @@ try {
   (void)hipDeviceSynchronize();
   (void)hpt_comm_destroy(c);
   lbvhDestroy(c->lbvh); c->lbvh = nullptr;
-  c->dNodes.release(); c->dTris.release(); c->dInsts.release(); c->dSweepInsts.release(); c->dSweepTris.release(); c->dSweepBoxes.release(); c->dSweepPlanes.release(); c->dLevelNodes.release(); c->dShadeTris.release(); c->dNodes4.release(); c->dNodes4Src.release(); c->dTriBox.release(); c->dNodeBounds.release(); c->dInstO2W.release(); c->dTriIndices.release(); c->dMatIdByPrim.release();
+  c->dNodes.release(); c->dTris.release(); c->dInsts.release(); c->dSweepInsts.release(); c->dSweepTris.release(); c->dSweepBoxes.release(); c->dSweepPlanes.release(); c->dSweepPairBoxes.release(); c->dLevelNodes.release(); c->dShadeTris.release(); c->dNodes4.release(); c->dNodes4Src.release(); c->dTriBox.release(); c->dNodeBounds.release(); c->dInstO2W.release(); c->dTriIndices.release(); c->dMatIdByPrim.release();
   c->dMatVertOffset.release(); c->dPackedXY.release(); c->dVData.release(); c->dNormMat.release(); c->dRemapInst.release();
   c->dRemapLists.release(); c->dMaterials.release(); c->dLights.release(); c->dTextures.release(); c->dArrays1f.release(); c->dSpecValues.release(); c->dSpecOffsetSz.release(); c->dCieXYZ.release(); c->dFilmsEtaK.release(); c->dPrecompFilms.release(); c->dFilmsSpecId.release(); c->dSpecTexIdsWavelengths.release(); c->dSpecTexOffsetSz.release(); c->dGens.release();
   c->dQueue.release(); c->dStackOvf.release(); c->dCounters.release(); c->dFrame.release(); c->dRecord.release(); c->dRef.release(); c->dData.release();
@@ -895,8 +900,13 @@ try {
     std::vector<SweepPlane> sp((st.size() + 1) / 2);
     for (size_t k = 0; k < sp.size(); k++) sweepPairPlane(st[2 * k], 2 * k + 1 < st.size() ? st[2 * k + 1] : st[2 * k], sp[k]);
     HIPCHK(c, c->dSweepPlanes.upload(sp.data(), sp.size()));
+    // one box per record pair (traceSweep's per-lane pass; hpt_types.h: sweepPairBox)
+    std::vector<SweepPairBox> sbx(sp.size());
+    for (size_t k = 0; k < sbx.size(); k++) sweepPairBox(st[2 * k], 2 * k + 1 < st.size() ? st[2 * k + 1] : st[2 * k], sbx[k]);
+    HIPCHK(c, c->dSweepPairBoxes.upload(sbx.data(), sbx.size()));
     std::vector<BvhInst> sw(dinst);
-    for (size_t i = 0; i < ni; i++) { const uint g = c->insts[i].geomId; sw[i].root = geomTriBase[g]; sw[i].pad0 = 0; sw[i].pad1 = (uint)(c->geoms[g].tris.size() + 1) / 2u; }
+    for (size_t i = 0; i < ni; i++) { const uint g = c->insts[i].geomId; sw[i].root = geomTriBase[g]; sw[i].pad1 = (uint)(c->geoms[g].tris.size() + 1) / 2u;
+                                 sw[i].pad0 = sw[i].pad1 >= 2u && sw[i].pad1 <= 32u ? 1u : 0u; }   // per-lane pass: 2 .. 32 pairs (a 32-bit mask per lane)
     HIPCHK(c, c->dSweepInsts.upload(sw.data(), sw.size()));
     // the instances' padded world boxes (over their triangles' world-space vertices): traceSweep's wave-uniform skip
     std::vector<float> sb(8 * std::max<size_t>(ni, 1), 0.0f);
@@ -916,6 +926,7 @@ try {
   }
   c->S.sweep = sweep ? 1u : 0u; c->S.sweepInsts = sweep ? c->dSweepInsts.p : nullptr; c->S.sweepTris = sweep ? c->dSweepTris.p : nullptr; c->S.sweepBoxes = sweep ? (const float4*)c->dSweepBoxes.p : nullptr;
   c->S.sweepPlanes = sweep ? (const float4*)c->dSweepPlanes.p : nullptr; c->S.sweepCull = sweep ? c->sweepCull : 0u;
+  c->S.sweepPairBoxes = sweep ? (const float4*)c->dSweepPairBoxes.p : nullptr; c->S.sweepLanes = sweep ? c->sweepLanes : 0u;
   if (nodes.empty()) nodes.push_back(BvhNode());           // keep the pointers valid
   if (tris.empty()) tris.push_back(BvhTri());
   HIPCHK(c, c->dNodes.upload(nodes.data(), nodes.size()));
@@ -2357,6 +2368,7 @@ try {
   else if (k == "build_threads") c->buildThreads = std::min(value, 64);                // host threads CommitScene builds its trees with (0: the usable cores, at most 16)
   else if (k == "stats_wide") c->statsWide = value != 0;
   else if (k == "sweep_cull") { if (value > 1) return c->fail(HPT_ERR_ARG, "sweep_cull: 0 off, 1 on"); c->sweepCull = (uint)value; if (c->S.sweep) c->S.sweepCull = c->sweepCull; }
+  else if (k == "sweep_lanes") { if (value < 0 || value > 1) return c->fail(HPT_ERR_ARG, "sweep_lanes: 0 off, 1 on"); c->sweepLanes = (uint)value; if (c->S.sweep) c->S.sweepLanes = c->sweepLanes; }
   else if (k == "bw_refill_below") { if (value < 1 || value > 64) return c->fail(HPT_ERR_ARG, "bw_refill_below: 1..64"); c->bwRefillBelow = (uint)value; }
   else if (k == "bw_wide") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "bw_wide: -1 automatic, 0, 1"); c->bwWide = value; }
   else if (k == "bw_node_min") { if (value < 0 || value > 64) return c->fail(HPT_ERR_ARG, "bw_node_min: 0..64"); c->bwNodeMin = (uint)value; }

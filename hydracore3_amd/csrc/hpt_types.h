@@ -214,6 +214,69 @@ HPT_HD bool sweepPairMayReach(const float n0, const float n1, const float n2, co
   return !(away | below);
 }
 
+// ---- sweep pair boxes (traceSweep's per-lane pass) ------------------------------------------------------------------------------------------
+// One box per record PAIR of DevScene::sweepTris, in the instance's object space, around the vertices as the exact test sees them (v0, v0 + e1,
+// v0 + e2 of both triangles), padded like the BVH's node boxes (bvh_build.h: Aabb::pad), {lo.xyz, k1} {hi.xyz, k0}.
+// The padding alone does not make the box conservative against the exact float test: Moeller-Trumbore's u, v and t carry errors that grow with
+// the distance |o - v0| and with 1 / cos of the angle between the ray and the plane (det = |N| n^.d), so a far or oblique ray can be accepted
+// a little outside the triangle. The point o + t d the test accepts lies within C u |o - v0| / (sin(phi) cos(theta)) of the triangle (phi: the
+// triangle's angle at v0, |N| = |e1| |e2| sin(phi); C is EMPIRICAL, not derived: tests/cpp/sweep_lane_box_test.cpp misses 8 999 of 24 M hits
+// with C = 0 and none with C = 1; C = 4 keeps a factor 4 over that). Each
+// lane therefore widens the box by delta = k1 |o|_1 + k0 (|o - v0| <= |o|_1 + |v0|_1), k1 = C u / (sin(phi) SIGMA), k0 = k1 max |v0|_1, and takes
+// the pair whatever the box says when |n.d| < SIGMA |d|_1 (n: the pair's plane, SweepPlane; n = 0 when not coplanar: always taken).
+// A padding-only pair gets a point box without widening: it may be taken, and then never hits.
+static const float SWEEP_GRAZE = 1.0e-3f;
+struct SweepPairBox { float lo[3], k1; float hi[3], k0; };
+static_assert(sizeof(SweepPairBox) == 32, "pair box must be two float4");
+
+HPT_HD void sweepPairBox(const BvhTri& t0, const BvhTri& t1, SweepPairBox& b)
+{
+  const double u = 1.0 / 16777216.0, C = 4.0;
+  const BvhTri* t[2] = { &t0, &t1 };
+  double lo[3] = { 1e300, 1e300, 1e300 }, hi[3] = { -1e300, -1e300, -1e300 }, k1 = 0.0, m = 0.0;
+  bool any = false, finite = true;
+  for (int j = 0; j < 2; j++) {
+    const float* a = t[j]->v0; const float* e1 = t[j]->e1; const float* e2 = t[j]->e2;
+    bool live = false;                                          // the padding record is all zero: d x e2 = 0, det = 0, never hit
+    for (int k = 0; k < 3; k++) live |= e1[k] != 0.0f || e2[k] != 0.0f;
+    if (!live) continue;
+    any = true;
+    double l1 = 0.0, l2 = 0.0, N[3] = { (double)e1[1] * e2[2] - (double)e1[2] * e2[1], (double)e1[2] * e2[0] - (double)e1[0] * e2[2], (double)e1[0] * e2[1] - (double)e1[1] * e2[0] }, av = 0.0;
+    for (int k = 0; k < 3; k++) {
+      const double v[3] = { (double)a[k], (double)a[k] + e1[k], (double)a[k] + e2[k] };
+      for (int w = 0; w < 3; w++) { finite &= isfinite(v[w]) != 0; lo[k] = fmin(lo[k], v[w]); hi[k] = fmax(hi[k], v[w]); }
+      l1 += (double)e1[k] * e1[k]; l2 += (double)e2[k] * e2[k]; av += fabs((double)a[k]);
+    }
+    const double sinphi = sqrt(N[0] * N[0] + N[1] * N[1] + N[2] * N[2]) / sqrt(l1 * l2);
+    k1 = fmax(k1, sinphi > 0.0 ? C * u / (sinphi * SWEEP_GRAZE) : INFINITY);
+    m = fmax(m, av);
+  }
+  if (!any) { for (int k = 0; k < 3; k++) { b.lo[k] = 0.0f; b.hi[k] = 0.0f; } b.k1 = b.k0 = 0.0f; return; }
+  if (!finite || !(k1 < 1e30)) { for (int k = 0; k < 3; k++) { b.lo[k] = -INFINITY; b.hi[k] = INFINITY; } b.k1 = b.k0 = 0.0f; return; }   // (never skipped)
+  double ex = 0.0, mag = 0.0;
+  for (int k = 0; k < 3; k++) { ex = fmax(ex, hi[k] - lo[k]); mag = fmax(mag, fmax(fabs(lo[k]), fabs(hi[k]))); }
+  const double p = 1e-5 * fmax(ex, mag) + 1e-30;
+  for (int k = 0; k < 3; k++) { b.lo[k] = (float)(lo[k] - p); b.hi[k] = (float)(hi[k] + p); }
+  b.k1 = (float)(k1 * 1.01); b.k0 = (float)(k1 * 1.01 * m * 1.01);
+}
+
+// May the ray meet the pair at a t in [tnear, lim], tnear >= 0? Object space: o, d, id (slabRay's clamped reciprocal), oSum = |o|_1,
+// dSum = |d|_1; the pair's box (lo, hi, k1, k0) and its plane normal n (SweepPlane::n). The slab test of the instance-box skip in traceSweep
+// with its widening (as nodeSlabs), on the box widened by delta = k1 oSum + k0, or true for a ray within SWEEP_GRAZE of the plane. false only
+// when the exact triangle tests of the pair reject the interval (tests/cpp/sweep_lane_box_test.cpp).
+HPT_HD bool sweepBoxMayHit(const float lo0, const float lo1, const float lo2, const float k1, const float hi0, const float hi1, const float hi2, const float k0,
+                           const float n0, const float n1, const float n2, const float ox, const float oy, const float oz, const float dx, const float dy, const float dz,
+                           const float ix, const float iy, const float iz, const float oSum, const float dSum, const float tnear, const float lim)
+{
+  const float del = __builtin_fmaf(k1, oSum, k0);
+  const float wx = del * fabsf(ix), wy = del * fabsf(iy), wz = del * fabsf(iz);
+  const float ax0 = (lo0 - ox) * ix, ax1 = (hi0 - ox) * ix, ay0 = (lo1 - oy) * iy, ay1 = (hi1 - oy) * iy, az0 = (lo2 - oz) * iz, az1 = (hi2 - oz) * iz;
+  const float tn = fmaxf(fmaxf(fminf(ax0, ax1) - wx, fminf(ay0, ay1) - wy), fmaxf(fminf(az0, az1) - wz, tnear));
+  const float tf = fminf(fminf(fmaxf(ax0, ax1) + wx, fmaxf(ay0, ay1) + wy), fminf(fmaxf(az0, az1) + wz, lim));
+  const float sd = __builtin_fmaf(n0, dx, __builtin_fmaf(n1, dy, n2 * dz));
+  return (fabsf(sd) < SWEEP_GRAZE * dSum) | (tn * 0.999999f <= tf * 1.000001f);
+}
+
 struct TexRec
 {
   uint w, h, format, flags, addrU, addrV, filter, pad;
@@ -258,7 +321,7 @@ struct DevScene
   const float*       instMotion;  // 24 floats per instance: object->world rows (3x4) at time 0, then at time 1 (only read for BvhInst::pad0 != 0)
   const float*       normMat2;    // 12 floats per instance: rows of the upper 3x3 of m_normMatrices[m_normMatrices2Offs + i]
   uint               motion;      // m_normMatrices2Offs != 0: a time is drawn per path and normals are interpolated
-  uint               sweep;       // 1: the scene is small enough for the wave-uniform triangle sweep (traceSweep); BvhInst::root / pad1 = the instance's triangle range
+  uint               sweep;       // 1: the scene is small enough for the wave-uniform triangle sweep (traceSweep); BvhInst::root = the instance's first triangle record, pad1 = its number of record pairs, pad0 (word 14) = 1: the per-lane pass (sweepLanes)
   // lens simulation (integrator_pt.cpp:78-104, 806-938): m_lines as {curvatureRadius, thickness, eta, apertureRadius}, film side first
   const float4*      lensLines;   // lensCount entries; lensCount = 0: m_enableOpticSim off
   uint               lensCount;
@@ -295,6 +358,9 @@ struct DevScene
   // sweep scenes: one SweepPlane per record pair of sweepTris (same pair index): traceSweep skips a pair none of the wave's rays can reach
   const float4*      sweepPlanes;
   uint               sweepCull;   // 1: traceSweep uses sweepPlanes (hpt_set_option("sweep_cull", 0 / 1)); the occlusion sweep, and the closest-hit one if built with HPT_SWEEP_CULL_CLOSEST=1
+  // sweep scenes: one SweepPairBox per record pair of sweepTris (same pair index): traceSweep's per-lane pass
+  const float4*      sweepPairBoxes;
+  uint               sweepLanes;  // 1: traceSweep takes the instances flagged in sweepInsts (word 14) through the per-lane pass (hpt_set_option("sweep_lanes", 0 / 1))
 };
 
 struct Counters { unsigned long long v[32]; };  // rays, nodes, tris, surfaceHits, shadowRays, paths, instEnter, texFetch,
