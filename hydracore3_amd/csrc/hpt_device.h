@@ -1119,6 +1119,13 @@ typedef float f32x2 __attribute__((ext_vector_type(2)));
 #ifndef HPT_PACKED_SLABS
 #define HPT_PACKED_SLABS 0   // measured: v_pk_add/mul_f32 (12 instead of 24 instructions) is NOT faster here: Cornell 1805 vs 1820, 1M triangles 200 vs 206
 #endif
+// The widened overlap test of a slab interval [tn, tf]. With tnear >= 0, tn >= 0 and the two factors widen the interval (a negative tf fails either
+// way). A ray query may pass tnear < 0: then both ends can be negative, where the same factors NARROW the interval and lose hits behind the origin
+// in flat boxes, so such a ray widens each end by its own magnitude. The path tracer passes tnear = 0.0f as a constant: the select folds away there.
+HPT_DEV bool slabOverlap(const float tn, const float tf, const float tnear)
+{
+  return tnear >= 0.0f ? (tn * 0.999999f <= tf * 1.000001f) : (tn - fabsf(tn) * 1e-6f <= tf + fabsf(tf) * 1e-6f);
+}
 HPT_DEV void nodeSlabs(const float4 q0, const float4 q1, const float4 q2, const V3 oid, const V3 id, const float tnear, const float best,
                        bool& h0, bool& h1, float& t0n, float& t1n)
 {
@@ -1135,8 +1142,8 @@ HPT_DEV void nodeSlabs(const float4 q0, const float4 q1, const float4 q2, const 
   const float t0f = fminf(fminf(fmaxf(ax.x, ax.y), fmaxf(ay.x, ay.y)), fminf(fmaxf(az.x, az.y), best));
   t1n = fmaxf(fmaxf(fminf(bx.x, bx.y), fminf(by.x, by.y)), fmaxf(fminf(bz.x, bz.y), tnear));
   const float t1f = fminf(fminf(fmaxf(bx.x, bx.y), fmaxf(by.x, by.y)), fminf(fmaxf(bz.x, bz.y), best));
-  h0 = (t0n * 0.999999f <= t0f * 1.000001f);
-  h1 = (t1n * 0.999999f <= t1f * 1.000001f);
+  h0 = slabOverlap(t0n, t0f, tnear);
+  h1 = slabOverlap(t1n, t1f, tnear);
 }
 
 // Moeller-Trumbore on a 48-byte record (v0, e1, e2): exact (IEEE) arithmetic, inclusive [tnear, current best], no back-face culling; at equal
@@ -1290,16 +1297,20 @@ HPT_DEV void wideNodeStep(const DevScene& S, const TravStack& stk, const V3 oid,
   const float bx = __builtin_fmaf(__uint_as_float(w0.x), id.x, -oid.x), by = __builtin_fmaf(__uint_as_float(w0.y), id.y, -oid.y), bz = __builtin_fmaf(__uint_as_float(w0.z), id.z, -oid.z);
   const bool negX = id.x < 0.0f, negY = id.y < 0.0f, negZ = id.z < 0.0f;
   const uint nX = negX ? w1.w : w1.x, fX = negX ? w1.x : w1.w, nY = negY ? w2.x : w1.y, fY = negY ? w1.y : w2.x, nZ = negZ ? w2.y : w1.z, fZ = negZ ? w1.z : w2.y;
-  const float bestW = best * 1.0000021f;                                                       // (tn * 0.999999 <= tf * 1.000001 of nodeSlabs, as one factor on the far side)
+  // (tn * 0.999999 <= tf * 1.000001 of nodeSlabs, as one factor on the far side; with tnear < 0 (ray queries) tf may be negative, where the factor
+  // would narrow the interval: slabOverlap's form instead, folded away for the path tracer's constant tnear = 0)
+  const bool behind = !(tnear >= 0.0f);
+  const float bestW = behind ? best + fabsf(best) * 2.1e-6f : best * 1.0000021f;
   uint key[4], ref[4] = { w3.x, w3.y, w3.z, w3.w };
 #pragma unroll
   for (int c = 0; c < 4; c++) {
     const float tnx = __builtin_fmaf(ubyteToFloat(nX, c), sx, bx), tny = __builtin_fmaf(ubyteToFloat(nY, c), sy, by), tnz = __builtin_fmaf(ubyteToFloat(nZ, c), sz, bz);
     const float tfx = __builtin_fmaf(ubyteToFloat(fX, c), sx, bx), tfy = __builtin_fmaf(ubyteToFloat(fY, c), sy, by), tfz = __builtin_fmaf(ubyteToFloat(fZ, c), sz, bz);
     const float tn = fmaxf(fmaxf(tnx, tny), fmaxf(tnz, tnear));
-    const float tf = fminf(fminf(fminf(tfx, tfy), tfz) * 1.0000021f, bestW);
+    const float tfm = fminf(fminf(tfx, tfy), tfz);
+    const float tf = fminf(behind ? tfm + fabsf(tfm) * 2.1e-6f : tfm * 1.0000021f, bestW);
     const bool hit = (tn <= tf) & (((w0.w >> (24 + c)) & 1u) != 0u);
-    key[c] = hit ? (((__float_as_uint(tn) & 0x7FFFFFFCu)) | (uint)c) : 0xFFFFFFFFu;        // tn >= 0: its bit pattern orders like the value
+    key[c] = hit ? (((__float_as_uint(tn) & 0x7FFFFFFCu)) | (uint)c) : 0xFFFFFFFFu;        // tn >= 0: its bit pattern orders like the value (tnear < 0 only reorders the visits)
   }
 #define HPT_CE(a, b) do { const bool sw = key[b] < key[a]; const uint ka = sw ? key[b] : key[a], kb = sw ? key[a] : key[b], ra = sw ? ref[b] : ref[a], rb = sw ? ref[a] : ref[b]; \
                           key[a] = ka; key[b] = kb; ref[a] = ra; ref[b] = rb; } while (0)
@@ -1465,7 +1476,7 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
       const float ax0 = (blo.x - wo.x) * id.x, ax1 = (bhi.x - wo.x) * id.x, ay0 = (blo.y - wo.y) * id.y, ay1 = (bhi.y - wo.y) * id.y, az0 = (blo.z - wo.z) * id.z, az1 = (bhi.z - wo.z) * id.z;
       const float tn = fmaxf(fmaxf(fminf(ax0, ax1), fminf(ay0, ay1)), fmaxf(fminf(az0, az1), tnear));
       const float tf = fminf(fminf(fmaxf(ax0, ax1), fmaxf(ay0, ay1)), fminf(fmaxf(az0, az1), lim));
-      if (__ballot(tn * 0.999999f <= tf * 1.000001f) == 0ull) continue;
+      if (__ballot(slabOverlap(tn, tf, tnear)) == 0ull) continue;
     }
     // toObjectSpace (same expressions, same order)
     const V3 o = v3(r0.x * wo.x + r0.y * wo.y + r0.z * wo.z + r0.w, r1.x * wo.x + r1.y * wo.y + r1.z * wo.z + r1.w, r2.x * wo.x + r2.y * wo.y + r2.z * wo.z + r2.w);

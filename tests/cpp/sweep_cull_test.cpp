@@ -61,6 +61,22 @@ static BvhTri tri(V a, V b, V c)
   return t;
 }
 static float maxcomp(V p) { return std::max(p.x, std::max(p.y, p.z)); }
+// world -> object rows of an instance matrix (column-major 4x4, affine): hpt_host.hip: inverse_rows, line by line
+static void inverse_rows(const float* m, float row0[4], float row1[4], float row2[4])
+{
+  const double a00 = m[0], a01 = m[4], a02 = m[8],  tx = m[12];
+  const double a10 = m[1], a11 = m[5], a12 = m[9],  ty = m[13];
+  const double a20 = m[2], a21 = m[6], a22 = m[10], tz = m[14];
+  const double c00 = a11 * a22 - a12 * a21, c01 = a12 * a20 - a10 * a22, c02 = a10 * a21 - a11 * a20;
+  const double det = a00 * c00 + a01 * c01 + a02 * c02;
+  const double id = 1.0 / det;
+  const double i00 = c00 * id, i01 = (a02 * a21 - a01 * a22) * id, i02 = (a01 * a12 - a02 * a11) * id;
+  const double i10 = c01 * id, i11 = (a00 * a22 - a02 * a20) * id, i12 = (a02 * a10 - a00 * a12) * id;
+  const double i20 = c02 * id, i21 = (a01 * a20 - a00 * a21) * id, i22 = (a00 * a11 - a01 * a10) * id;
+  row0[0] = (float)i00; row0[1] = (float)i01; row0[2] = (float)i02; row0[3] = (float)(-(i00 * tx + i01 * ty + i02 * tz));
+  row1[0] = (float)i10; row1[1] = (float)i11; row1[2] = (float)i12; row1[3] = (float)(-(i10 * tx + i11 * ty + i12 * tz));
+  row2[0] = (float)i20; row2[1] = (float)i21; row2[2] = (float)i22; row2[3] = (float)(-(i20 * tx + i21 * ty + i22 * tz));
+}
 
 int main()
 {
@@ -70,7 +86,13 @@ int main()
   auto unit = [&]() { double x, y, z, l; do { x = uni(-1, 1); y = uni(-1, 1); z = uni(-1, 1); l = x * x + y * y + z * z; } while (l > 1.0 || l < 1e-6);
                       l = std::sqrt(l); return std::array<double, 3>{ x / l, y / l, z / l }; };
   long long rays = 0, culled = 0, bad = 0, ownWall = 0, ownCulled = 0, bentPairs = 0, bentCulling = 0;
-  const int QUADS = 40000, RAYS = 100;
+  const int QUADS = 40000, RAYS = 100, IRAYS = 30;
+  // the instanced class draws from its own generator, so the rays of the classes above stay what they were
+  std::mt19937 rng2(20261019);
+  auto uni2 = [&](double a, double b) { return a + (b - a) * U(rng2); };
+  auto unit2 = [&]() { double x, y, z, l; do { x = uni2(-1, 1); y = uni2(-1, 1); z = uni2(-1, 1); l = x * x + y * y + z * z; } while (l > 1.0 || l < 1e-6);
+                       l = std::sqrt(l); return std::array<double, 3>{ x / l, y / l, z / l }; };
+  long long irays = 0, iculled = 0, ihits = 0;
   for (int qi = 0; qi < QUADS; qi++) {
     const double scale = std::pow(10.0, uni(-3.0, 4.0));
     const bool axis = (qi & 1) == 0;
@@ -151,6 +173,76 @@ int main()
         bad++;
       }
     }
+    // instanced rays: a unit WORLD ray taken to the quad's object space the way the sweep does it - the instance's world -> object rows
+    // (inverse_rows above) and traceSweep's toObjectSpace expressions in the same order - so the object-space direction has any length and
+    // orientation. Instances: rotation, scales 1e-2 .. 1e2 per axis, a mirror (one in three), a shear (one in three), translations up to 1e3.
+    // World rays leave the world surface from the renderer's offset (into the half-space, grazing, or coming back) or come from anywhere
+    // with a segment ending a relative 1e-5 short of or past the plane.
+    for (int ri = 0; ri < IRAYS; ri++) {
+      const int kind = ri % 4;
+      double L[3][3], T[3];
+      {
+        const std::array<double, 3> ax = unit2(); const double an = uni2(0.0, 6.283185307179586), c = std::cos(an), sn = std::sin(an), k = 1.0 - c;
+        const double Rm[3][3] = { { c + ax[0] * ax[0] * k, ax[0] * ax[1] * k - ax[2] * sn, ax[0] * ax[2] * k + ax[1] * sn },
+                                  { ax[1] * ax[0] * k + ax[2] * sn, c + ax[1] * ax[1] * k, ax[1] * ax[2] * k - ax[0] * sn },
+                                  { ax[2] * ax[0] * k - ax[1] * sn, ax[2] * ax[1] * k + ax[0] * sn, c + ax[2] * ax[2] * k } };
+        double sc[3]; for (double& x : sc) x = std::pow(10.0, uni2(-2.0, 2.0));
+        if (rng2() % 3u == 0u) sc[rng2() % 3u] *= -1.0;                                 // mirror
+        double Sh[3][3] = { { 1, 0, 0 }, { 0, 1, 0 }, { 0, 0, 1 } };
+        if (rng2() % 3u == 0u) { Sh[0][1] = uni2(-1.5, 1.5); Sh[1][2] = uni2(-1.5, 1.5); Sh[0][2] = uni2(-1.5, 1.5); }
+        for (int r = 0; r < 3; r++) for (int q = 0; q < 3; q++) { double a = 0.0; for (int k2 = 0; k2 < 3; k2++) a += Sh[r][k2] * Rm[k2][q]; L[r][q] = a * sc[q]; }
+        for (double& x : T) x = uni2(-1.0, 1.0) * std::pow(10.0, uni2(-1.0, 3.0));
+      }
+      float m[16];                                                       // column-major 4x4, as the host keeps an instance matrix
+      for (int r = 0; r < 3; r++) { for (int q = 0; q < 3; q++) m[4 * q + r] = (float)L[r][q]; m[12 + r] = (float)T[r]; m[3 + 4 * r] = 0.0f; }
+      m[15] = 1.0f;
+      float row0[4], row1[4], row2[4];
+      inverse_rows(m, row0, row1, row2);
+      auto toWorld = [&](double x, double y, double z) { std::array<double, 3> w; for (int r = 0; r < 3; r++) w[r] = (double)m[r] * x + (double)m[4 + r] * y + (double)m[8 + r] * z + (double)m[12 + r]; return w; };
+      const double a = uni2(-1.2, 1.2), b = uni2(-1.2, 1.2);
+      const std::array<double, 3> hw = toWorld(cx + a * hu * tu[0] + b * hv * tv[0], cy + a * hu * tu[1] + b * hv * tv[1], cz + a * hu * tu[2] + b * hv * tv[2]);
+      std::array<double, 3> nw;                                          // the world plane's normal (inverse transpose)
+      for (int r = 0; r < 3; r++) nw[r] = (double)row0[r] * nrm[0] + (double)row1[r] * nrm[1] + (double)row2[r] * nrm[2];
+      { const double l = std::sqrt(nw[0] * nw[0] + nw[1] * nw[1] + nw[2] * nw[2]); for (double& x : nw) x /= l; }
+      const double side = (ri & 4) ? 1.0 : -1.0;
+      double wo[3], wd[3], lim;
+      if (kind <= 2) {
+        const float hp[3] = { (float)hw[0], (float)hw[1], (float)hw[2] };
+        const float h = std::max(std::max(hp[0], std::max(hp[1], hp[2])), 1.0f) * 5e-6f;
+        for (int k = 0; k < 3; k++) wo[k] = (double)(hp[k] + (float)(side * nw[k]) * h);
+        std::array<double, 3> w = unit2();
+        double wn = w[0] * nw[0] + w[1] * nw[1] + w[2] * nw[2];
+        if (kind == 1) { const double g = std::pow(10.0, uni2(-7.0, -1.0)); for (int k = 0; k < 3; k++) w[k] = w[k] - wn * nw[k] + g * side * nw[k]; }
+        else if ((wn * side < 0) != (kind == 2)) { for (double& x : w) x = -x; }
+        const double wl = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
+        for (int k = 0; k < 3; k++) wd[k] = w[k] / wl;
+        lim = ri % 3 == 0 ? FLT_MAX : std::fabs(scale) * uni2(0.0, 4.0) * 10.0;
+      } else {
+        const std::array<double, 3> w = unit2();
+        const double dist = std::max(scale, 1e-3) * std::pow(10.0, uni2(-3.0, 2.0));
+        double dd[3], l = 0.0;
+        for (int k = 0; k < 3; k++) wo[k] = (double)(float)(hw[k] + w[k] * dist);
+        for (int k = 0; k < 3; k++) { dd[k] = hw[k] - wo[k]; l += dd[k] * dd[k]; }
+        l = std::sqrt(l); if (!(l > 0.0)) continue;
+        for (int k = 0; k < 3; k++) wd[k] = dd[k] / l;
+        lim = l * (1.0 + uni2(-1e-5, 1e-5));
+        if (ri % 7 == 0) lim = FLT_MAX;
+      }
+      const V fo = v((float)wo[0], (float)wo[1], (float)wo[2]), fd = v((float)wd[0], (float)wd[1], (float)wd[2]);
+      // traceSweep's toObjectSpace, the same expressions in the same order
+      const V o = v(row0[0] * fo.x + row0[1] * fo.y + row0[2] * fo.z + row0[3], row1[0] * fo.x + row1[1] * fo.y + row1[2] * fo.z + row1[3], row2[0] * fo.x + row2[1] * fo.y + row2[2] * fo.z + row2[3]);
+      const V d = v(row0[0] * fd.x + row0[1] * fd.y + row0[2] * fd.z, row1[0] * fd.x + row1[1] * fd.y + row1[2] * fd.z, row2[0] * fd.x + row2[1] * fd.y + row2[2] * fd.z);
+      const float flim = (float)lim, tnear = 0.0f;
+      irays++;
+      const bool hit = occludes(t0, o, d, tnear, flim) || occludes(t1, o, d, tnear, flim) || closerHit(t0, o, d, tnear, flim, false) || closerHit(t1, o, d, tnear, flim, false);
+      ihits += hit;
+      if (sweepPairMayReach(p.n[0], p.n[1], p.n[2], p.c, p.ctr[0], p.ctr[1], p.ctr[2], p.m0, p.q[0], p.q[1], p.q[2], o.x, o.y, o.z, d.x, d.y, d.z, flim + 0.0f)) continue;
+      iculled++;
+      if (hit) {
+        if (bad < 10) std::printf("MISSED (instanced) quad %d ray %d scale %g axis %d: o (%.9g %.9g %.9g) d (%.9g %.9g %.9g) lim %.9g\n", qi, ri, scale, (int)axis, o.x, o.y, o.z, d.x, d.y, d.z, flim);
+        bad++;
+      }
+    }
   }
   // a ray with tnear < 0 is never culled (traceSweep passes lim = NaN for it)
   {
@@ -161,6 +253,8 @@ int main()
   }
   std::printf("%lld rays, %lld culled (%.1f %%), %lld missed hits; own wall (axis-aligned) culled %.2f %% of %lld; bent pairs allowed to cull: %lld of %lld\n",
               rays, culled, 100.0 * culled / rays, bad, 100.0 * ownCulled / std::max(1LL, ownWall), ownWall, bentCulling, bentPairs);
-  if (bad == 0 && bentCulling == 0 && ownCulled * 10 > ownWall * 9) std::printf("all conservative\n");
+  std::printf("instanced (object-space rays through inverse_rows): %lld rays, %lld culled (%.1f %%), %lld exact hits\n", irays, iculled,
+              100.0 * iculled / std::max(1LL, irays), ihits);
+  if (bad == 0 && bentCulling == 0 && ownCulled * 10 > ownWall * 9 && iculled > irays / 10 && ihits > irays / 20) std::printf("all conservative\n");
   return bad == 0 ? 0 : 1;
 }
