@@ -87,7 +87,15 @@ ABI = {
     "hpt_set_option": (_i, [_vp, C.c_char_p, _i]),
     "hpt_get_commit_time": (_i, [_vp, C.POINTER(_f)]),
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
+    "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
+    "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
 }
+
+# hpt_gbuffer_pixel = Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords
+GBUFFER_SAMPLES = 16
+GBUFFER_DTYPE = np.dtype([("depth", np.float32), ("norm", np.float32, (3,)), ("texc", np.float32, (2,)), ("rgba", np.float32, (4,)),
+                          ("shadow", np.float32), ("coverage", np.float32), ("matId", np.int32), ("objId", np.int32), ("instId", np.int32)])
+assert GBUFFER_DTYPE.itemsize == 60
 
 _LIB = None
 
@@ -247,6 +255,34 @@ class HipIntegrator:
         img = np.zeros((self.H, self.W, channels), np.float32)
         (self.NaivePathTraceBlock if naive else self.PathTraceBlock)(self.N, channels, img, spp)
         return img
+
+    def EvalGBuffer(self, blockNum=None, samples=False, out=None):
+        """Integrator::EvalGBuffer(blockNum, out_gbuffer) (integrator_pt.h:251): a GBUFFER_DTYPE array [winHeight, winWidth]; the records of
+        pixels past blockNum (in m_packedXY order) keep what `out` held (zeros without `out`). samples=True also returns the [blockNum, 16]
+        records of the single samples as they are before the reduction (device-pointer form of the call)."""
+        blockNum = self.N if blockNum is None else int(blockNum)
+        if out is None:
+            out = np.zeros((self.H, self.W), GBUFFER_DTYPE)
+        assert out.dtype == GBUFFER_DTYPE and out.flags["C_CONTIGUOUS"] and out.size == self.N
+        if not samples:
+            self._chk(self.L.hpt_eval_gbuffer(self.h, blockNum, out.ctypes.data))
+            return out
+        raw = np.zeros((blockNum, GBUFFER_SAMPLES), GBUFFER_DTYPE)
+        d_out, d_raw = _vp(), _vp()
+        self._chk(self.L.hpt_device_malloc(self.h, out.nbytes, C.byref(d_out)))
+        try:
+            self._chk(self.L.hpt_device_malloc(self.h, max(raw.nbytes, 60), C.byref(d_raw)))
+            try:
+                self._chk(self.L.hpt_device_copy(self.h, d_out, out.ctypes.data, out.nbytes, 1))
+                self._chk(self.L.hpt_eval_gbuffer_dev(self.h, blockNum, d_out, d_raw, None))
+                self._chk(self.L.hpt_device_copy(self.h, out.ctypes.data, d_out, out.nbytes, 2))      # synchronous copies on the null stream: after the kernel
+                if raw.nbytes:
+                    self._chk(self.L.hpt_device_copy(self.h, raw.ctypes.data, d_raw, raw.nbytes, 2))
+            finally:
+                self.L.hpt_device_free(self.h, d_raw)
+        finally:
+            self.L.hpt_device_free(self.h, d_out)
+        return out, raw
 
     def GetExecutionTime(self, name):
         out = (C.c_float * 4)(0, 0, 0, 0)

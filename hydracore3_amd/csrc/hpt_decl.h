@@ -186,6 +186,13 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
 template <bool DEEP, bool FLAT, bool STATS, bool MOTION = false, bool WIDE = false>   // WIDE: walk DevScene::nodes4 (4-wide compressed nodes) instead of the BVH2
 __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScene S, const WfPool P, uint iter, uint refillBelow, uint grace,
                                                                    uint* stackOverflow, uint gridLanes, Counters* counters);
+// ---- EvalGBuffer (hpt_gbuffer.hip) -----------------------------------------------------------------------------------------------------
+struct GBufferPixel { float depth, norm[3], texc[2], rgba[4], shadow, coverage; int matId, objId, instId; };   // integrator_pt.h:187-198 = hpt_gbuffer_pixel
+static_assert(sizeof(GBufferPixel) == 60, "GBufferPixel is 15 dwords");
+// one lane per (pixel, sample): 16 * blockNum lanes in blocks of 256; `samples` (null or 16 * blockNum records) receives the records before the reduction
+template <bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uint* packedXY, uint blockNum, GBufferPixel* out, GBufferPixel* samples, uint* stackOverflow);
+
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);
 

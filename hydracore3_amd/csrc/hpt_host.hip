@@ -2094,6 +2094,62 @@ extern "C" int hpt_naive_path_trace_block(hpt_ctx* c, uint32_t tidBegin, uint32_
 try { return path_trace_host(c, tidBegin, tidCount, channels, out, passNum, 1); }
 catch (...) { return hptGuard(c, "hpt_naive_path_trace_block"); }
 
+// ---- EvalGBuffer (integrator_pt.h:251, integrator_gbuffer.cpp:264-267) ------------------------------------------------------------------------
+static_assert(sizeof(hpt_gbuffer_pixel) == 60 && sizeof(hpt_gbuffer_pixel) == sizeof(GBufferPixel), "GBufferPixel is 15 dwords (integrator_pt.h:187-198)");
+// Device-pointer form: 16 lanes per pixel through the traversal variant ray_query() would take (hpt_gbuffer.hip). The pass draws no random
+// numbers and changes no state of the context; it reads only RGB base colours, so m_spectral_mode does not matter. Asynchronous.
+extern "C" int hpt_eval_gbuffer_dev(hpt_ctx* c, uint32_t blockNum, hpt_gbuffer_pixel* outDev, hpt_gbuffer_pixel* samplesDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (!outDev) return c->fail(HPT_ERR_ARG, "EvalGBuffer: out_gbuffer is null");
+  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitDeviceData");
+  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitScene");
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "EvalGBuffer before UpdateMembersPlainData");
+  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "EvalGBuffer before PackXYBlock");
+  if (blockNum > c->packedCount) return c->fail(HPT_ERR_ARG, "EvalGBuffer: blockNum exceeds the packed pixel count");
+  if (blockNum == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const uint blocks = (uint)(((size_t)blockNum * 16u + 255u) / 256u);
+  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
+  GBufferPixel* o = (GBufferPixel*)outDev; GBufferPixel* sm = (GBufferPixel*)samplesDev;
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+  if (c->S.sweep)                         gbufferKernel<false, false, true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  else if (c->S.flatMode && c->anyMotion) gbufferKernel<true, true, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  else if (c->S.flatMode)                 gbufferKernel<true, false, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  else if (c->anyMotion)                  gbufferKernel<false, true, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  else                                    gbufferKernel<false, false, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_eval_gbuffer_dev"); }
+// Integrator::EvalGBuffer(blockNum, out_gbuffer) (integrator_pt.h:251; main.cpp:269-277): host pointer to winWidth * winHeight records. The
+// reference writes only the records of pixels packedXY[0 .. blockNum); so does this: the caller's buffer goes up and comes back.
+extern "C" int hpt_eval_gbuffer(hpt_ctx* c, uint32_t blockNum, hpt_gbuffer_pixel* out)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (!out) return c->fail(HPT_ERR_ARG, "EvalGBuffer: out_gbuffer is null");
+  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitDeviceData");      // (before the window size below means anything)
+  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitScene");
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "EvalGBuffer before UpdateMembersPlainData");
+  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "EvalGBuffer before PackXYBlock");
+  if (blockNum > c->packedCount) return c->fail(HPT_ERR_ARG, "EvalGBuffer: blockNum exceeds the packed pixel count");
+  if (blockNum == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  DevBuf<hpt_gbuffer_pixel> d;
+  const size_t n = (size_t)c->packedCount;
+  const bool partial = blockNum < c->packedCount;
+  HIPCHK(c, d.alloc(n));
+  if (partial) HIPCHK(c, hipMemcpy(d.p, out, n * sizeof(hpt_gbuffer_pixel), hipMemcpyHostToDevice));
+  int rc = hpt_eval_gbuffer_dev(c, blockNum, d.p, nullptr, nullptr);
+  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(hpt_gbuffer_pixel), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
+  if (rc == HPT_OK) { float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1); c->lastKernelMs = kms; }
+  d.release();
+  return rc;
+}
+catch (...) { return hptGuard(c, "hpt_eval_gbuffer"); }
+
 // ---- differentiable rendering ---------------------------------------------------------------------------------------------------------
 extern "C" int hpt_reset_diff_tex(hpt_ctx* c)
 try {

@@ -238,6 +238,21 @@ int  hpt_path_trace_block_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount
 int  hpt_path_trace_from_input_rays_block(hpt_ctx* ctx, uint32_t tid, uint32_t channels, const float* rayPosAndW, const float* rayDirAndT, float* out_color, uint32_t passNum);
 int  hpt_path_trace_from_input_rays_block_dev(hpt_ctx* ctx, uint32_t tid, uint32_t channels, const float* rayPosAndWDev, const float* rayDirAndTDev, float* outDev, uint32_t passNum, void* stream);
 
+/* ---- G-buffer (integrator_gbuffer.cpp) ------------------------------------------------------------------------------- */
+/* Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords. A miss: depth 0, norm (0, 0, 1), ids -1, coverage 0. rgba[3] of a hit is
+ * DEFINED as 1 (the reference reads color[3] of a float3 there, integrator_gbuffer.cpp:190: undefined); shadow is 0 (not implemented there). */
+typedef struct hpt_gbuffer_pixel { float depth, norm[3], texc[2], rgba[4], shadow, coverage; int32_t matId, objId, instId; } hpt_gbuffer_pixel;
+/* Integrator::EvalGBuffer(blockNum, out_gbuffer) (integrator_pt.h:251, integrator_gbuffer.cpp:243-267; main.cpp:269-277): for each of the
+ * first blockNum pixels of m_packedXY, GBUFFER_SAMPLES = 16 pinhole primary rays at the pixel's Hammersley points (RayQuery_NearestHit, moving
+ * instances at time 0), one record per ray, and GBufferReduction: the record most similar to the other fifteen, with the mean rgba of the
+ * sixteen and its coverage estimate, written at out[y * winWidth + x]. out = winWidth * winHeight records in host memory; records of pixels
+ * past blockNum are left as they are. Needs CommitDeviceData, CommitScene, UpdateMembersPlainData and PackXYBlock (else HPT_ERR_STATE); draws
+ * no random numbers (no InitRandomGens), changes no state, works with m_spectral_mode on or off (it reads RGB base colours only). */
+int  hpt_eval_gbuffer(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* out);
+/* The same with the records resident in device memory; asynchronous on stream (a hipStream_t, NULL = default stream). samplesDev: NULL, or
+ * 16 * blockNum records that receive every sample's record as it is before the reduction (sample k of packed pixel b at [16 * b + k]). */
+int  hpt_eval_gbuffer_dev(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* outDev, hpt_gbuffer_pixel* samplesDev, void* stream);
+
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
@@ -344,7 +359,7 @@ int  hpt_get_schedule(hpt_ctx* ctx, int* lastSchedule, uint32_t* lastIterations)
  * out[0] = schedule (1 / 2), out[1] = 1 when rays walked the 4-wide compressed tree, out[2] = 1 when surface data came from the 64-byte
  * shading records, out[3] = 1 when the traversal stacks had an HBM part. */
 int  hpt_get_last_launch(hpt_ctx* ctx, uint32_t out[4]);
-/* Duration of the last path-tracing kernel, measured with HIP events on the stream it ran on (ms). */
+/* Duration of the last path-tracing or G-buffer kernel, measured with HIP events on the stream it ran on (ms). */
 int  hpt_last_kernel_ms(hpt_ctx* ctx, float* ms);
 
 #ifdef __cplusplus
