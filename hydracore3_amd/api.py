@@ -89,6 +89,10 @@ ABI = {
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
     "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
+    "hpt_cast_single_ray_block": (_i, [_vp, _u32, _vp, _u32]),
+    "hpt_cast_single_ray_block_dev": (_i, [_vp, _u32, _vp, _u32, _vp]),
+    "hpt_ray_trace_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
+    "hpt_ray_trace_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp]),
 }
 
 # hpt_gbuffer_pixel = Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords
@@ -250,6 +254,26 @@ class HipIntegrator:
         for a in (in_rayPosAndNear, in_rayDirAndFar, out_color):
             assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"]
         self._chk(self.L.hpt_path_trace_from_input_rays_block(self.h, tid, channels, in_rayPosAndNear.ctypes.data, in_rayDirAndFar.ctypes.data, out_color.ctypes.data, a_passNum))
+
+    def CastSingleRayBlock(self, tid, out_color, a_passNum=1):
+        """Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254): out_color float32 [winHeight, winWidth, 4]; the
+        first tid pixels of m_packedXY are ASSIGNED (base colour x texture, fourth float 0; a miss: four zeros), the others keep their contents."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and out_color.size == self.N * 4
+        self._chk(self.L.hpt_cast_single_ray_block(self.h, tid, out_color.ctypes.data, a_passNum))
+
+    def RayTraceBlock(self, tid, channels, out_color, a_passNum=1):
+        """Integrator::RayTraceBlock(tid, channels, out_color, a_passNum) (integrator_pt.h:263): one Whitted path per pixel, ADDED to the first three
+        of the pixel's `channels` floats. channels 3 or 4; 1 and 2 raise; above 4 nothing is written (out_color may then be any float32 array)."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and (channels not in (3, 4) or out_color.size == self.N * channels)
+        self._chk(self.L.hpt_ray_trace_block(self.h, tid, channels, out_color.ctypes.data, a_passNum))
+
+    def cast_single_ray_block_dev(self, dev_ptr, tid=None, pass_num=1, stream=None):
+        """CastSingleRayBlock on a device frame of winWidth * winHeight * 4 floats; asynchronous on `stream`."""
+        self._chk(self.L.hpt_cast_single_ray_block_dev(self.h, self.N if tid is None else tid, dev_ptr, pass_num, stream))
+
+    def ray_trace_block_dev(self, dev_ptr, tid=None, channels=4, pass_num=1, stream=None):
+        """RayTraceBlock on a device frame of winWidth * winHeight * channels floats; asynchronous on `stream`."""
+        self._chk(self.L.hpt_ray_trace_block_dev(self.h, self.N if tid is None else tid, channels, dev_ptr, pass_num, stream))
 
     def render(self, spp, channels=4, naive=False):
         img = np.zeros((self.H, self.W, channels), np.float32)

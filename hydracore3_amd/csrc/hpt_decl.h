@@ -192,6 +192,12 @@ static_assert(sizeof(GBufferPixel) == 60, "GBufferPixel is 15 dwords");
 // one lane per (pixel, sample): 16 * blockNum lanes in blocks of 256; `samples` (null or 16 * blockNum records) receives the records before the reduction
 template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uint* packedXY, uint blockNum, GBufferPixel* out, GBufferPixel* samples, uint* stackOverflow);
+// ---- CastSingleRayBlock / RayTraceBlock (hpt_raytrace.hip) -----------------------------------------------------------------------------
+// one lane per pixel of packedXY[0 .. tidCount); outColor: winWidth * winHeight pixels of 4 floats (assigned) / of `channels` = 3 or 4 floats (added to)
+template <bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256) castSingleRayKernel(const DevScene S, const uint* packedXY, uint tidCount, float* outColor, uint* stackOverflow);
+template <bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const uint* packedXY, uint tidCount, uint channels, float* outColor, uint* stackOverflow);
 
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);

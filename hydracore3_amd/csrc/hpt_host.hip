@@ -189,6 +189,7 @@ struct hpt_ctx
 
   // GetExecutionTime slots
   float tPathTrace[4] = {0, 0, 0, 0}, tNaive[4] = {0, 0, 0, 0}, tDR[4] = {0, 0, 0, 0}, tFromRays[4] = {0, 0, 0, 0};
+  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0};
   float lastKernelMs = 0.0f;
 
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
@@ -2150,6 +2151,112 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_eval_gbuffer"); }
 
+// ---- CastSingleRayBlock / RayTraceBlock (integrator_pt.h:254, 263; integrator_rt.cpp:420-461; integrator_pt_host.cpp:29-36, 75-90) ----------------
+// What both passes need before they can run, in the words hpt_eval_gbuffer uses. `what` names the reference's method.
+static int rt_check(hpt_ctx* c, const char* what, const void* out, uint32_t tid)
+{
+  const std::string w(what);
+  if (!out) return c->fail(HPT_ERR_ARG, w + ": out_color is null");
+  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, w + " before CommitDeviceData");
+  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, w + " before CommitScene");
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, w + " before UpdateMembersPlainData");
+  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, w + " before PackXYBlock");
+  if (tid > c->packedCount) return c->fail(HPT_ERR_ARG, w + ": tid exceeds the packed pixel count");
+  return HPT_OK;
+}
+// channels of RayTraceBlock: 1 and 2 are refused (the reference writes three floats at that stride: over the next pixel and, for the last
+// one, past the buffer - DESIGN.md 7); above 4 its kernel_ContributeToImage3 writes nothing, so there is nothing to launch
+static int rt_check_channels(hpt_ctx* c, uint32_t channels)
+{
+  if (channels < 3u) return c->fail(HPT_ERR_ARG, "RayTraceBlock: channels must be 3 or 4 (1 and 2 make the reference write outside the pixel; above 4 nothing is written)");
+  return HPT_OK;
+}
+// one lane per pixel through the traversal variant ray_query() would take (hpt_raytrace.hip); channels = 0: CastSingleRay
+static int rt_launch(hpt_ctx* c, uint32_t tid, uint32_t channels, float* outDev, hipStream_t st)
+{
+  (void)hipSetDevice(c->device);
+  const uint blocks = (tid + 255u) / 256u;
+  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+#define HPT_RT_LAUNCH(FLAT, MOTION, SWEEP) do { \
+    if (channels == 0u) castSingleRayKernel<FLAT, MOTION, SWEEP><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, outDev, c->dStackOvf.p); \
+    else                rayTraceKernel<FLAT, MOTION, SWEEP><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, outDev, c->dStackOvf.p); } while (0)
+  if (c->S.sweep)                         HPT_RT_LAUNCH(false, false, true);
+  else if (c->S.flatMode && c->anyMotion) HPT_RT_LAUNCH(true, true, false);
+  else if (c->S.flatMode)                 HPT_RT_LAUNCH(true, false, false);
+  else if (c->anyMotion)                  HPT_RT_LAUNCH(false, true, false);
+  else                                    HPT_RT_LAUNCH(false, false, false);
+#undef HPT_RT_LAUNCH
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+// Host-pointer form of either pass: the caller's frame goes up (RayTraceBlock adds to it; CastSingleRayBlock leaves the pixels past tid as
+// they are) and comes back; the four GetExecutionTime slots are kernel, copy in, copy out, overhead, as path_trace_host fills them.
+static int rt_host(hpt_ctx* c, uint32_t tid, uint32_t channels, float* out, float slots[4])
+{
+  (void)hipSetDevice(c->device);
+  const size_t n = (size_t)c->packedCount * (channels == 0u ? 4u : channels);
+  DevBuf<float> d;
+  const double t0 = now_ms();
+  HIPCHK(c, d.upload(out, n));
+  const double t1 = now_ms();
+  int rc = rt_launch(c, tid, channels, d.p, nullptr);
+  if (rc == HPT_OK) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = c->hipFail(e, "hipDeviceSynchronize"); }
+  const double t2 = now_ms();
+  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
+  const double t3 = now_ms();
+  if (rc == HPT_OK) {
+    float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
+    c->lastKernelMs = kms;
+    slots[0] = kms; slots[1] = float(t1 - t0); slots[2] = float(t3 - t2); slots[3] = float((t2 - t1) - kms);
+  }
+  d.release();
+  return rc;
+}
+
+// Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254, integrator_pt_host.cpp:29-36): a_passNum is unused there and here
+extern "C" int hpt_cast_single_ray_block_dev(hpt_ctx* c, uint32_t tid, float* outDev, uint32_t passNum, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)passNum;
+  if (int rc = rt_check(c, "CastSingleRayBlock", outDev, tid)) return rc;
+  if (tid == 0u) return HPT_OK;
+  return rt_launch(c, tid, 0u, outDev, (hipStream_t)stream);
+}
+catch (...) { return hptGuard(c, "hpt_cast_single_ray_block_dev"); }
+extern "C" int hpt_cast_single_ray_block(hpt_ctx* c, uint32_t tid, float* out, uint32_t passNum)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)passNum;
+  if (int rc = rt_check(c, "CastSingleRayBlock", out, tid)) return rc;
+  if (tid == 0u) return HPT_OK;
+  return rt_host(c, tid, 0u, out, c->tCastSingleRay);
+}
+catch (...) { return hptGuard(c, "hpt_cast_single_ray_block"); }
+
+// Integrator::RayTraceBlock(tid, channels, out_color, a_passNum) (integrator_pt.h:263, integrator_pt_host.cpp:75-90): a_passNum is unused there and here
+extern "C" int hpt_ray_trace_block_dev(hpt_ctx* c, uint32_t tid, uint32_t channels, float* outDev, uint32_t passNum, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)passNum;
+  if (int rc = rt_check(c, "RayTraceBlock", outDev, tid)) return rc;
+  if (int rc = rt_check_channels(c, channels)) return rc;
+  if (tid == 0u || channels > 4u) return HPT_OK;
+  return rt_launch(c, tid, channels, outDev, (hipStream_t)stream);
+}
+catch (...) { return hptGuard(c, "hpt_ray_trace_block_dev"); }
+extern "C" int hpt_ray_trace_block(hpt_ctx* c, uint32_t tid, uint32_t channels, float* out, uint32_t passNum)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)passNum;
+  if (int rc = rt_check(c, "RayTraceBlock", out, tid)) return rc;
+  if (int rc = rt_check_channels(c, channels)) return rc;
+  if (tid == 0u || channels > 4u) return HPT_OK;
+  return rt_host(c, tid, channels, out, c->tRayTrace);
+}
+catch (...) { return hptGuard(c, "hpt_ray_trace_block"); }
+
 // ---- differentiable rendering ---------------------------------------------------------------------------------------------------------
 extern "C" int hpt_reset_diff_tex(hpt_ctx* c)
 try {
@@ -2364,6 +2471,8 @@ try {
   else if (n == "NaivePathTrace" || n == "NaivePathTraceBlock") src = c->tNaive;
   else if (n == "PathTraceFromInputRays" || n == "PathTraceFromInputRaysBlock") src = c->tFromRays;
   else if (n == "PathTraceDR" || n == "PathTraceDRBlock") src = c->tDR;                     // integrator_dr2.cpp:82-88
+  else if (n == "CastSingleRay" || n == "CastSingleRayBlock") src = c->tCastSingleRay;      // main.cpp:443
+  else if (n == "RayTrace" || n == "RayTraceBlock") src = c->tRayTrace;                     // raytraceTime (integrator_pt_host.cpp:75-90)
   if (!src) return HPT_OK;                                                                 // unknown names leave `out` untouched, as the reference does
   for (int i = 0; i < 4; i++) out[i] = src[i];
   return HPT_OK;

@@ -3,8 +3,9 @@
 // hydra_api's CommandBuffer::CommitToStorage :109-127), the driver converts them to Mesh4fInput and calls LoadScene; Render() is
 // SetFrameBufferSize -> SetViewport -> UpdateMembersPlainData -> PackXYBlock -> the block call. Same class and member names; the scene
 // description arrives as XML text + folder (the reference passes its parsed hydra_xml::HydraScene, which lives in LiteScene and stays there).
-// The reference's Render currently calls CastSingleRayBlock with the PathTraceBlock call commented out (hydra_cpu.cpp:105-106); this driver makes the
-// PathTraceBlock call - the hot path this repository replaces.
+// The reference's Render currently calls CastSingleRayBlock with the PathTraceBlock call commented out (hydra_cpu.cpp:105-106). This driver makes the
+// PathTraceBlock call by default - the hot path this repository replaces - and the reference's CastSingleRayBlock call after
+// SetRenderMode(RENDER_CAST_SINGLE_RAY): the cheap preview frame (4 floats per pixel, assigned; `channels` and a_passNumber unused, as there).
 #pragma once
 #include <memory>
 #include <string>
@@ -43,6 +44,8 @@ struct HydraHipRenderDriver : IRenderDriver
   explicit HydraHipRenderDriver(int device = 0) { if (hpt_create(device, &m_ctx) != HPT_OK) m_ctx = nullptr; }
   ~HydraHipRenderDriver() override { if (m_ctx) hpt_destroy(m_ctx); }
   bool valid() const { return m_ctx != nullptr; }
+  enum RenderMode { RENDER_PATH_TRACE = 0, RENDER_CAST_SINGLE_RAY = 1 };      // which block call Render makes (hydra_cpu.cpp:105-106)
+  void SetRenderMode(RenderMode a_mode) { m_mode = a_mode; }
   const std::string& lastError() const { return m_err; }
 
   bool LoadScene(const std::string& a_xmlText, const std::string& a_folder, const RDScene_Input& a_input, uint32_t a_updateFlags) override
@@ -92,6 +95,11 @@ struct HydraHipRenderDriver : IRenderDriver
     }
     int rc = hpt_update_params(m_ctx, &p);
     if (rc == HPT_OK) rc = hpt_pack_xy(m_ctx, (uint32_t)sizeX, sizeY);
+    if (rc == HPT_OK && m_mode == RENDER_CAST_SINGLE_RAY) {                    // m_pImpl->CastSingleRayBlock(sizeX*sizeY, data, a_passNumber) (hydra_cpu.cpp:105): no generators
+      rc = hpt_cast_single_ray_block(m_ctx, (uint32_t)(sizeX * (int)sizeY), data, a_passNumber);
+      if (rc != HPT_OK) m_err = hpt_last_error(m_ctx);
+      return;
+    }
     if (rc == HPT_OK && m_gens != (uint32_t)(sizeX * (int)sizeY)) { rc = hpt_init_random_gens(m_ctx, (uint32_t)(sizeX * (int)sizeY)); m_gens = (uint32_t)(sizeX * (int)sizeY); }   // (the reference's constructor seeds 1024 x 1024 generators once)
     if (rc == HPT_OK) rc = hpt_path_trace_block(m_ctx, 0, (uint32_t)(sizeX * (int)sizeY), channels, data, a_passNumber);      // m_pImpl->PathTraceBlock(sizeX*sizeY, channels, data, a_passNumber)
     if (rc != HPT_OK) m_err = hpt_last_error(m_ctx);
@@ -102,6 +110,7 @@ struct HydraHipRenderDriver : IRenderDriver
   std::unordered_map<int, Mesh4fInput> m_meshPtrs;                             // Integrator::m_LSMeshPtrs
   std::string m_err;
   bool m_loaded = false, m_committed = false; uint32_t m_gens = 0;
+  RenderMode m_mode = RENDER_PATH_TRACE;
 };
 
 inline std::shared_ptr<IRenderDriver> MakeHydraRenderHIP(int device = 0) { return std::make_shared<HydraHipRenderDriver>(device); }   // HR2::MakeHydraRenderCPU's counterpart (hydra_cpu.cpp:20-23)

@@ -4,7 +4,7 @@
 //   hydra_hip::BVH2SceneHIP   <->  ISceneObject                      (external/CrossRT/CrossRT.h:45-176)
 //   hydra_hip::IntegratorHIP  <->  Integrator                        (integrator_pt.h:123-703): the virtual hooks the
 //                                  kernel_slicer-generated Integrator_Generated overrides (main.cpp:221-224) --
-//                                  PathTraceBlock, NaivePathTraceBlock, EvalGBuffer, PackXYBlock, CommitDeviceData,
+//                                  PathTraceBlock, NaivePathTraceBlock, EvalGBuffer, CastSingleRayBlock, RayTraceBlock, PackXYBlock, CommitDeviceData,
 //                                  UpdateMembersPlainData, GetExecutionTime, Update_m_materials / Update_m_lights
 //   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136)
 //
@@ -180,6 +180,11 @@ public:
   { if (m_ctx) report(hpt_path_trace_block(m_ctx, 0, tid, channels, out_color, a_passNum), "PathTraceBlock"); }
   virtual void NaivePathTraceBlock(uint32_t tid, uint32_t channels, float* out_color, uint32_t a_passNum)
   { if (m_ctx) report(hpt_naive_path_trace_block(m_ctx, 0, tid, channels, out_color, a_passNum), "NaivePathTraceBlock"); }
+  // integrator_pt.h:254, 263 (main.cpp:435-472): the primary-ray preview (4 floats per pixel, assigned) and the Whitted pass (added; channels 3 or 4)
+  virtual void CastSingleRayBlock(uint32_t tid, float* out_color, uint32_t a_passNum)
+  { if (m_ctx) report(hpt_cast_single_ray_block(m_ctx, tid, out_color, a_passNum), "CastSingleRayBlock"); }
+  virtual void RayTraceBlock(uint32_t tid, uint32_t channels, float* out_color, uint32_t a_passNum)
+  { if (m_ctx) report(hpt_ray_trace_block(m_ctx, tid, channels, out_color, a_passNum), "RayTraceBlock"); }
   // integrator_pt.h:187-198, 251 (main.cpp:269-277): the G-buffer pass; out_gbuffer holds winWidth * winHeight records
   struct GBufferPixel { float depth; float norm[3]; float texc[2]; float rgba[4]; float shadow; float coverage; int32_t matId; int32_t objId; int32_t instId; };
   static_assert(sizeof(GBufferPixel) == sizeof(hpt_gbuffer_pixel), "GBufferPixel and hpt_gbuffer_pixel are the same 15 dwords");

@@ -253,6 +253,31 @@ int  hpt_eval_gbuffer(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* out);
  * 16 * blockNum records that receive every sample's record as it is before the reduction (sample k of packed pixel b at [16 * b + k]). */
 int  hpt_eval_gbuffer_dev(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* outDev, hpt_gbuffer_pixel* samplesDev, void* stream);
 
+/* ---- primary-ray preview and Whitted ray tracing (integrator_rt.cpp) ------------------------------------------------- */
+/* Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254, integrator_pt_host.cpp:29-36, integrator_rt.cpp:33-53,
+ * 116-161, 420-430; main.cpp:435-446; hydra_api/hydra_cpu.cpp:105): for each of the first tid pixels of m_packedXY one pinhole ray through
+ * the pixel centre, RayQuery_NearestHit (moving instances at time 0) and colour = colors[GLTF_COLOR_BASE].w > 0 ? clamp(w, 0, 1) splat :
+ * colors[GLTF_COLOR_BASE] * texture, ASSIGNED to out_color[(y * winWidth + x) * 4 + 0..2], the fourth float 0. out_color = winWidth *
+ * winHeight * 4 floats in host memory; pixels past tid keep their contents. A miss assigns 0 to the four floats of its own pixel (the
+ * reference writes out_color[tid] = 0 there, one float that races with the pixel owning it: DESIGN.md 7). a_passNum is unused, as in the
+ * reference. Needs CommitDeviceData, CommitScene, UpdateMembersPlainData and PackXYBlock (else HPT_ERR_STATE naming the missing call); tid >
+ * winWidth * winHeight and null pointers are HPT_ERR_ARG; tid = 0 does nothing. Draws no random numbers (no InitRandomGens), changes no
+ * state, is the same with m_spectral_mode on or off. hpt_get_execution_time("CastSingleRayBlock") gives its four slots. */
+int  hpt_cast_single_ray_block(hpt_ctx* ctx, uint32_t tid, float* out_color, uint32_t passNum);
+/* Integrator::RayTraceBlock(tid, channels, out_color, a_passNum) (integrator_pt.h:263, integrator_pt_host.cpp:75-90, integrator_rt.cpp:55-82,
+ * 164-299, 432-461; main.cpp:459-472): one deterministic Whitted path per pixel - up to m_traceDepth times kernel_RayTrace2 (at time 0)
+ * and kernel_RayBounce: an emitter adds throughput * emission and ends the path; otherwise every entry of m_lights is lit as a point at
+ * its pos behind a RayQuery_AnyHit shadow ray, and the path continues as a perfect mirror weighted alpha * colors[METAL] + (1 - alpha) *
+ * colors[COAT]. No environment term, no random numbers. The result is ADDED to out_color[(y * winWidth + x) * channels + 0..2]. channels
+ * 3 and 4 are served; 1 and 2 are HPT_ERR_ARG (the reference then writes over the neighbouring pixel and past the buffer: DESIGN.md 7);
+ * above 4 nothing is written, as in the reference (HPT_OK). Other errors, a_passNum and the state it needs: as hpt_cast_single_ray_block.
+ * hpt_get_execution_time("RayTraceBlock") gives raytraceTime's four slots. */
+int  hpt_ray_trace_block(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* out_color, uint32_t passNum);
+/* The same with the frame resident in device memory; asynchronous on stream (a hipStream_t, NULL = default stream). hpt_last_kernel_ms
+ * gives the kernel time of the last call. */
+int  hpt_cast_single_ray_block_dev(hpt_ctx* ctx, uint32_t tid, float* outDev, uint32_t passNum, void* stream);
+int  hpt_ray_trace_block_dev(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* outDev, uint32_t passNum, void* stream);
+
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
