@@ -93,6 +93,11 @@ ABI = {
     "hpt_cast_single_ray_block_dev": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "hpt_ray_trace_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
     "hpt_ray_trace_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp]),
+    "hpt_qmc_table": (_i, [_vp]),
+    "hpt_qmc_layout": (_i, [_i, _i, _i, _vp]),
+    "hpt_qmc_sample_count": (_u32, [_u32, _u32]),
+    "hpt_path_trace_qmc_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
+    "hpt_path_trace_qmc_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
 }
 
 # hpt_gbuffer_pixel = Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords
@@ -121,6 +126,27 @@ def load_library():
             fn.restype, fn.argtypes = res, args
         _LIB = lib
     return _LIB
+
+
+def qmc_table():
+    """qmc::init (mlt/rnd_qmc.cpp): the 11 x 31 Niederreiter base-2 table, uint32 [11, 31]. Host code: needs the library, no GPU."""
+    out = np.zeros((11, 31), np.uint32)
+    if load_library().hpt_qmc_table(out.ctypes.data) != 0:
+        raise HydraHipError("hpt_qmc_table failed")
+    return out
+
+
+def qmc_layout(dof, spectral, motion):
+    """IntegratorQMC::EnableQMC: the dimension offsets {"dof", "spd", "motion", "mat", "lgt"} of a scene with these features (0 = pseudo)."""
+    out = np.zeros(5, np.uint32)
+    if load_library().hpt_qmc_layout(int(bool(dof)), int(bool(spectral)), int(bool(motion)), out.ctypes.data) != 0:
+        raise HydraHipError("hpt_qmc_layout failed")
+    return dict(zip(("dof", "spd", "motion", "mat", "lgt"), (int(v) for v in out)))
+
+
+def qmc_sample_count(pixels_num, pass_num):
+    """Samples of one PathTraceBlockQMC call: min(2^32 - 1, pixelsNum * a_passNum)."""
+    return int(load_library().hpt_qmc_sample_count(pixels_num, pass_num))
 
 
 COUNTER_NAMES = ("rays", "nodes", "tris", "surface_hits", "shadow_rays", "paths", "instances_entered", "tex_fetches",
@@ -274,6 +300,50 @@ class HipIntegrator:
     def ray_trace_block_dev(self, dev_ptr, tid=None, channels=4, pass_num=1, stream=None):
         """RayTraceBlock on a device frame of winWidth * winHeight * channels floats; asynchronous on `stream`."""
         self._chk(self.L.hpt_ray_trace_block_dev(self.h, self.N if tid is None else tid, channels, dev_ptr, pass_num, stream))
+
+    # ---- IntegratorQMC (mlt/integrator_qmc.cpp) -----------------------------------------------------------------------
+    def PathTraceBlockQMC(self, pixelsNum, channels, out_color, a_passNum):
+        """IntegratorQMC::PathTraceBlock(pixelsNum, channels, out_color, a_passNum): min(2^32 - 1, pixelsNum * a_passNum) samples of the
+        Niederreiter sequence, each ADDED (float atomics) to the pixel its first two dimensions select; out_color float32 [winHeight, winWidth, channels]."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and (channels not in (1, 3, 4) or out_color.size == self.N * channels)
+        self._chk(self.L.hpt_path_trace_qmc_block(self.h, pixelsNum, channels, out_color.ctypes.data, a_passNum))
+
+    def path_trace_qmc_block_dev(self, dev_ptr, pass_num, pixels_num=None, channels=4, sample_color_ptr=None, sample_pixel_ptr=None, stream=None):
+        """PathTraceBlockQMC on a device frame (may be None when both record pointers are given); asynchronous on `stream`."""
+        self._chk(self.L.hpt_path_trace_qmc_block_dev(self.h, self.N if pixels_num is None else pixels_num, channels, dev_ptr, pass_num,
+                                                      sample_color_ptr, sample_pixel_ptr, stream))
+
+    def render_qmc(self, spp, channels=4, frame=True, records=False, pixels_num=None):
+        """One PathTraceBlockQMC call through the device-pointer form. Returns (frame or None, colours [S, 4] or None, pixel indices [S] or None):
+        the frame is the atomic sum (zeros before the call), the records are the per-sample values in sample order."""
+        pixels_num = self.N if pixels_num is None else pixels_num
+        S = qmc_sample_count(pixels_num, spp)
+        img = np.zeros((self.H, self.W, channels), np.float32) if frame else None
+        col = np.zeros((S, 4), np.float32) if records else None
+        pix = np.zeros(S, np.uint32) if records else None
+        ptrs = []
+
+        def dev(nbytes):
+            p = _vp()
+            self._chk(self.L.hpt_device_malloc(self.h, max(nbytes, 16), C.byref(p)))
+            ptrs.append(p)
+            return p
+        try:
+            d_img = dev(img.nbytes) if frame else None
+            d_col = dev(col.nbytes) if records else None
+            d_pix = dev(pix.nbytes) if records else None
+            if frame:
+                self._chk(self.L.hpt_device_copy(self.h, d_img, img.ctypes.data, img.nbytes, 1))
+            self.path_trace_qmc_block_dev(d_img, spp, pixels_num, channels, d_col, d_pix)
+            if frame:
+                self._chk(self.L.hpt_device_copy(self.h, img.ctypes.data, d_img, img.nbytes, 2))
+            if records:
+                self._chk(self.L.hpt_device_copy(self.h, col.ctypes.data, d_col, col.nbytes, 2))
+                self._chk(self.L.hpt_device_copy(self.h, pix.ctypes.data, d_pix, pix.nbytes, 2))
+        finally:
+            for p in ptrs:
+                self.L.hpt_device_free(self.h, p)
+        return img, col, pix
 
     def render(self, spp, channels=4, naive=False):
         img = np.zeros((self.H, self.W, channels), np.float32)

@@ -199,6 +199,22 @@ __global__ void __launch_bounds__(256) castSingleRayKernel(const DevScene S, con
 template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const uint* packedXY, uint tidCount, uint channels, float* outColor, uint* stackOverflow);
 
+// ---- IntegratorQMC::PathTraceBlock (hpt_qmc.hip) ---------------------------------------------------------------------------------------
+static const uint QMC_DIMENSIONS = 11u, QMC_RESOLUTION = 31u;
+struct QmcJob
+{
+  const uint* table;              // QMC_DIMENSIONS x QMC_RESOLUTION generator-matrix columns (qmc_table.h; uploaded once per context)
+  uint   samples;                 // S = min(2^32 - 1, pixels x passes)
+  uint   gensCount;               // N = size of m_randomGens: sample s runs on generator s % N
+  uint   dofDim, motionDim, matDim, lgtDim;   // EnableQMC's dimension offsets (0: that draw stays pseudo)
+  float4* sampleColor;            // per-sample records, indexed by s (both null or both set): the colour as added ...
+  uint*   samplePixel;            // ... and the pixel index y * winWidth + x
+};
+// Job carries outColor (may be null when the records are asked for), channels, gens, queue, packedXY / packedCount (camera back plate),
+// the stack overflow area and tidCount = min(N, S) generator slots with work
+template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q);
+
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);
 

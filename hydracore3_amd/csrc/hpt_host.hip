@@ -3,6 +3,7 @@
 #include "plastic_precompute.h"
 #include "film_precompute.h"
 #include "jpeg_decode.h"
+#include "qmc_table.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -143,7 +144,9 @@ struct hpt_ctx
   std::vector<uint> hTriIndices;                         // host mirror of m_triIndices: Update_m_matIdOffsets re-validates the vertex indices a mesh will read
   bool envLightOk(uint id) const { return id < hLightGeom.size() && hLightGeom[id] == LIGHT_GEOM_ENV; }
   DevBuf<Rng> dGens;
+  uint gensCount = 0;                                    // m_randomGens.size() as the last InitRandomGens / hpt_set_random_gens left it (the buffer never shrinks)
   DevBuf<uint> dQueue, dStackOvf; DevBuf<Counters> dCounters;
+  DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // wavefront schedule (hpt_wavefront.hip): the pixels of a call are cut into groups, each with its own path pool, ray queue and
@@ -189,7 +192,7 @@ struct hpt_ctx
 
   // GetExecutionTime slots
   float tPathTrace[4] = {0, 0, 0, 0}, tNaive[4] = {0, 0, 0, 0}, tDR[4] = {0, 0, 0, 0}, tFromRays[4] = {0, 0, 0, 0};
-  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0};
+  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0};
   float lastKernelMs = 0.0f;
 
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
@@ -252,7 +255,7 @@ try {
   lbvhDestroy(c->lbvh); c->lbvh = nullptr;
   c->dNodes.release(); c->dTris.release(); c->dInsts.release(); c->dSweepInsts.release(); c->dSweepTris.release(); c->dSweepBoxes.release(); c->dSweepPlanes.release(); c->dSweepPairBoxes.release(); c->dLevelNodes.release(); c->dShadeTris.release(); c->dNodes4.release(); c->dNodes4Src.release(); c->dTriBox.release(); c->dNodeBounds.release(); c->dInstO2W.release(); c->dTriIndices.release(); c->dMatIdByPrim.release();
   c->dMatVertOffset.release(); c->dPackedXY.release(); c->dVData.release(); c->dNormMat.release(); c->dRemapInst.release();
-  c->dRemapLists.release(); c->dMaterials.release(); c->dLights.release(); c->dTextures.release(); c->dArrays1f.release(); c->dSpecValues.release(); c->dSpecOffsetSz.release(); c->dCieXYZ.release(); c->dFilmsEtaK.release(); c->dPrecompFilms.release(); c->dFilmsSpecId.release(); c->dSpecTexIdsWavelengths.release(); c->dSpecTexOffsetSz.release(); c->dGens.release();
+  c->dRemapLists.release(); c->dMaterials.release(); c->dLights.release(); c->dTextures.release(); c->dArrays1f.release(); c->dSpecValues.release(); c->dSpecOffsetSz.release(); c->dCieXYZ.release(); c->dFilmsEtaK.release(); c->dPrecompFilms.release(); c->dFilmsSpecId.release(); c->dSpecTexIdsWavelengths.release(); c->dSpecTexOffsetSz.release(); c->dGens.release(); c->dQmcTable.release();
   c->dQueue.release(); c->dStackOvf.release(); c->dCounters.release(); c->dFrame.release(); c->dRecord.release(); c->dRef.release(); c->dData.release();
   c->dGrad.release(); c->dLoss.release(); c->dLossAcc.release();
   for (hpt_ctx::WfGroup* g : c->wfGroups) {
@@ -1494,6 +1497,7 @@ try {
   if (!c || n == 0) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
   HIPCHK(c, c->dGens.alloc(n));
+  c->gensCount = n;
   initRandomGensKernel<<<dim3((n + 255) / 256), dim3(256), 0, 0>>>(c->dGens.p, n, firstSeed);
   HIPCHK(c, hipGetLastError());
   return HPT_OK;
@@ -1514,6 +1518,7 @@ try {
   if (!c || !in) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
   HIPCHK(c, c->dGens.alloc(count));
+  c->gensCount = count;
   HIPCHK(c, hipMemcpy(c->dGens.p, in, (size_t)count * 8, hipMemcpyHostToDevice));
   return HPT_OK;
 }
@@ -2257,6 +2262,118 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_ray_trace_block"); }
 
+// ---- IntegratorQMC::PathTraceBlock (mlt/integrator_qmc.cpp:284-315; hpt_qmc.hip) -----------------------------------------------------------------
+extern "C" int hpt_qmc_table(uint32_t out[341])
+try {
+  if (!out) return HPT_ERR_ARG;
+  static_assert(hpt_qmc::DIMENSIONS * hpt_qmc::RESOLUTION == 341 && hpt_qmc::DIMENSIONS == (int)QMC_DIMENSIONS && hpt_qmc::RESOLUTION == (int)QMC_RESOLUTION, "11 x 31 table");
+  hpt_qmc::buildTable(out);
+  return HPT_OK;
+}
+catch (...) { return hptGuard(nullptr, "hpt_qmc_table"); }
+extern "C" int hpt_qmc_layout(int dof, int spectral, int motion, uint32_t out[5])
+try {
+  if (!out) return HPT_ERR_ARG;
+  hpt_qmc::layout(dof != 0, spectral != 0, motion != 0, out);
+  return HPT_OK;
+}
+catch (...) { return hptGuard(nullptr, "hpt_qmc_layout"); }
+// m_maxThreadId = min(numeric_limits<unsigned>::max(), pixelsNum * a_passNum) (integrator_qmc.cpp:293-294)
+extern "C" uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum)
+try {
+  const unsigned long long n = (unsigned long long)pixelsNum * (unsigned long long)passNum;
+  return n > 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)n;
+}
+catch (...) { (void)hptGuard(nullptr, "hpt_qmc_sample_count"); return 0u; }
+// what the call needs, in the order the reference's driver makes its calls; `out` / records: at least one destination
+static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void* sampleColor, const void* samplePixel)
+{
+  if (!out && !sampleColor && !samplePixel) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: no frame and no sample records to write");
+  if ((sampleColor == nullptr) != (samplePixel == nullptr)) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: the sample records come as a pair (colours and pixel indices)");
+  if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlockQMC before CommitDeviceData / UpdateMembersPlainData");
+  if (c->S.spectralMode != 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: m_spectral_mode is not served (the spectral kernels are a separate family; hpt_qmc_layout still answers for it)");
+  if (channels > 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: channels above 4 are the wavelength layers of spectral rendering");
+  if (channels == 2u || channels == 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: a framebuffer of 1, 3 or 4 channels (three components are written per pixel)");
+  if (c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlockQMC before PackXYBlock");
+  if (c->gensCount == 0u) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC before InitRandomGens: sample s runs on generator s % m_randomGens.size()");
+  if (c->hasFilm && !c->filmTablesRGB) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)");
+  return HPT_OK;
+}
+extern "C" int hpt_path_trace_qmc_block_dev(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                            float* sampleColorDev, uint32_t* samplePixelDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = qmc_check(c, channels, outDev, sampleColorDev, samplePixelDev)) return rc;
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t samples = hpt_qmc_sample_count(pixelsNum, passNum);
+  if (samples == 0u) return HPT_OK;
+  if (c->dQmcTable.n == 0) {                                               // qmc::init in IntegratorQMC's constructor
+    uint32_t table[341];
+    hpt_qmc::buildTable(table);
+    HIPCHK(c, c->dQmcTable.upload(table, 341));
+  }
+  DevScene Sq = c->S; Sq.shadeTris = nullptr;                             // every BSDF branch gathers through the index chain: the walk reports primitive ids
+  const uint n = c->gensCount;
+  uint32_t lay[5];
+  hpt_qmc::layout(c->S.camLensRadius > 0.0f || c->S.lensCount != 0u, false, c->S.motion != 0u, lay);          // EnableQMC
+  QmcJob q; std::memset(&q, 0, sizeof(q));
+  q.table = c->dQmcTable.p; q.samples = samples; q.gensCount = n;
+  q.dofDim = lay[0]; q.motionDim = lay[2]; q.matDim = lay[3]; q.lgtDim = lay[4];
+  q.sampleColor = (float4*)sampleColorDev; q.samplePixel = samplePixelDev;
+  Job job; std::memset(&job, 0, sizeof(job));
+  job.tidCount = std::min(n, samples); job.passNum = passNum; job.channels = channels; job.outColor = outDev;
+  job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, false, true), ((size_t)job.tidCount + 255) / 256);
+  HIPCHK(c, c->dQueue.alloc(1));
+  HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
+  job.queue = c->dQueue.p;
+  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
+  job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
+  const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
+  c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
+  c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
+  const dim3 g(blocks), b(256);
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+  if (c->S.motion != 0u) {
+    if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, true, false><<<g, b, 0, st>>>(Sq, job, q); }
+    else               { if (deep) pathTraceQmcKernel<true, false, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, true, false><<<g, b, 0, st>>>(Sq, job, q); }
+  }
+  else if (c->S.sweep)    pathTraceQmcKernel<false, false, false, true><<<g, b, 0, st>>>(Sq, job, q);
+  else if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, false, false><<<g, b, 0, st>>>(Sq, job, q); }
+  else                    { if (deep) pathTraceQmcKernel<true, false, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, false, false><<<g, b, 0, st>>>(Sq, job, q); }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block_dev"); }
+// host-pointer form: the caller's frame goes up, is added to and comes back; slots as path_trace_host fills them
+extern "C" int hpt_path_trace_qmc_block(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* out, uint32_t passNum)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = qmc_check(c, channels, out, nullptr, nullptr)) return rc;
+  (void)hipSetDevice(c->device);
+  if (hpt_qmc_sample_count(pixelsNum, passNum) == 0u) return HPT_OK;
+  const size_t n = (size_t)c->packedCount * channels;
+  DevBuf<float> d;
+  const double t0 = now_ms();
+  HIPCHK(c, d.upload(out, n));
+  const double t1 = now_ms();
+  int rc = hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, d.p, passNum, nullptr, nullptr, nullptr);
+  if (rc == HPT_OK) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = c->hipFail(e, "hipDeviceSynchronize"); }
+  const double t2 = now_ms();
+  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
+  const double t3 = now_ms();
+  if (rc == HPT_OK) {
+    float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
+    c->lastKernelMs = kms;
+    c->tPathTraceQmc[0] = kms; c->tPathTraceQmc[1] = float(t1 - t0); c->tPathTraceQmc[2] = float(t3 - t2); c->tPathTraceQmc[3] = float((t2 - t1) - kms);
+  }
+  d.release();
+  return rc;
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block"); }
+
 // ---- differentiable rendering ---------------------------------------------------------------------------------------------------------
 extern "C" int hpt_reset_diff_tex(hpt_ctx* c)
 try {
@@ -2472,6 +2589,7 @@ try {
   else if (n == "PathTraceFromInputRays" || n == "PathTraceFromInputRaysBlock") src = c->tFromRays;
   else if (n == "PathTraceDR" || n == "PathTraceDRBlock") src = c->tDR;                     // integrator_dr2.cpp:82-88
   else if (n == "CastSingleRay" || n == "CastSingleRayBlock") src = c->tCastSingleRay;      // main.cpp:443
+  else if (n == "PathTraceQMC" || n == "PathTraceBlockQMC") src = c->tPathTraceQmc;            // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
   else if (n == "RayTrace" || n == "RayTraceBlock") src = c->tRayTrace;                     // raytraceTime (integrator_pt_host.cpp:75-90)
   if (!src) return HPT_OK;                                                                 // unknown names leave `out` untouched, as the reference does
   for (int i = 0; i < 4; i++) out[i] = src[i];

@@ -105,12 +105,11 @@ HPT_DEV bool traceLensesFromFilm(const DevScene& S, V3& rayPos, V3& rayDir)
 // SampleCameraRay + kernel_InitEyeRay2 (integrator_pt.cpp:44-157), RGB subset
 // LENS: the lens-simulation branch exists only in the kernels with every BSDF branch (the host routes scenes with m_enableOpticSim to them):
 // compiled into the lean kernels it cost the Cornell benchmark 0.6 % without ever running (profiles/ab.sh, base vs -DHPT_NO_LENS)
+// cameraRayAt: the ray through the normalised film point (xn, yn); pixelOffsets.zw are the lens numbers. cameraRay derives the point from the
+// pixel and the jitter, the QMC integrator passes its two numbers straight through (IntegratorQMC::SampleCameraRay, integrator_qmc.cpp:148-187).
 template <bool LENS>
-HPT_DEV void cameraRay(const DevScene& S, uint x, uint y, V4 pixelOffsets, V3& rayPos, V3& rayDir)
+HPT_DEV void cameraRayAt(const DevScene& S, const float xn, const float yn, V4 pixelOffsets, V3& rayPos, V3& rayDir)
 {
-  const float fx = float(x) + pixelOffsets.x, fy = float(y) + pixelOffsets.y;
-  const float xn = (fx + float(S.winStartX)) / float(S.fbWidth);
-  const float yn = (fy + float(S.winStartY)) / float(S.fbHeight);
   V4 pos = v4(2.0f * xn - 1.0f, 2.0f * yn - 1.0f, 0.0f, 1.0f);          // EyeRayDirNormalized (cglobals.h:49-55)
   pos = mul4x4(S.projInv, pos);
   V3 dir = normalize(v3(pos.x / pos.w, pos.y / pos.w, pos.z / pos.w));
@@ -136,6 +135,14 @@ HPT_DEV void cameraRay(const DevScene& S, uint x, uint y, V4 pixelOffsets, V3& r
   const V3 p2 = mul4x3(S.worldViewInv, org + 100.0f * dir);
   rayPos = p1;
   rayDir = normalize(p2 - p1);
+}
+template <bool LENS>
+HPT_DEV void cameraRay(const DevScene& S, uint x, uint y, V4 pixelOffsets, V3& rayPos, V3& rayDir)
+{
+  const float fx = float(x) + pixelOffsets.x, fy = float(y) + pixelOffsets.y;
+  const float xn = (fx + float(S.winStartX)) / float(S.fbWidth);
+  const float yn = (fy + float(S.winStartY)) / float(S.fbHeight);
+  cameraRayAt<LENS>(S, xn, yn, pixelOffsets, rayPos, rayDir);
 }
 
 // ---- normal-map bump (integrator_pt_mat.cpp:94-107, 131-139, 298-303, 336-355; NormalMapTransform in include/cmaterial.h) -------------------
@@ -222,6 +229,15 @@ HPT_DEV void blendTreeEval(const DevScene& S, uint rootId, V2 uv, V3 l, V3 v, V3
   } while (top > 0);
 }
 
+// Where a vertex's light and material numbers come from. The default is the pseudo generator in the base class's order (GetRandomNumbersLgts:
+// the light-selection float, then the float4; GetRandomNumbersMats: one float4 - integrator_pt.cpp:29-35); the QMC integrator passes its
+// own source (hpt_qmc.hip: QmcRands).
+struct PseudoRands
+{
+  HPT_DEV V4 lights(Rng& gen, uint /*bounce*/, float& rndId) const { rndId = rng_float1(gen); return rng_float4(gen); }
+  HPT_DEV V4 mats(Rng& gen, uint /*bounce*/) const { return rng_float4(gen); }
+};
+
 // Shades the vertex a closest-hit query returned for one path.  All path registers are passed by reference and the
 // function is always inlined, so both callers keep them in VGPRs.  Returns true when the path continues (didBounce).
 // A miss only sets the OUT_OF_SCENE flags.  The caller traces the shadow ray (if wantShadow) and adds `contrib`.
@@ -229,11 +245,11 @@ HPT_DEV void blendTreeEval(const DevScene& S, uint rootId, V2 uv, V3 l, V3 v, V3
 // LEAN: the scene holds gltf and emissive materials only (the host checked): the conductor / diffuse / glass / dielectric branches are
 // compiled out - fewer live registers and spills in the kernels every benchmark scene runs (the DR variant is lean by definition).
 // FILM: the scene holds thin films (MAT_TYPE_THIN_FILM, hpt_film.h): their branches exist in the FILM variants only.
-template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false>
+template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false, class RANDS = PseudoRands>
 HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec& hit,
                          V3& rpos, V3& rdir, V3& accum, V3& thr, float& misPdf, float& misIor, uint& flags, const uint bounce, Rng& gen,
                          bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V3& contrib,
-                         V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f)
+                         V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f, const RANDS rands_ = RANDS())
 {
   bool didBounce = false;
   if (hit.inst == 0xFFFFFFFFu) {
@@ -307,8 +323,8 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
     const V3 baseCol = ld3(m.colors[GLTF_COLOR_BASE]);
 
     if (!NAIVE) {
-      const float rndId = rng_float1(gen);                             // GetRandomNumbersLgts: two generator steps, in this order
-      const V4 r4 = rng_float4(gen);
+      float rndId;                                                     // GetRandomNumbersLgts: two generator steps (PseudoRands: the float, then the float4)
+      const V4 r4 = rands_.lights(gen, bounce, rndId);
       const int nLights = (int)S.numLights;
       const int lightId = min((int)floorf(rndId * float(nLights)), nLights - 1);
       if (lightId >= 0 && mtype != MAT_TYPE_LIGHT_SOURCE) {
@@ -403,7 +419,7 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
       const bool leafBump = !(DR || LEAN) && ml.texid[1] != 0xFFFFFFFFu;        // the leaf's normal map bends the shading normal (:131-139)
       V3 sNorm = hitNorm;
       if (leafBump) sNorm = bumpNormal(S, ml, hitNorm, hitTang, uv);
-      const V4 rands = rng_float4(gen);                                // GetRandomNumbersMats: drawn for every material type (integrator_pt_mat.cpp:147)
+      const V4 rands = rands_.mats(gen, bounce);                       // GetRandomNumbersMats: drawn for every material type (integrator_pt_mat.cpp:147)
       if (lt == MAT_TYPE_GLTF) gltfSampleAndEval(ml, rands, vdir, sNorm, ld3(ml.colors[GLTF_COLOR_BASE]) * ltex3, lfour, ms);
       else if (!(DR || LEAN) && lt == MAT_TYPE_CONDUCTOR) {
         if (smax(ml.data[1], ml.data[0]) < 1e-3f) conductorSmoothSampleAndEval(ml, ml.data[2], ml.data[3], vdir, sNorm, ms);

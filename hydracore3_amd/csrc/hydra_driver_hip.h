@@ -46,6 +46,7 @@ struct HydraHipRenderDriver : IRenderDriver
   bool valid() const { return m_ctx != nullptr; }
   enum RenderMode { RENDER_PATH_TRACE = 0, RENDER_CAST_SINGLE_RAY = 1 };      // which block call Render makes (hydra_cpu.cpp:105-106)
   void SetRenderMode(RenderMode a_mode) { m_mode = a_mode; }
+  void SetQMC(bool a_on) { m_qmc = a_on; }                                     // `hydra --qmc`: the path-trace mode calls IntegratorQMC's PathTraceBlock; off by default
   const std::string& lastError() const { return m_err; }
 
   bool LoadScene(const std::string& a_xmlText, const std::string& a_folder, const RDScene_Input& a_input, uint32_t a_updateFlags) override
@@ -101,7 +102,8 @@ struct HydraHipRenderDriver : IRenderDriver
       return;
     }
     if (rc == HPT_OK && m_gens != (uint32_t)(sizeX * (int)sizeY)) { rc = hpt_init_random_gens(m_ctx, (uint32_t)(sizeX * (int)sizeY)); m_gens = (uint32_t)(sizeX * (int)sizeY); }   // (the reference's constructor seeds 1024 x 1024 generators once)
-    if (rc == HPT_OK) rc = hpt_path_trace_block(m_ctx, 0, (uint32_t)(sizeX * (int)sizeY), channels, data, a_passNumber);      // m_pImpl->PathTraceBlock(sizeX*sizeY, channels, data, a_passNumber)
+    if (rc == HPT_OK && m_qmc) rc = hpt_path_trace_qmc_block(m_ctx, (uint32_t)(sizeX * (int)sizeY), channels, data, a_passNumber);   // ... of an IntegratorQMC
+    else if (rc == HPT_OK) rc = hpt_path_trace_block(m_ctx, 0, (uint32_t)(sizeX * (int)sizeY), channels, data, a_passNumber);      // m_pImpl->PathTraceBlock(sizeX*sizeY, channels, data, a_passNumber)
     if (rc != HPT_OK) m_err = hpt_last_error(m_ctx);
   }
 
@@ -111,6 +113,7 @@ struct HydraHipRenderDriver : IRenderDriver
   std::string m_err;
   bool m_loaded = false, m_committed = false; uint32_t m_gens = 0;
   RenderMode m_mode = RENDER_PATH_TRACE;
+  bool m_qmc = false;
 };
 
 inline std::shared_ptr<IRenderDriver> MakeHydraRenderHIP(int device = 0) { return std::make_shared<HydraHipRenderDriver>(device); }   // HR2::MakeHydraRenderCPU's counterpart (hydra_cpu.cpp:20-23)

@@ -248,6 +248,16 @@ protected:
 };
 
 // ---- IntegratorDR-shaped front end (diff_render/integrator_dr.h:27-136) -------------------------------------------------------
+// IntegratorQMC (mlt/integrator_qmc.h): the subclass whose PathTraceBlock runs the Niederreiter sequence over pixels x passes samples. `tid`
+// is the reference's pixelsNum; the sampler's table lives with the context (hpt_qmc_table gives a copy).
+class IntegratorQMCHIP : public IntegratorHIP
+{
+public:
+  using IntegratorHIP::IntegratorHIP;
+  void PathTraceBlock(uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t a_passNum) override
+  { if (m_ctx) report(hpt_path_trace_qmc_block(m_ctx, pixelsNum, channels, out_color, a_passNum), "PathTraceBlockQMC"); }
+};
+
 class IntegratorDRHIP : public IntegratorHIP
 {
 public:

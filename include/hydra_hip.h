@@ -278,6 +278,33 @@ int  hpt_ray_trace_block(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* o
 int  hpt_cast_single_ray_block_dev(hpt_ctx* ctx, uint32_t tid, float* outDev, uint32_t passNum, void* stream);
 int  hpt_ray_trace_block_dev(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* outDev, uint32_t passNum, void* stream);
 
+/* ---- quasi-Monte-Carlo path tracing (mlt/integrator_qmc.{h,cpp}, mlt/rnd_qmc.{h,cpp}; `hydra --qmc`) ------------------ */
+/* qmc::init: the 11 x 31 table of 31-bit Niederreiter base-2 generator-matrix columns, out[dim * 31 + bit]. qmc::rndFloat(pos, dim) is the
+ * XOR of the columns the low 31 bits of pos select, plus one, times 2^-31 in float (it reaches 1.0). Host code; no context, no GPU. */
+int  hpt_qmc_table(uint32_t out[341]);
+/* IntegratorQMC::EnableQMC (integrator_qmc.cpp:11-86): out = { m_qmcDofDim, m_qmcSpdDim, m_qmcMotionDim, m_qmcMatDim, m_qmcLgtDim } for
+ * a scene with (dof = lens radius > 0 or lens stack, spectral = m_spectral_mode, motion = moving instances); 0 = that draw stays with the
+ * pseudo generator. Host code; no context, no GPU. */
+int  hpt_qmc_layout(int dof, int spectral, int motion, uint32_t out[5]);
+/* IntegratorQMC::PathTraceBlock(pixelsNum, channels, out_color, a_passNum) (integrator_qmc.cpp:284-315): S = min(2^32 - 1, pixelsNum *
+ * a_passNum) samples of the Niederreiter sequence. Sample s takes its film position, lens point, time and the first bounce's material and
+ * light numbers from the table (hpt_qmc_layout says which), everything else from generator s % N, N = the size InitRandomGens gave; its
+ * pixel is x = min(uint(u0 * winWidth), winWidth - 1), y likewise from u1, and exposure * (colour * camRespoceRGB) is ADDED to that pixel
+ * (channels 3 / 4: rgb; channels 1: the luma 0.2126 / 0.7152 / 0.0722). out_color = winWidth * winHeight * channels floats in host memory.
+ * Samples s, s + N, s + 2N ... run in that order on generator s % N (what the reference computes on one thread: DESIGN.md 7); the sum
+ * into a pixel is made with float atomics, so the frame is reproducible to rounding only. HPT_ERR_UNSUPPORTED with m_spectral_mode on and
+ * for channels 2 or above 4; HPT_ERR_ARG for a null context or buffer and before InitRandomGens (N = 0); HPT_ERR_STATE before
+ * CommitDeviceData, UpdateMembersPlainData or PackXYBlock. Megakernel schedule only. hpt_get_execution_time("PathTraceBlockQMC") gives its four slots. */
+int  hpt_path_trace_qmc_block(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t passNum);
+/* The same on device memory, asynchronous on stream. sampleColorDev (4 floats per sample) and samplePixelDev (one uint32 per sample),
+ * either both NULL or both S elements long, receive for sample index s the colour as it was added (rgb and 0; channels 1: the luma and three
+ * zeros) and the pixel index y * winWidth + x: these records are bit-reproducible and let a caller compose a deterministic frame. outDev may
+ * be NULL when the records are asked for; all three NULL is HPT_ERR_ARG. */
+int  hpt_path_trace_qmc_block_dev(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                  float* sampleColorDev, uint32_t* samplePixelDev, void* stream);
+/* S of the two calls above for (pixelsNum, passNum): min(2^32 - 1, pixelsNum * passNum). Host code; no context. */
+uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum);
+
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
