@@ -256,9 +256,10 @@ HPT_DEV V4 texel(const TexRec& t, int off)
   return v4(v, v, v, v);
 }
 
-HPT_DEV V4 texSample(const TexRec* texs, uint texId, V2 uv)
+// The filtered fetch without the sRGB decode (the texture record comes back in `t`: its flags say whether a decode is due)
+HPT_DEV V4 texFetch(const TexRec* texs, uint texId, V2 uv, TexRec& t)
 {
-  const TexRec t = texs[texId];
+  t = texs[texId];
   V4 res;
   if (t.filter == 0) {
     int px = (int)floorf(uv.x * float(t.w)), py = (int)floorf(uv.y * float(t.h));
@@ -273,30 +274,21 @@ HPT_DEV V4 texSample(const TexRec* texs, uint texId, V2 uv)
     res.z = a.z * k.w[0] + b.z * k.w[1] + c.z * k.w[2] + d.z * k.w[3];
     res.w = a.w * k.w[0] + b.w * k.w[1] + c.w * k.w[2] + d.w * k.w[3];
   }
+  return res;
+}
+HPT_DEV V4 texSample(const TexRec* texs, uint texId, V2 uv)
+{
+  TexRec t; V4 res = texFetch(texs, texId, uv, t);
   if (t.flags & 1u) { res.x = powf(res.x, 2.2f); res.y = powf(res.y, 2.2f); res.z = powf(res.z, 2.2f); }
   return res;
 }
 // texSample with the sRGB decode CORRECTLY ROUNDED (the power in double, rounded to float once) instead of the device's powf, which is
 // faithful but off by one in the last bit for about 3 % of its arguments (profiles/gbuffer.md). For the passes whose colours are compared
-// bit by bit with a float32 restatement on the host (hpt_raytrace.hip; hpt_gbuffer.hip holds the same sampler as gbTexSample).
+// bit by bit with a float32 restatement on the host (hpt_gbuffer.hip, hpt_raytrace.hip).
 HPT_DEV float srgbDecodeRounded(float v) { return (float)pow((double)v, (double)2.2f); }
 HPT_DEV V4 texSampleRounded(const TexRec* texs, uint texId, V2 uv)
 {
-  const TexRec t = texs[texId];
-  V4 res;
-  if (t.filter == 0) {
-    int px = (int)floorf(uv.x * float(t.w)), py = (int)floorf(uv.y * float(t.h));
-    px = (t.addrU == 2) ? min(max(px, 0), (int)t.w - 1) : wrapi(px, (int)t.w);
-    py = (t.addrV == 2) ? min(max(py, 0), (int)t.h - 1) : wrapi(py, (int)t.h);
-    res = texel(t, py * (int)t.w + px);
-  } else {
-    const Taps k = bilinearTaps(t.w, t.h, t.addrU, t.addrV, uv);
-    const V4 a = texel(t, k.off[0]), b = texel(t, k.off[1]), c = texel(t, k.off[2]), d = texel(t, k.off[3]);
-    res.x = a.x * k.w[0] + b.x * k.w[1] + c.x * k.w[2] + d.x * k.w[3];
-    res.y = a.y * k.w[0] + b.y * k.w[1] + c.y * k.w[2] + d.y * k.w[3];
-    res.z = a.z * k.w[0] + b.z * k.w[1] + c.z * k.w[2] + d.z * k.w[3];
-    res.w = a.w * k.w[0] + b.w * k.w[1] + c.w * k.w[2] + d.w * k.w[3];
-  }
+  TexRec t; V4 res = texFetch(texs, texId, uv, t);
   if (t.flags & 1u) { res.x = srgbDecodeRounded(res.x); res.y = srgbDecodeRounded(res.y); res.z = srgbDecodeRounded(res.z); }
   return res;
 }

@@ -12,6 +12,7 @@
 // arithmetic in numpy float32 and the GPU tests ask for equal bits.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
+#include "hpt_primary.h"
 
 namespace hpt {
 
@@ -50,32 +51,6 @@ HPT_DEV float gbDiff(float4 s1, float4 id1, float ppSize, float4 s2, float4 id2)
   return surfaceDiff + objDiff + matDiff + alphaDiff;
 }
 
-// texSample (hpt_device.h: the same taps, weights and texel decode) with the sRGB decode rgb^2.2 CORRECTLY ROUNDED: the power is taken in double
-// and rounded to float once. The device's powf is faithful but off by one in the last bit for about 3 % of its arguments; a host's powf is
-// correctly rounded for all but a few in 10^4. The albedo is averaged over 16 samples and compared across implementations bit by bit, so the
-// pass does not add the library's rounding to it (profiles/gbuffer.md).
-HPT_DEV float gbSrgbDecode(float v) { return (float)pow((double)v, (double)2.2f); }
-HPT_DEV V4 gbTexSample(const TexRec* texs, uint texId, V2 uv)
-{
-  const TexRec t = texs[texId];
-  V4 res;
-  if (t.filter == 0) {
-    int px = (int)floorf(uv.x * float(t.w)), py = (int)floorf(uv.y * float(t.h));
-    px = (t.addrU == 2) ? min(max(px, 0), (int)t.w - 1) : wrapi(px, (int)t.w);
-    py = (t.addrV == 2) ? min(max(py, 0), (int)t.h - 1) : wrapi(py, (int)t.h);
-    res = texel(t, py * (int)t.w + px);
-  } else {
-    const Taps k = bilinearTaps(t.w, t.h, t.addrU, t.addrV, uv);
-    const V4 a = texel(t, k.off[0]), b = texel(t, k.off[1]), c = texel(t, k.off[2]), d = texel(t, k.off[3]);
-    res.x = a.x * k.w[0] + b.x * k.w[1] + c.x * k.w[2] + d.x * k.w[3];
-    res.y = a.y * k.w[0] + b.y * k.w[1] + c.y * k.w[2] + d.y * k.w[3];
-    res.z = a.z * k.w[0] + b.z * k.w[1] + c.z * k.w[2] + d.z * k.w[3];
-    res.w = a.w * k.w[0] + b.w * k.w[1] + c.w * k.w[2] + d.w * k.w[3];
-  }
-  if (t.flags & 1u) { res.x = gbSrgbDecode(res.x); res.y = gbSrgbDecode(res.y); res.z = gbSrgbDecode(res.z); }
-  return res;
-}
-
 // kernelBE1D_EvalGBuffer (integrator_gbuffer.cpp:243-258): lane = (pixel blockId, sample localId)
 template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uint* packedXY, uint blockNum, GBufferPixel* out, GBufferPixel* samples, uint* stackOverflow)
@@ -92,19 +67,11 @@ __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uin
   const uint k = g & 15u;
 
   // -- kernel_InitEyeRayGB (integrator_gbuffer.cpp:91-108); PlaneHammersley (:8-24): u = radical inverse of k in base 2, v = (k + 0.5) / 16 --
-  const uint XY = packedXY[blockId];
-  const uint x = XY & 0x0000FFFFu, y = (XY & 0xFFFF0000u) >> 16;
   float hu = 0.0f;
   { uint kk = k; for (float p = 0.5f; kk; p *= 0.5f, kk >>= 1) if (kk & 1u) hu += p; }
   const float hv = (float(k) + 0.5f) / float(GBUFFER_SAMPLES);
-  const float xn = (float(x + (uint)S.winStartX) + hu) / float(S.fbWidth);     // the integer add first: not cameraRay's order (hpt_shade.h)
-  const float yn = (float(y + (uint)S.winStartY) + hv) / float(S.fbHeight);
-  V4 pos = v4(2.0f * xn - 1.0f, 2.0f * yn - 1.0f, 0.0f, 1.0f);                   // EyeRayDirNormalized (cglobals.h:49-55)
-  pos = mul4x4(S.projInv, pos);
-  const V3 dir = normalize(v3(pos.x / pos.w, pos.y / pos.w, pos.z / pos.w));
-  const V3 p1 = mul4x3(S.worldViewInv, v3(0, 0, 0));                             // transform_ray3f (cglobals.h:254-263); always a pinhole
-  const V3 p2 = mul4x3(S.worldViewInv, v3(0, 0, 0) + 100.0f * dir);
-  const V3 rayPos = p1, rayDir = normalize(p2 - p1);
+  uint x, y; V3 rayPos, rayDir;
+  pinholeEyeRay(S, packedXY[blockId], hu, hv, x, y, rayPos, rayDir);
 
   // -- kernel_RayTrace: RayQuery_NearestHit, tnear 0, tfar FLT_MAX; moving instances at time 0 --
   HitRec h; TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
@@ -117,26 +84,14 @@ __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uin
   r.matId = -1; r.objId = -1; r.instId = -1;
   if (found) {
     const uint instId = h.inst, geomId = S.insts[instId].geomId;
-    const uint triOffset = S.matVertOffset[2 * geomId + 0], vertOffset = S.matVertOffset[2 * geomId + 1];
-    const uint matId = S.matIdByPrimId[triOffset + h.prim];              // no remap list, no blend resolution: as the reference
+    V3 nrmO; V2 uv; uint matId;
+    gatherHitVertex(S, h, nrmO, uv, matId);                              // no remap list, no blend resolution: as the reference
     const MaterialRec& m = S.materials[matId & 0x00FFFFFFu];            // (the upload checks the id under this mask)
-    const float uvx = h.v, uvy = h.u;                                    // coords[0] = v, coords[1] = u (EmbreeRT.cpp:350-352)
-    const uint A = S.triIndices[(triOffset + h.prim) * 3 + 0];
-    const uint B = S.triIndices[(triOffset + h.prim) * 3 + 1];
-    const uint C = S.triIndices[(triOffset + h.prim) * 3 + 2];
-    const float4 nA = ((const float4*)S.vData8f)[2 * (A + vertOffset)], nB = ((const float4*)S.vData8f)[2 * (B + vertOffset)], nC = ((const float4*)S.vData8f)[2 * (C + vertOffset)];
-    const float tyA = S.vData8f[8 * (A + vertOffset) + 7], tyB = S.vData8f[8 * (B + vertOffset) + 7], tyC = S.vData8f[8 * (C + vertOffset) + 7];
-    const float wA = 1.0f - uvx - uvy;
-    const V3 nrmO = v3(wA * nA.x + uvy * nB.x + uvx * nC.x, wA * nA.y + uvy * nB.y + uvx * nC.y, wA * nA.z + uvy * nB.z + uvx * nC.z);
-    const V2 uv = v2(wA * nA.w + uvy * nB.w + uvx * nC.w, wA * tyA + uvy * tyB + uvx * tyC);
-    const float* nm = S.normMat + 12 * instId;                           // mul3x3(m_normMatrices[instId], hitNorm), normalised, NOT flipped towards the ray
-    const V3 hitNorm = normalize(v3(nm[0] * nrmO.x + nm[1] * nrmO.y + nm[2] * nrmO.z,
-                                    nm[4] * nrmO.x + nm[5] * nrmO.y + nm[6] * nrmO.z,
-                                    nm[8] * nrmO.x + nm[9] * nrmO.y + nm[10] * nrmO.z));
+    const V3 hitNorm = normalize(mulNormMat(S.normMat + 12 * instId, nrmO));   // mul3x3(m_normMatrices[instId], hitNorm), normalised, NOT flipped towards the ray
     const V2 texCoordT = mulRows2x4(m.row0[0], m.row1[0], uv);
     V3 color = v3(0, 0, 0);
     if (m.mtype != MAT_TYPE_LIGHT_SOURCE) {                              // colors[GLTF_COLOR_BASE] whatever mtype is; a light source gives 0 (its texture tap is dead)
-      const V4 texColor = gbTexSample(S.textures, m.texid[0], texCoordT);
+      const V4 texColor = texSampleRounded(S.textures, m.texid[0], texCoordT);
       color = v3(m.colors[GLTF_COLOR_BASE][0] * texColor.x, m.colors[GLTF_COLOR_BASE][1] * texColor.y, m.colors[GLTF_COLOR_BASE][2] * texColor.z);
     }
     r.depth = h.t; r.norm[0] = hitNorm.x; r.norm[1] = hitNorm.y; r.norm[2] = hitNorm.z; r.texc[0] = texCoordT.x; r.texc[1] = texCoordT.y;
@@ -183,7 +138,7 @@ __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uin
 }
 
 #define HPT_GB_INST(FLAT, MOTION, SWEEP) template __global__ void gbufferKernel<FLAT, MOTION, SWEEP>(const DevScene, const uint*, uint, GBufferPixel*, GBufferPixel*, uint*);
-HPT_GB_INST(false, false, true)     // the traversal variants ray_query() dispatches (hpt_host.hip): sweep, single-level, single-level with motion,
+HPT_GB_INST(false, false, true)     // the traversal variants traversalDispatch() picks (hpt_host.hip): sweep, single-level, single-level with motion,
 HPT_GB_INST(true, true, false)      // two-level, two-level with motion
 HPT_GB_INST(true, false, false)
 HPT_GB_INST(false, true, false)

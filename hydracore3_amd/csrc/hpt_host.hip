@@ -18,6 +18,7 @@
 #include <sched.h>
 #include <thread>
 #include <atomic>
+#include <type_traits>
 
 #include "../../include/hydra_hip.h"
 #include "hpt_decl.h"
@@ -959,6 +960,20 @@ static hipError_t ensureStackOverflow(hpt_ctx* c, size_t lanes)
   return c->dStackOvf.alloc(extra * lanes);
 }
 
+// The traversal variant of the committed layout for the kernels that are built for five of them (rayQueryKernel, gbufferKernel, castSingleRayKernel,
+// rayTraceKernel): sweep; single-level with motion; single-level; two-level with motion; two-level. f gets (FLAT, MOTION, SWEEP) as
+// std::bool_constant objects, i.e. as compile-time constants. (The path-tracing ladders also switch on the stack depth and are their own.)
+template <class F>
+static void traversalDispatch(const hpt_ctx* c, F f)
+{
+  const std::true_type T; const std::false_type N;
+  if (c->S.sweep)                         f(N, N, T);
+  else if (c->S.flatMode && c->anyMotion) f(T, T, N);
+  else if (c->S.flatMode)                 f(T, N, N);
+  else if (c->anyMotion)                  f(N, T, N);
+  else                                    f(N, N, N);
+}
+
 static int ray_query(hpt_ctx* c, const float* posNear, const float* dirFar, uint32_t n, void* out, int any, float time = 0.0f)
 {
   if (!c || !posNear || !dirFar || !out) return HPT_ERR_ARG;
@@ -972,14 +987,11 @@ static int ray_query(hpt_ctx* c, const float* posNear, const float* dirFar, uint
   HIPCHK(c, dout.alloc(outWords));
   const uint blocks = (n + 255) / 256;
   HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-  if (c->S.sweep)        rayQueryKernel<false, false, true><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p);
-  else if (c->S.flatMode && c->anyMotion) rayQueryKernel<true, true><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p, time);
-  else if (c->S.flatMode) rayQueryKernel<true><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p);
-  else if (c->anyMotion) rayQueryKernel<false, true><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p, time);
-  else                   rayQueryKernel<false><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p);
+  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {           // the time goes to the motion variants only
+    rayQueryKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p, motion() ? time : 0.0f);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipMemcpy(out, dout.p, outWords * 4, hipMemcpyDeviceToHost));
-  dp.release(); dd.release(); dout.release();
   return HPT_OK;
 }
 
@@ -2032,28 +2044,51 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_block_dev"); }
 
+// The round trip of the host-pointer entry points: up() copies the caller's buffers to the device, launch() runs the device-pointer form,
+// down() copies the results back; each returns an HPT_ code. The kernel time is the event pair the device-pointer form recorded; it goes to
+// hpt_last_kernel_ms and, with the copy times, to the four GetExecutionTime slots: kernel, copy in, copy out, overhead (main.cpp:417-419).
+enum KernelTime { KERNEL_EVENTS,       // read the event pair
+                  KERNEL_NONE,         // nothing was launched (a zero-size call that still makes its copies): the kernel time is 0
+                  KERNEL_UNTIMED };    // the device-pointer form records no events: hpt_last_kernel_ms and the slots stay as they are
+template <class Up, class Launch, class Down>
+static int roundTrip(hpt_ctx* c, float* slots, KernelTime kt, Up up, Launch launch, Down down)
+{
+  const double t0 = now_ms();
+  if (int rc = up()) return rc;
+  const double t1 = now_ms();
+  if (int rc = launch()) return rc;
+  HIPCHK(c, hipDeviceSynchronize());
+  const double t2 = now_ms();
+  if (int rc = down()) return rc;
+  const double t3 = now_ms();
+  if (kt == KERNEL_UNTIMED) return HPT_OK;
+  float kms = 0.0f;
+  if (kt == KERNEL_EVENTS) (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
+  c->lastKernelMs = kms;
+  if (slots) { slots[0] = kms; slots[1] = float(t1 - t0); slots[2] = float(t3 - t2); slots[3] = float((t2 - t1) - kms); }
+  return HPT_OK;
+}
+// ... with one call-local device copy of one host buffer of n elements: up (unless `upload` is false: every element is written), launch(device pointer), down
+template <class T, class Launch>
+static int roundTrip(hpt_ctx* c, float* slots, T* host, size_t n, bool upload, Launch launch)
+{
+  DevBuf<T> d;
+  return roundTrip(c, slots, KERNEL_EVENTS,
+                   [&]() -> int { HIPCHK(c, d.alloc(n)); if (upload) HIPCHK(c, hipMemcpy(d.p, host, n * sizeof(T), hipMemcpyHostToDevice)); return HPT_OK; },
+                   [&]() -> int { return launch(d.p); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(host, d.p, n * sizeof(T), hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+
 static int path_trace_host(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, uint32_t passNum, int naive)
 {
   if (!c || !out) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
   if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before UpdateMembersPlainData");
-  float* slots = naive ? c->tNaive : c->tPathTrace;
   const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
-  const double t0 = now_ms();
-  HIPCHK(c, c->dFrame.alloc(n));
-  HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));            // the callee ACCUMULATES into the caller's buffer
-  const double t1 = now_ms();
-  int rc = hpt_path_trace_block_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, naive, nullptr);
-  if (rc) return rc;
-  HIPCHK(c, hipDeviceSynchronize());
-  const double t2 = now_ms();
-  HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost));
-  const double t3 = now_ms();
-  float kms = 0.0f;
-  if (tidCount && passNum) (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
-  c->lastKernelMs = kms;
-  slots[0] = kms; slots[1] = float(t1 - t0); slots[2] = float(t3 - t2); slots[3] = float((t2 - t1) - kms);
-  return HPT_OK;
+  return roundTrip(c, naive ? c->tNaive : c->tPathTrace, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+                   [&]() -> int { HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice)); return HPT_OK; },   // the callee ACCUMULATES into the caller's buffer
+                   [&]() -> int { return hpt_path_trace_block_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, naive, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost)); return HPT_OK; });
 }
 
 // PathTraceFromInputRaysBlock (integrator_pt.h:261, integrator_pt_host.cpp:92-103): device and host-pointer forms
@@ -2075,21 +2110,10 @@ try {
   if (tid == 0 || passNum == 0) return HPT_OK;
   DevBuf<float> dp, dd, dout;
   const size_t n = (size_t)tid * channels;
-  const double t0 = now_ms();
-  HIPCHK(c, dp.upload(rayPos, (size_t)tid * 4)); HIPCHK(c, dd.upload(rayDir, (size_t)tid * 4)); HIPCHK(c, dout.upload(out, n));
-  const double t1 = now_ms();
-  int rc = hpt_path_trace_from_input_rays_block_dev(c, tid, channels, dp.p, dd.p, dout.p, passNum, nullptr);
-  if (rc == HPT_OK) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = c->hipFail(e, "hipDeviceSynchronize"); }
-  const double t2 = now_ms();
-  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
-  const double t3 = now_ms();
-  if (rc == HPT_OK) {                                                      // fromRaysPtTime (integrator_pt_host.cpp:92-103) in GetExecutionTime's four slots
-    float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
-    c->lastKernelMs = kms;
-    c->tFromRays[0] = kms; c->tFromRays[1] = float(t1 - t0); c->tFromRays[2] = float(t3 - t2); c->tFromRays[3] = float((t2 - t1) - kms);
-  }
-  dp.release(); dd.release(); dout.release();
-  return rc;
+  return roundTrip(c, c->tFromRays, KERNEL_EVENTS,                        // fromRaysPtTime (integrator_pt_host.cpp:92-103) in GetExecutionTime's four slots
+                   [&]() -> int { HIPCHK(c, dp.upload(rayPos, (size_t)tid * 4)); HIPCHK(c, dd.upload(rayDir, (size_t)tid * 4)); HIPCHK(c, dout.upload(out, n)); return HPT_OK; },
+                   [&]() -> int { return hpt_path_trace_from_input_rays_block_dev(c, tid, channels, dp.p, dd.p, dout.p, passNum, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_from_input_rays_block"); }
 
@@ -2102,17 +2126,25 @@ catch (...) { return hptGuard(c, "hpt_naive_path_trace_block"); }
 
 // ---- EvalGBuffer (integrator_pt.h:251, integrator_gbuffer.cpp:264-267) ------------------------------------------------------------------------
 static_assert(sizeof(hpt_gbuffer_pixel) == 60 && sizeof(hpt_gbuffer_pixel) == sizeof(GBufferPixel), "GBufferPixel is 15 dwords (integrator_pt.h:187-198)");
-// Device-pointer form: 16 lanes per pixel through the traversal variant ray_query() would take (hpt_gbuffer.hip). The pass draws no random
+// What a per-pixel pass (EvalGBuffer, CastSingleRayBlock, RayTraceBlock) needs before it can run, in the order the reference's driver makes its
+// calls. `what` names the reference's method, `outName` its output argument, `countName` its pixel count.
+static int pixelPassCheck(hpt_ctx* c, const char* what, const char* outName, const void* out, const char* countName, uint32_t count)
+{
+  const std::string w(what);
+  if (!out) return c->fail(HPT_ERR_ARG, w + ": " + outName + " is null");
+  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, w + " before CommitDeviceData");
+  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, w + " before CommitScene");
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, w + " before UpdateMembersPlainData");
+  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, w + " before PackXYBlock");
+  if (count > c->packedCount) return c->fail(HPT_ERR_ARG, w + ": " + countName + " exceeds the packed pixel count");
+  return HPT_OK;
+}
+// Device-pointer form: 16 lanes per pixel through the traversal variant of the committed layout (hpt_gbuffer.hip). The pass draws no random
 // numbers and changes no state of the context; it reads only RGB base colours, so m_spectral_mode does not matter. Asynchronous.
 extern "C" int hpt_eval_gbuffer_dev(hpt_ctx* c, uint32_t blockNum, hpt_gbuffer_pixel* outDev, hpt_gbuffer_pixel* samplesDev, void* stream)
 try {
   if (!c) return HPT_ERR_ARG;
-  if (!outDev) return c->fail(HPT_ERR_ARG, "EvalGBuffer: out_gbuffer is null");
-  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitDeviceData");
-  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitScene");
-  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "EvalGBuffer before UpdateMembersPlainData");
-  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "EvalGBuffer before PackXYBlock");
-  if (blockNum > c->packedCount) return c->fail(HPT_ERR_ARG, "EvalGBuffer: blockNum exceeds the packed pixel count");
+  if (int rc = pixelPassCheck(c, "EvalGBuffer", "out_gbuffer", outDev, "blockNum", blockNum)) return rc;
   if (blockNum == 0u) return HPT_OK;
   (void)hipSetDevice(c->device);
   hipStream_t st = (hipStream_t)stream;
@@ -2120,55 +2152,29 @@ try {
   HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
   GBufferPixel* o = (GBufferPixel*)outDev; GBufferPixel* sm = (GBufferPixel*)samplesDev;
   HIPCHK(c, hipEventRecord(c->ev0, st));
-  if (c->S.sweep)                         gbufferKernel<false, false, true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
-  else if (c->S.flatMode && c->anyMotion) gbufferKernel<true, true, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
-  else if (c->S.flatMode)                 gbufferKernel<true, false, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
-  else if (c->anyMotion)                  gbufferKernel<false, true, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
-  else                                    gbufferKernel<false, false, false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+    gbufferKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev1, st));
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_eval_gbuffer_dev"); }
 // Integrator::EvalGBuffer(blockNum, out_gbuffer) (integrator_pt.h:251; main.cpp:269-277): host pointer to winWidth * winHeight records. The
-// reference writes only the records of pixels packedXY[0 .. blockNum); so does this: the caller's buffer goes up and comes back.
+// reference writes only the records of pixels packedXY[0 .. blockNum); so does this: the caller's buffer goes up (when some record is not
+// written) and comes back. No GetExecutionTime slot.
 extern "C" int hpt_eval_gbuffer(hpt_ctx* c, uint32_t blockNum, hpt_gbuffer_pixel* out)
 try {
   if (!c) return HPT_ERR_ARG;
-  if (!out) return c->fail(HPT_ERR_ARG, "EvalGBuffer: out_gbuffer is null");
-  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitDeviceData");      // (before the window size below means anything)
-  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, "EvalGBuffer before CommitScene");
-  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "EvalGBuffer before UpdateMembersPlainData");
-  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "EvalGBuffer before PackXYBlock");
-  if (blockNum > c->packedCount) return c->fail(HPT_ERR_ARG, "EvalGBuffer: blockNum exceeds the packed pixel count");
+  if (int rc = pixelPassCheck(c, "EvalGBuffer", "out_gbuffer", out, "blockNum", blockNum)) return rc;   // (before packedCount below means anything)
   if (blockNum == 0u) return HPT_OK;
   (void)hipSetDevice(c->device);
-  DevBuf<hpt_gbuffer_pixel> d;
-  const size_t n = (size_t)c->packedCount;
-  const bool partial = blockNum < c->packedCount;
-  HIPCHK(c, d.alloc(n));
-  if (partial) HIPCHK(c, hipMemcpy(d.p, out, n * sizeof(hpt_gbuffer_pixel), hipMemcpyHostToDevice));
-  int rc = hpt_eval_gbuffer_dev(c, blockNum, d.p, nullptr, nullptr);
-  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(hpt_gbuffer_pixel), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
-  if (rc == HPT_OK) { float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1); c->lastKernelMs = kms; }
-  d.release();
-  return rc;
+  return roundTrip(c, nullptr, out, (size_t)c->packedCount, blockNum < c->packedCount,
+                   [&](hpt_gbuffer_pixel* d) { return hpt_eval_gbuffer_dev(c, blockNum, d, nullptr, nullptr); });
 }
 catch (...) { return hptGuard(c, "hpt_eval_gbuffer"); }
 
 // ---- CastSingleRayBlock / RayTraceBlock (integrator_pt.h:254, 263; integrator_rt.cpp:420-461; integrator_pt_host.cpp:29-36, 75-90) ----------------
-// What both passes need before they can run, in the words hpt_eval_gbuffer uses. `what` names the reference's method.
-static int rt_check(hpt_ctx* c, const char* what, const void* out, uint32_t tid)
-{
-  const std::string w(what);
-  if (!out) return c->fail(HPT_ERR_ARG, w + ": out_color is null");
-  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, w + " before CommitDeviceData");
-  if (!c->accelCommitted) return c->fail(HPT_ERR_STATE, w + " before CommitScene");
-  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, w + " before UpdateMembersPlainData");
-  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, w + " before PackXYBlock");
-  if (tid > c->packedCount) return c->fail(HPT_ERR_ARG, w + ": tid exceeds the packed pixel count");
-  return HPT_OK;
-}
 // channels of RayTraceBlock: 1 and 2 are refused (the reference writes three floats at that stride: over the next pixel and, for the last
 // one, past the buffer - DESIGN.md 7); above 4 its kernel_ContributeToImage3 writes nothing, so there is nothing to launch
 static int rt_check_channels(hpt_ctx* c, uint32_t channels)
@@ -2176,48 +2182,28 @@ static int rt_check_channels(hpt_ctx* c, uint32_t channels)
   if (channels < 3u) return c->fail(HPT_ERR_ARG, "RayTraceBlock: channels must be 3 or 4 (1 and 2 make the reference write outside the pixel; above 4 nothing is written)");
   return HPT_OK;
 }
-// one lane per pixel through the traversal variant ray_query() would take (hpt_raytrace.hip); channels = 0: CastSingleRay
+// one lane per pixel through the traversal variant of the committed layout (hpt_raytrace.hip); channels = 0: CastSingleRay
 static int rt_launch(hpt_ctx* c, uint32_t tid, uint32_t channels, float* outDev, hipStream_t st)
 {
   (void)hipSetDevice(c->device);
   const uint blocks = (tid + 255u) / 256u;
   HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
   HIPCHK(c, hipEventRecord(c->ev0, st));
-#define HPT_RT_LAUNCH(FLAT, MOTION, SWEEP) do { \
-    if (channels == 0u) castSingleRayKernel<FLAT, MOTION, SWEEP><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, outDev, c->dStackOvf.p); \
-    else                rayTraceKernel<FLAT, MOTION, SWEEP><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, outDev, c->dStackOvf.p); } while (0)
-  if (c->S.sweep)                         HPT_RT_LAUNCH(false, false, true);
-  else if (c->S.flatMode && c->anyMotion) HPT_RT_LAUNCH(true, true, false);
-  else if (c->S.flatMode)                 HPT_RT_LAUNCH(true, false, false);
-  else if (c->anyMotion)                  HPT_RT_LAUNCH(false, true, false);
-  else                                    HPT_RT_LAUNCH(false, false, false);
-#undef HPT_RT_LAUNCH
+  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+    if (channels == 0u) castSingleRayKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, outDev, c->dStackOvf.p);
+    else                rayTraceKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, outDev, c->dStackOvf.p);
+  });
   HIPCHK(c, hipGetLastError());
   HIPCHK(c, hipEventRecord(c->ev1, st));
   return HPT_OK;
 }
 // Host-pointer form of either pass: the caller's frame goes up (RayTraceBlock adds to it; CastSingleRayBlock leaves the pixels past tid as
-// they are) and comes back; the four GetExecutionTime slots are kernel, copy in, copy out, overhead, as path_trace_host fills them.
+// they are) and comes back
 static int rt_host(hpt_ctx* c, uint32_t tid, uint32_t channels, float* out, float slots[4])
 {
   (void)hipSetDevice(c->device);
-  const size_t n = (size_t)c->packedCount * (channels == 0u ? 4u : channels);
-  DevBuf<float> d;
-  const double t0 = now_ms();
-  HIPCHK(c, d.upload(out, n));
-  const double t1 = now_ms();
-  int rc = rt_launch(c, tid, channels, d.p, nullptr);
-  if (rc == HPT_OK) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = c->hipFail(e, "hipDeviceSynchronize"); }
-  const double t2 = now_ms();
-  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
-  const double t3 = now_ms();
-  if (rc == HPT_OK) {
-    float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
-    c->lastKernelMs = kms;
-    slots[0] = kms; slots[1] = float(t1 - t0); slots[2] = float(t3 - t2); slots[3] = float((t2 - t1) - kms);
-  }
-  d.release();
-  return rc;
+  return roundTrip(c, slots, out, (size_t)c->packedCount * (channels == 0u ? 4u : channels), true,
+                   [&](float* d) { return rt_launch(c, tid, channels, d, nullptr); });
 }
 
 // Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254, integrator_pt_host.cpp:29-36): a_passNum is unused there and here
@@ -2225,7 +2211,7 @@ extern "C" int hpt_cast_single_ray_block_dev(hpt_ctx* c, uint32_t tid, float* ou
 try {
   if (!c) return HPT_ERR_ARG;
   (void)passNum;
-  if (int rc = rt_check(c, "CastSingleRayBlock", outDev, tid)) return rc;
+  if (int rc = pixelPassCheck(c, "CastSingleRayBlock", "out_color", outDev, "tid", tid)) return rc;
   if (tid == 0u) return HPT_OK;
   return rt_launch(c, tid, 0u, outDev, (hipStream_t)stream);
 }
@@ -2234,7 +2220,7 @@ extern "C" int hpt_cast_single_ray_block(hpt_ctx* c, uint32_t tid, float* out, u
 try {
   if (!c) return HPT_ERR_ARG;
   (void)passNum;
-  if (int rc = rt_check(c, "CastSingleRayBlock", out, tid)) return rc;
+  if (int rc = pixelPassCheck(c, "CastSingleRayBlock", "out_color", out, "tid", tid)) return rc;
   if (tid == 0u) return HPT_OK;
   return rt_host(c, tid, 0u, out, c->tCastSingleRay);
 }
@@ -2245,7 +2231,7 @@ extern "C" int hpt_ray_trace_block_dev(hpt_ctx* c, uint32_t tid, uint32_t channe
 try {
   if (!c) return HPT_ERR_ARG;
   (void)passNum;
-  if (int rc = rt_check(c, "RayTraceBlock", outDev, tid)) return rc;
+  if (int rc = pixelPassCheck(c, "RayTraceBlock", "out_color", outDev, "tid", tid)) return rc;
   if (int rc = rt_check_channels(c, channels)) return rc;
   if (tid == 0u || channels > 4u) return HPT_OK;
   return rt_launch(c, tid, channels, outDev, (hipStream_t)stream);
@@ -2255,7 +2241,7 @@ extern "C" int hpt_ray_trace_block(hpt_ctx* c, uint32_t tid, uint32_t channels, 
 try {
   if (!c) return HPT_ERR_ARG;
   (void)passNum;
-  if (int rc = rt_check(c, "RayTraceBlock", out, tid)) return rc;
+  if (int rc = pixelPassCheck(c, "RayTraceBlock", "out_color", out, "tid", tid)) return rc;
   if (int rc = rt_check_channels(c, channels)) return rc;
   if (tid == 0u || channels > 4u) return HPT_OK;
   return rt_host(c, tid, channels, out, c->tRayTrace);
@@ -2354,23 +2340,8 @@ try {
   if (int rc = qmc_check(c, channels, out, nullptr, nullptr)) return rc;
   (void)hipSetDevice(c->device);
   if (hpt_qmc_sample_count(pixelsNum, passNum) == 0u) return HPT_OK;
-  const size_t n = (size_t)c->packedCount * channels;
-  DevBuf<float> d;
-  const double t0 = now_ms();
-  HIPCHK(c, d.upload(out, n));
-  const double t1 = now_ms();
-  int rc = hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, d.p, passNum, nullptr, nullptr, nullptr);
-  if (rc == HPT_OK) { hipError_t e = hipDeviceSynchronize(); if (e != hipSuccess) rc = c->hipFail(e, "hipDeviceSynchronize"); }
-  const double t2 = now_ms();
-  if (rc == HPT_OK) { hipError_t e = hipMemcpy(out, d.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
-  const double t3 = now_ms();
-  if (rc == HPT_OK) {
-    float kms = 0.0f; (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
-    c->lastKernelMs = kms;
-    c->tPathTraceQmc[0] = kms; c->tPathTraceQmc[1] = float(t1 - t0); c->tPathTraceQmc[2] = float(t3 - t2); c->tPathTraceQmc[3] = float((t2 - t1) - kms);
-  }
-  d.release();
-  return rc;
+  return roundTrip(c, c->tPathTraceQmc, out, (size_t)c->packedCount * channels, true,
+                   [&](float* d) { return hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, d, passNum, nullptr, nullptr, nullptr); });
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block"); }
 
@@ -2429,29 +2400,26 @@ try {
   (void)hipSetDevice(c->device);
   if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceDR before UpdateMembersPlainData");
   const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
-  const double t0 = now_ms();
-  HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, c->dRef.alloc(n)); HIPCHK(c, c->dData.alloc(gradSize)); HIPCHK(c, c->dGrad.alloc(gradSize)); HIPCHK(c, c->dLoss.alloc(1));
-  HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->dRef.p, refImg, n * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemcpy(c->dData.p, data, gradSize * 4, hipMemcpyHostToDevice));
-  HIPCHK(c, hipMemset(c->dGrad.p, 0, gradSize * 4));                       // memset(a_dataGrad, 0, ...) (integrator_dr.cpp:1139)
-  HIPCHK(c, hipMemset(c->dLoss.p, 0, 4));
-  const double t1 = now_ms();
-  int rc = hpt_path_trace_dr_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, c->dRef.p, c->dData.p, c->dGrad.p, gradSize, c->dLoss.p, nullptr);
-  if (rc) return rc;
-  HIPCHK(c, hipDeviceSynchronize());
-  const double t2 = now_ms();
   float lossSum = 0.0f;
-  HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(dataGrad, c->dGrad.p, gradSize * 4, hipMemcpyDeviceToHost));
-  HIPCHK(c, hipMemcpy(&lossSum, c->dLoss.p, 4, hipMemcpyDeviceToHost));
-  const double t3 = now_ms();
-  if (outLoss) *outLoss = lossSum / float(c->S.winWidth * c->S.winHeight);  // avgLoss /= W*H (integrator_dr.cpp:1206)
-  float kms = 0.0f;
-  if (tidCount && passNum) (void)hipEventElapsedTime(&kms, c->ev0, c->ev1);
-  c->lastKernelMs = kms;
-  c->tDR[0] = kms; c->tDR[1] = float(t1 - t0); c->tDR[2] = float(t3 - t2); c->tDR[3] = float((t2 - t1) - kms);
-  return HPT_OK;
+  const int rc = roundTrip(c, c->tDR, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+    [&]() -> int {
+      HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, c->dRef.alloc(n)); HIPCHK(c, c->dData.alloc(gradSize)); HIPCHK(c, c->dGrad.alloc(gradSize)); HIPCHK(c, c->dLoss.alloc(1));
+      HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->dRef.p, refImg, n * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->dData.p, data, gradSize * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemset(c->dGrad.p, 0, gradSize * 4));                   // memset(a_dataGrad, 0, ...) (integrator_dr.cpp:1139)
+      HIPCHK(c, hipMemset(c->dLoss.p, 0, 4));
+      return HPT_OK;
+    },
+    [&]() -> int { return hpt_path_trace_dr_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, c->dRef.p, c->dData.p, c->dGrad.p, gradSize, c->dLoss.p, nullptr); },
+    [&]() -> int {
+      HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(dataGrad, c->dGrad.p, gradSize * 4, hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(&lossSum, c->dLoss.p, 4, hipMemcpyDeviceToHost));
+      return HPT_OK;
+    });
+  if (rc == HPT_OK && outLoss) *outLoss = lossSum / float(c->S.winWidth * c->S.winHeight);   // avgLoss /= W*H (integrator_dr.cpp:1206)
+  return rc;
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_dr"); }
 
@@ -2486,11 +2454,10 @@ try {
   const size_t n = (size_t)w * h * 4;
   if (n == 0) return HPT_OK;
   DevBuf<float> dd, dg;
-  HIPCHK(c, dd.upload(data, n)); HIPCHK(c, dg.upload(grad, n));
-  int rc = hpt_image2d4f_regularizer_dev(c, w, h, dd.p, dg.p, nullptr);
-  if (rc == HPT_OK) { hipError_t e = hipMemcpy(grad, dg.p, n * sizeof(float), hipMemcpyDeviceToHost); if (e != hipSuccess) rc = c->hipFail(e, "hipMemcpy"); }
-  dd.release(); dg.release();
-  return rc;
+  return roundTrip(c, nullptr, KERNEL_UNTIMED,
+                   [&]() -> int { HIPCHK(c, dd.upload(data, n)); HIPCHK(c, dg.upload(grad, n)); return HPT_OK; },
+                   [&]() -> int { return hpt_image2d4f_regularizer_dev(c, w, h, dd.p, dg.p, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(grad, dg.p, n * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
 }
 catch (...) { return hptGuard(c, "hpt_image2d4f_regularizer"); }
 

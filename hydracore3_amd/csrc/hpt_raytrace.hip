@@ -16,41 +16,9 @@
 //     on the device and in its CPU checker alike, is used (hpt_device.h: reflect): i - 2 * dot(n, i) * n.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
+#include "hpt_primary.h"
 
 namespace hpt {
-
-// kernel_InitEyeRay / kernel_InitEyeRay3 (integrator_rt.cpp:33-82): the pixel centre, the integer add first (not cameraRay's order,
-// hpt_shade.h), always a pinhole
-HPT_DEV void rtEyeRay(const DevScene& S, uint XY, uint& x, uint& y, V3& rayPos, V3& rayDir)
-{
-  x = XY & 0x0000FFFFu; y = (XY & 0xFFFF0000u) >> 16;
-  const float xn = (float(x + (uint)S.winStartX) + 0.5f) / float(S.fbWidth);
-  const float yn = (float(y + (uint)S.winStartY) + 0.5f) / float(S.fbHeight);
-  V4 pos = v4(2.0f * xn - 1.0f, 2.0f * yn - 1.0f, 0.0f, 1.0f);                   // EyeRayDirNormalized (cglobals.h:49-55)
-  pos = mul4x4(S.projInv, pos);
-  const V3 dir = normalize(v3(pos.x / pos.w, pos.y / pos.w, pos.z / pos.w));
-  const V3 p1 = mul4x3(S.worldViewInv, v3(0, 0, 0));                             // transform_ray3f (cglobals.h:254-263)
-  const V3 p2 = mul4x3(S.worldViewInv, v3(0, 0, 0) + 100.0f * dir);
-  rayPos = p1; rayDir = normalize(p2 - p1);
-}
-
-// The vertex gather of kernel_GetRayColor (integrator_rt.cpp:128-145) and kernel_RayTrace2 (integrator_pt.cpp:263-272), as shadeVertex and
-// gbufferKernel do it: the interpolated object-space normal, the texture coordinate and the primitive's material id before any remap
-HPT_DEV void rtGather(const DevScene& S, const HitRec& h, V3& nrmO, V2& uv, uint& matIdOriginal)
-{
-  const uint geomId = S.insts[h.inst].geomId;
-  const uint triOffset = S.matVertOffset[2 * geomId + 0], vertOffset = S.matVertOffset[2 * geomId + 1];
-  const float uvx = h.v, uvy = h.u;                                      // coords[0] = v, coords[1] = u (EmbreeRT.cpp:350-352)
-  const uint A = S.triIndices[(triOffset + h.prim) * 3 + 0];
-  const uint B = S.triIndices[(triOffset + h.prim) * 3 + 1];
-  const uint C = S.triIndices[(triOffset + h.prim) * 3 + 2];
-  const float4 nA = ((const float4*)S.vData8f)[2 * (A + vertOffset)], nB = ((const float4*)S.vData8f)[2 * (B + vertOffset)], nC = ((const float4*)S.vData8f)[2 * (C + vertOffset)];
-  const float tyA = S.vData8f[8 * (A + vertOffset) + 7], tyB = S.vData8f[8 * (B + vertOffset) + 7], tyC = S.vData8f[8 * (C + vertOffset) + 7];
-  const float wA = 1.0f - uvx - uvy;
-  nrmO = v3(wA * nA.x + uvy * nB.x + uvx * nC.x, wA * nA.y + uvy * nB.y + uvx * nC.y, wA * nA.z + uvy * nB.z + uvx * nC.z);
-  uv = v2(wA * nA.w + uvy * nB.w + uvx * nC.w, wA * tyA + uvy * tyB + uvx * tyC);
-  matIdOriginal = S.matIdByPrimId[triOffset + h.prim];
-}
 
 // colors[GLTF_COLOR_BASE].xyz * texture(texid[0]) at the material's transformed coordinate: kernel_GetRayColor, MaterialEvalWhitted and the
 // light branch of kernel_RayBounce all read it (integrator_rt.cpp:147-151, 166-169, 225-229)
@@ -69,13 +37,13 @@ __global__ void __launch_bounds__(256) castSingleRayKernel(const DevScene S, con
   TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = stackOverflow + g; stk.ovfStride = gridDim.x * 256u;
   if (g >= tidCount) return;
   uint x, y; V3 rayPos, rayDir;
-  rtEyeRay(S, packedXY[g], x, y, rayPos, rayDir);
+  pinholeEyeRay(S, packedXY[g], 0.5f, 0.5f, x, y, rayPos, rayDir);      // kernel_InitEyeRay: the pixel centre
   HitRec h; TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
   const bool found = traceAny<false, false, true, FLAT, MOTION, SWEEP>(S, rayPos, rayDir, 0.0f, HPT_FLT_MAX, h, stk, st, 0.0f);
   V3 color = v3(0.0f, 0.0f, 0.0f);                                       // a miss: 0 to the four floats of its own pixel (decision 1 above)
   if (found) {
     V3 nrmO; V2 uv; uint matId;
-    rtGather(S, h, nrmO, uv, matId);                                     // no remap list: m_matIdByPrimId straight (the upload checks the id under this mask)
+    gatherHitVertex(S, h, nrmO, uv, matId);                              // no remap list: m_matIdByPrimId straight (the upload checks the id under this mask)
     const MaterialRec& m = S.materials[matId & 0x00FFFFFFu];
     const float w = m.colors[GLTF_COLOR_BASE][3];
     color = (w > 0.0f) ? v3s(clampf(w, 0.0f, 1.0f)) : rtBaseTimesTex(S, m, uv);
@@ -97,7 +65,7 @@ __global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const ui
   TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = stackOverflow + g; stk.ovfStride = gridDim.x * 256u;
   if (g >= tidCount) return;
   uint x, y; V3 rpos, rdir;
-  rtEyeRay(S, packedXY[g], x, y, rpos, rdir);
+  pinholeEyeRay(S, packedXY[g], 0.5f, 0.5f, x, y, rpos, rdir);          // kernel_InitEyeRay3: the pixel centre
   V3 accum = v3(0.0f, 0.0f, 0.0f), thr = v3(1.0f, 1.0f, 1.0f);
   TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
   const float time = 0.0f;                                               // RayTrace passes time 0 to kernel_RayTrace2 (integrator_rt.cpp:444)
@@ -108,16 +76,10 @@ __global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const ui
     const uint instId = h.inst;
     const V3 hitPos = rpos + h.t * (1.f - 1e-6f) * rdir;
     V3 nrmO; V2 uv; uint midOriginal;
-    rtGather(S, h, nrmO, uv, midOriginal);
-    const float* nm = S.normMat + 12 * instId;
-    V3 hitNorm = v3(nm[0] * nrmO.x + nm[1] * nrmO.y + nm[2] * nrmO.z,
-                    nm[4] * nrmO.x + nm[5] * nrmO.y + nm[6] * nrmO.z,
-                    nm[8] * nrmO.x + nm[9] * nrmO.y + nm[10] * nrmO.z);
+    gatherHitVertex(S, h, nrmO, uv, midOriginal);
+    V3 hitNorm = mulNormMat(S.normMat + 12 * instId, nrmO);
     if (MOTION && (S.motion & 2u) == 0u) {                               // integrator_pt.cpp:285-292 as shadeVertex has it: lerp(hitNorm, hitNorm2, time) written out, time = 0
-      const float* nm2 = S.normMat2 + 12 * instId;
-      const V3 n2 = v3(nm2[0] * hitNorm.x + nm2[1] * hitNorm.y + nm2[2] * hitNorm.z,
-                       nm2[4] * hitNorm.x + nm2[5] * hitNorm.y + nm2[6] * hitNorm.z,
-                       nm2[8] * hitNorm.x + nm2[9] * hitNorm.y + nm2[10] * hitNorm.z);
+      const V3 n2 = mulNormMat(S.normMat2 + 12 * instId, hitNorm);
       hitNorm = hitNorm + time * (n2 - hitNorm);
     }
     hitNorm = normalize(hitNorm);
@@ -167,7 +129,7 @@ __global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const ui
 #define HPT_RT_INST(FLAT, MOTION, SWEEP) \
   template __global__ void castSingleRayKernel<FLAT, MOTION, SWEEP>(const DevScene, const uint*, uint, float*, uint*); \
   template __global__ void rayTraceKernel<FLAT, MOTION, SWEEP>(const DevScene, const uint*, uint, uint, float*, uint*);
-HPT_RT_INST(false, false, true)     // the traversal variants ray_query() dispatches (hpt_host.hip): sweep, single-level with motion, single-level,
+HPT_RT_INST(false, false, true)     // the traversal variants traversalDispatch() picks (hpt_host.hip): sweep, single-level with motion, single-level,
 HPT_RT_INST(true, true, false)      // two-level with motion, two-level
 HPT_RT_INST(true, false, false)
 HPT_RT_INST(false, true, false)

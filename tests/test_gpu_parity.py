@@ -820,6 +820,64 @@ def test_execution_time_slots_and_launch_knobs(cornell):
         assert np.array_equal(g2.render(4), ref), bpc
 
 
+def test_host_entry_points_fill_only_their_own_time_slots():
+    """Every host-pointer entry point fills its own GetExecutionTime slot ([0] kernel ms > 0, [1] copy in and [2] copy out >= 0) and
+    hpt_last_kernel_ms with the same kernel time, and leaves the slots of the other names as they were. EvalGBuffer has no slot and sets
+    hpt_last_kernel_ms only; Image2D4fRegularizer sets neither. PathTraceBlock with a_passNum = 0 still makes its copies and writes its
+    slot with a kernel time of exactly 0; CastSingleRayBlock with tid = 0 returns before any copy and leaves its slot alone."""
+    from hydracore3_amd.api import HipIntegrator
+    sc = load_hydra_xml(scene_path("test_035"), 64, 64)
+    gpu = HipIntegrator(sc)
+    names = ["PathTraceBlock", "NaivePathTraceBlock", "PathTraceFromInputRaysBlock", "PathTraceDR", "PathTraceBlockQMC", "CastSingleRayBlock", "RayTraceBlock"]
+
+    def slots():
+        return {n: gpu.GetExecutionTime(n) for n in names}
+
+    def frame(channels=4):
+        return np.zeros((sc.height, sc.width, channels), np.float32)
+
+    n = 256
+    rng = np.random.default_rng(5)
+    pos = np.zeros((n, 4), np.float32); dr = np.zeros((n, 4), np.float32)
+    d = np.stack([rng.uniform(-0.35, 0.35, n), rng.uniform(-0.35, 0.35, n), -np.ones(n)], 1)
+    dr[:, :3] = d / np.linalg.norm(d, axis=1, keepdims=True)
+    _, size = gpu.PutDiffTex2D(1, 256, 256, 4)
+    data = np.full(size, 0.5, np.float32)
+    calls = {
+        "PathTraceBlock": lambda: gpu.PathTraceBlock(gpu.N, 4, frame(), 1),
+        "NaivePathTraceBlock": lambda: gpu.NaivePathTraceBlock(gpu.N, 4, frame(), 1),
+        "PathTraceFromInputRaysBlock": lambda: gpu.PathTraceFromInputRaysBlock(n, 4, pos, dr, np.zeros((n, 4), np.float32), 1),
+        "PathTraceDR": lambda: gpu.PathTraceDR(gpu.N, 4, frame(), 1, frame(), data, np.zeros_like(data)),
+        "PathTraceBlockQMC": lambda: gpu.PathTraceBlockQMC(gpu.N, 4, frame(), 1),
+        "CastSingleRayBlock": lambda: gpu.CastSingleRayBlock(gpu.N, frame()),
+        "RayTraceBlock": lambda: gpu.RayTraceBlock(gpu.N, 4, frame()),
+    }
+    assert list(calls) == names
+    for name in names:
+        before = slots()
+        calls[name]()
+        after = slots()
+        t = after.pop(name); before.pop(name)
+        print(name, t, gpu.last_kernel_ms())
+        assert t[0] > 0.0 and t[1] >= 0.0 and t[2] >= 0.0, (name, t)
+        assert gpu.last_kernel_ms() == t[0], name
+        assert after == before, name
+
+    before = slots()
+    gpu.EvalGBuffer()
+    assert gpu.last_kernel_ms() > 0.0 and slots() == before
+    before, ms = slots(), gpu.last_kernel_ms()
+    tex = rng.uniform(0.0, 1.0, (8, 8, 4)).astype(np.float32)
+    gpu.Image2D4fRegularizer(tex, np.zeros_like(tex))
+    assert slots() == before and gpu.last_kernel_ms() == ms
+
+    gpu.PathTraceBlock(gpu.N, 4, frame(), 0)                             # returns 0 (no exception); copies made, nothing launched
+    assert gpu.GetExecutionTime("PathTraceBlock")[0] == 0.0
+    before = slots()
+    gpu.CastSingleRayBlock(0, frame())
+    assert slots() == before
+
+
 def test_blend_materials_match_oracle():
     """MAT_TYPE_BLEND (integrator_pt_mat.cpp:23-77): one extra generator step per blend layer before the material's float4, the leaf
     sampler then overwrites val / pdf as in the reference; MaterialEval walks the tree with the 4-deep stack. Plain, texture-masked,
