@@ -98,6 +98,18 @@ ABI = {
     "hpt_qmc_sample_count": (_u32, [_u32, _u32]),
     "hpt_path_trace_qmc_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
     "hpt_path_trace_qmc_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "hpt_cam_create": (_i, [_vp, _i, C.POINTER(_vp)]),
+    "hpt_cam_destroy": (None, [_vp]),
+    "hpt_cam_set_parameters": (_i, [_vp, _u32, _u32, _vp, _i]),
+    "hpt_cam_set_lens": (_i, [_vp, _vp, _u32, _f, _f]),
+    "hpt_cam_set_batch_size": (_i, [_vp, _u32]),
+    "hpt_cam_make_rays_block": (_i, [_vp, _vp, _vp, _u32, _i]),
+    "hpt_cam_make_rays_block_dev": (_i, [_vp, _vp, _vp, _u32, _i, _vp]),
+    "hpt_cam_add_samples_contribution_block": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _i]),
+    "hpt_cam_add_samples_contribution_block_dev": (_i, [_vp, _vp, _vp, _u32, _u32, _u32, _i, _vp]),
+    "hpt_cam_read_state": (_i, [_vp, _vp, _vp, _vp, _u32]),
+    "hpt_cam_render_dev": (_i, [_vp, _vp, _vp, _u32, _vp]),
+    "hpt_cam_get_execution_time": (_i, [_vp, C.c_char_p, C.POINTER(_f)]),
 }
 
 # hpt_gbuffer_pixel = Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords
@@ -529,3 +541,90 @@ class HipIntegrator:
         name = C.create_string_buffer(128)
         self._chk(self.L.hpt_device_info(self.h, C.byref(cu), C.byref(wf), name, 128))
         return {"cus": cu.value, "wavefront": wf.value, "arch": name.value.decode()}
+
+
+CAM_PINHOLE, CAM_TABLE_LENS = 0, 1
+
+
+class CamRays:
+    """ICamRaysAPI2-shaped front end (cam_plugin/CamPluginAPI.h:39-77) of the device cameras: CamPinHole (kind 0) and CamTableLens (kind 1)
+    of the reference, with the reference's method names, plus render_dev (the loop of cam_plugin/main_with_cam_gpu.cpp). A camera belongs to
+    the integrator it was made from and keeps it alive."""
+
+    def __init__(self, integ: HipIntegrator, kind: int = CAM_PINHOLE):
+        self.integ, self.L, self.kind = integ, integ.L, int(kind)
+        self.width = self.height = self.batch = 0
+        self.spectral = 0
+        h = _vp()
+        integ._chk(self.L.hpt_cam_create(integ.h, self.kind, C.byref(h)))
+        self.h = h
+
+    def __del__(self):
+        try:
+            if getattr(self, "h", None) and getattr(self.integ, "h", None):
+                self.L.hpt_cam_destroy(self.h)
+            self.h = None
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        self.integ._chk(rc)
+
+    def SetParameters(self, a_width, a_height, projInv, spectralMode=0):
+        """SetParameters(a_width, a_height, a_params): projInv = inverse4x4(perspectiveMatrix(fov, aspect, near, far)), 16 floats column-major
+        (Params.projInv of the scene's camera is one); spectralMode = CamParameters::spectralMode."""
+        m = np.ascontiguousarray(list(projInv) if not isinstance(projInv, np.ndarray) else projInv, np.float32).reshape(16)
+        self._chk(self.L.hpt_cam_set_parameters(self.h, a_width, a_height, m.ctypes.data, int(spectralMode)))
+        self.width, self.height, self.spectral = int(a_width), int(a_height), int(bool(spectralMode))
+
+    def SetLens(self, lines, phys_size):
+        """The lens table and m_physSize of CamTableLens::Init: lines float32 [n, 4] = {curvatureRadius, thickness, eta, apertureRadius}, film side first."""
+        lines = np.ascontiguousarray(lines, np.float32).reshape(-1, 4)
+        self._chk(self.L.hpt_cam_set_lens(self.h, lines.ctypes.data if lines.size else None, lines.shape[0], float(phys_size[0]), float(phys_size[1])))
+
+    def SetBatchSize(self, a_tileSize):
+        self._chk(self.L.hpt_cam_set_batch_size(self.h, a_tileSize))
+        self.batch = int(a_tileSize)
+
+    def MakeRaysBlock(self, out_rayPosAndNear4f, out_rayDirAndFar4f, in_blockSize, subPassId):
+        """float32 [in_blockSize, 4] arrays (RayPosAndW / RayDirAndT), camera space."""
+        for a in (out_rayPosAndNear4f, out_rayDirAndFar4f):
+            assert a.dtype == np.float32 and a.flags["C_CONTIGUOUS"] and a.size >= 4 * in_blockSize
+        self._chk(self.L.hpt_cam_make_rays_block(self.h, out_rayPosAndNear4f.ctypes.data, out_rayDirAndFar4f.ctypes.data, in_blockSize, subPassId))
+
+    def AddSamplesContributionBlock(self, out_color4f, colors4f, in_blockSize, a_width, a_height, subPassId):
+        """out_color4f float32 [a_height, a_width, 4] (rgb added to); colors4f float32 [in_blockSize, 4], or [in_blockSize] in spectral mode."""
+        assert out_color4f.dtype == np.float32 and out_color4f.flags["C_CONTIGUOUS"] and out_color4f.size == a_width * a_height * 4
+        assert colors4f.dtype == np.float32 and colors4f.flags["C_CONTIGUOUS"] and colors4f.size >= in_blockSize * (1 if self.spectral else 4)
+        self._chk(self.L.hpt_cam_add_samples_contribution_block(self.h, out_color4f.ctypes.data, colors4f.ctypes.data, in_blockSize, a_width, a_height, subPassId))
+
+    def make_rays_block_dev(self, pos_ptr, dir_ptr, n, sub_pass_id, stream=None):
+        self._chk(self.L.hpt_cam_make_rays_block_dev(self.h, pos_ptr, dir_ptr, n, sub_pass_id, stream))
+
+    def add_samples_contribution_block_dev(self, frame_ptr, colors_ptr, n, sub_pass_id, stream=None):
+        self._chk(self.L.hpt_cam_add_samples_contribution_block_dev(self.h, frame_ptr, colors_ptr, n, self.width, self.height, sub_pass_id, stream))
+
+    def read_state(self, n=None):
+        """Host copies of the first n slots of (m_randomGens uint32 [n, 2], m_storedWaves [n], m_storedCos4 [n])."""
+        n = self.batch if n is None else int(n)
+        gens, waves, cos4 = np.zeros((n, 2), np.uint32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self._chk(self.L.hpt_cam_read_state(self.h, gens.ctypes.data, waves.ctypes.data, cos4.ctypes.data, n))
+        return gens, waves, cos4
+
+    def render_dev(self, frame_ptr, passes, stream=None):
+        """The device-resident loop: `passes` times over the tiles of the frame, into the width * height * 4 floats at frame_ptr (added to)."""
+        self._chk(self.L.hpt_cam_render_dev(self.integ.h, self.h, frame_ptr, passes, stream))
+
+    def render(self, passes):
+        """render_dev into a zeroed frame; returns float32 [height, width, 4]."""
+        frame = self.integ.dev_array(np.zeros((self.height, self.width, 4), np.float32))
+        try:
+            self.render_dev(frame.ptr, passes)
+            return frame.download()
+        finally:
+            frame.free()
+
+    def GetExecutionTime(self, name):
+        out = (C.c_float * 4)(0, 0, 0, 0)
+        self._chk(self.L.hpt_cam_get_execution_time(self.h, name.encode(), out))
+        return list(out)

@@ -215,6 +215,29 @@ struct QmcJob
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q);
 
+// ---- camera plug-in: CamPinHole / CamTableLens (cam_plugin/CamPinHole.cpp, CamTableLens.cpp; hpt_camrays.hip) -----------------------------
+// One lane per ray of a tile: lane tid serves pixel p = firstPixel + tid (x = p % width, y = p / width: the reference's pitch-linear split) and
+// owns slot tid of the three per-lane arrays. The scalars and the lens lines are the same for every lane (scalar loads).
+struct CamJob
+{
+  uint   n, firstPixel, width, height;   // rays of this tile; subPassId * batchSize
+  float  projInv[16];                    // m_projInv, column-major
+  float  physSize[2];                    // m_physSize
+  uint   lensCount, numCie;
+  const float4* lensLines;               // {curvatureRadius, thickness, eta, apertureRadius}, film side first
+  const float4* cie;                     // m_cie_xyz
+  Rng*   gens;                           // m_randomGens
+  float* waves;                          // m_storedWaves
+  float* cos4;                           // m_storedCos4
+  float4* rayPos; float4* rayDir;        // MakeRaysBlock: RayPosAndW / RayDirAndT [n]
+  const float* colors;                   // AddSamplesContributionBlock: 4 floats per ray, 1 in spectral mode
+  float4* frame;                         // ... and the width * height frame
+};
+enum : int { CAM_PINHOLE = 0, CAM_TABLE_LENS = 1 };
+template <int KIND, bool SPECTRAL> __global__ void __launch_bounds__(256) camMakeRaysKernel(const CamJob job);
+template <int KIND, bool SPECTRAL> __global__ void __launch_bounds__(256) camContribKernel(const CamJob job);
+__global__ void __launch_bounds__(256) camInitGensKernel(Rng* gens, uint n);   // RandomGenInit(i + 12345 * i), 32-bit wrap-around
+
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);
 

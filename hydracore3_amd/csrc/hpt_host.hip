@@ -4,6 +4,7 @@
 #include "film_precompute.h"
 #include "jpeg_decode.h"
 #include "qmc_table.h"
+#include "cie_fit.h"
 #include <hip/hip_runtime.h>
 #include <cstdio>
 #include <cstdlib>
@@ -2247,6 +2248,313 @@ try {
   return rt_host(c, tid, channels, out, c->tRayTrace);
 }
 catch (...) { return hptGuard(c, "hpt_ray_trace_block"); }
+
+// ---- camera plug-in: CamPinHole / CamTableLens (cam_plugin/CamPluginAPI.h:39-77; hpt_camrays.hip) ---------------------------------------------
+// The camera's state lives on the context's device; its failures go to the context's error text.
+static const uint32_t CAM_TIMED_TILES = 256;                  // tiles of a hpt_cam_render_dev loop that get per-stage events
+struct hpt_cam
+{
+  hpt_ctx* ctx = nullptr; int kind = 0;
+  bool paramsSet = false; uint width = 0, height = 0; int spectral = 0; float projInv[16] = {0};
+  uint batch = 0, lensCount = 0; float physSize[2] = {0, 0};
+  DevBuf<Rng> dGens; DevBuf<float> dWaves, dCos4, dColors; DevBuf<float4> dLines, dRayPos, dRayDir, dCie;   // per-lane arrays, lens lines, tile buffers, own m_cie_xyz
+  float tMake[4] = {0, 0, 0, 0}, tContrib[4] = {0, 0, 0, 0}, tTrace[4] = {0, 0, 0, 0}, tRender[4] = {0, 0, 0, 0};
+  std::vector<hipEvent_t> ev;                                 // 4 per timed tile of the last render loop, then its first and last event
+  uint32_t evTiles = 0; bool renderPending = false;
+  ~hpt_cam() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+};
+
+// what a tile call needs: both set-up calls made, the tile inside the batch and inside the frame
+static int camTileCheck(hpt_cam* cam, const char* what, uint32_t n, int subPassId)
+{
+  hpt_ctx* c = cam->ctx;
+  const std::string w(what);
+  if (!cam->paramsSet) return c->fail(HPT_ERR_ARG, w + " before SetParameters");
+  if (cam->batch == 0u) return c->fail(HPT_ERR_ARG, w + " before SetBatchSize");
+  if (subPassId < 0) return c->fail(HPT_ERR_ARG, w + ": negative subPassId");
+  if (n > cam->batch) return c->fail(HPT_ERR_ARG, w + ": in_blockSize exceeds the batch size");
+  if ((uint64_t)subPassId * cam->batch + n > (uint64_t)cam->width * cam->height) return c->fail(HPT_ERR_ARG, w + ": the tile reaches past width * height");
+  return HPT_OK;
+}
+static void camFillJob(const hpt_cam* cam, CamJob& job, uint32_t n, int subPassId)
+{
+  std::memset(&job, 0, sizeof(job));
+  job.n = n; job.firstPixel = (uint)subPassId * cam->batch; job.width = cam->width; job.height = cam->height;
+  std::memcpy(job.projInv, cam->projInv, sizeof(job.projInv));
+  job.physSize[0] = cam->physSize[0]; job.physSize[1] = cam->physSize[1];
+  job.lensCount = cam->lensCount; job.lensLines = cam->dLines.p;
+  job.gens = cam->dGens.p; job.waves = cam->dWaves.p; job.cos4 = cam->dCos4.p;
+}
+// m_cie_xyz of the camera: the table the context uploaded with a spectral scene, else an own copy of the loaders' table
+static int camEnsureCie(hpt_cam* cam)
+{
+  hpt_ctx* c = cam->ctx;
+  if ((c->S.cieXYZ && c->S.numCieXYZ) || cam->dCie.p) return HPT_OK;
+  const std::vector<float> t = hydra_hip::cieXyzFit();
+  std::vector<float4> cie(t.size() / 4);
+  for (size_t i = 0; i < cie.size(); i++) cie[i] = make_float4(t[4 * i], t[4 * i + 1], t[4 * i + 2], t[4 * i + 3]);
+  HIPCHK(c, cam->dCie.upload(cie.data(), cie.size()));
+  return HPT_OK;
+}
+// the two launches; e0 / e1 (may be null) are recorded around the kernel
+static int camLaunchMake(hpt_cam* cam, float4* pos, float4* dir, uint32_t n, int subPassId, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+  hpt_ctx* c = cam->ctx;
+  if (cam->kind == CAM_TABLE_LENS && cam->lensCount == 0u) return c->fail(HPT_ERR_ARG, "MakeRaysBlock: the table-lens camera has no lens lines (hpt_cam_set_lens)");
+  CamJob job; camFillJob(cam, job, n, subPassId);
+  job.rayPos = pos; job.rayDir = dir;
+  const dim3 g((n + 255u) / 256u), b(256);
+  if (e0) HIPCHK(c, hipEventRecord(e0, st));
+  if (cam->kind == CAM_PINHOLE) { if (cam->spectral) camMakeRaysKernel<CAM_PINHOLE, true><<<g, b, 0, st>>>(job); else camMakeRaysKernel<CAM_PINHOLE, false><<<g, b, 0, st>>>(job); }
+  else                          { if (cam->spectral) camMakeRaysKernel<CAM_TABLE_LENS, true><<<g, b, 0, st>>>(job); else camMakeRaysKernel<CAM_TABLE_LENS, false><<<g, b, 0, st>>>(job); }
+  HIPCHK(c, hipGetLastError());
+  if (e1) HIPCHK(c, hipEventRecord(e1, st));
+  return HPT_OK;
+}
+static int camLaunchContrib(hpt_cam* cam, float4* frame, const float* colors, uint32_t n, int subPassId, hipStream_t st, hipEvent_t e0, hipEvent_t e1)
+{
+  hpt_ctx* c = cam->ctx;
+  CamJob job; camFillJob(cam, job, n, subPassId);
+  job.frame = frame; job.colors = colors;
+  if (cam->spectral) {
+    if (int rc = camEnsureCie(cam)) return rc;
+    const bool own = !(c->S.cieXYZ && c->S.numCieXYZ);
+    job.cie = own ? cam->dCie.p : c->S.cieXYZ; job.numCie = own ? (uint)cam->dCie.n : c->S.numCieXYZ;
+  }
+  const dim3 g((n + 255u) / 256u), b(256);
+  if (e0) HIPCHK(c, hipEventRecord(e0, st));
+  if (cam->kind == CAM_PINHOLE) { if (cam->spectral) camContribKernel<CAM_PINHOLE, true><<<g, b, 0, st>>>(job); else camContribKernel<CAM_PINHOLE, false><<<g, b, 0, st>>>(job); }
+  else                          { if (cam->spectral) camContribKernel<CAM_TABLE_LENS, true><<<g, b, 0, st>>>(job); else camContribKernel<CAM_TABLE_LENS, false><<<g, b, 0, st>>>(job); }
+  HIPCHK(c, hipGetLastError());
+  if (e1) HIPCHK(c, hipEventRecord(e1, st));
+  return HPT_OK;
+}
+
+extern "C" int hpt_cam_create(hpt_ctx* c, int kind, hpt_cam** out)
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  *out = nullptr;
+  if (kind != CAM_PINHOLE && kind != CAM_TABLE_LENS) return c->fail(HPT_ERR_ARG, "hpt_cam_create: kind must be 0 (pinhole) or 1 (table lens)");
+  hpt_cam* cam = new hpt_cam();
+  cam->ctx = c; cam->kind = kind;
+  *out = cam;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_cam_create"); }
+extern "C" void hpt_cam_destroy(hpt_cam* cam)
+try {
+  if (!cam) return;
+  (void)hipSetDevice(cam->ctx->device);
+  (void)hipDeviceSynchronize();
+  delete cam;                                                  // (its DevBuf members free the device arrays)
+}
+catch (...) { (void)hptGuard(nullptr, "hpt_cam_destroy"); }
+
+extern "C" int hpt_cam_set_parameters(hpt_cam* cam, uint32_t width, uint32_t height, const float* projInv16, int spectralMode)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (!projInv16) return c->fail(HPT_ERR_ARG, "SetParameters: projInv16 is null");
+  if (width == 0u || height == 0u || (uint64_t)width * height > 0x7FFFFFFFull) return c->fail(HPT_ERR_ARG, "SetParameters: width * height must be 1 .. 2^31 - 1");
+  (void)hipSetDevice(c->device);
+  cam->width = width; cam->height = height; cam->spectral = spectralMode != 0 ? 1 : 0;
+  std::memcpy(cam->projInv, projInv16, sizeof(cam->projInv));
+  cam->paramsSet = true;
+  if (cam->spectral) { if (int rc = camEnsureCie(cam)) return rc; }
+  else if (cam->dWaves.p) HIPCHK(c, hipMemset(cam->dWaves.p, 0, (size_t)cam->batch * 4));   // RGB rays carry wavelength 0: the pinhole's RGB kernel does not write it again
+  return HPT_OK;
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_set_parameters"); }
+
+extern "C" int hpt_cam_set_lens(hpt_cam* cam, const float* lines4, uint32_t n, float physSizeX, float physSizeY)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (cam->kind != CAM_TABLE_LENS) return c->fail(HPT_ERR_ARG, "hpt_cam_set_lens: a pinhole camera has no lens table");
+  if (!lines4) return c->fail(HPT_ERR_ARG, "hpt_cam_set_lens: lines4 is null");
+  if (n == 0u || n > 64u) return c->fail(HPT_ERR_ARG, "hpt_cam_set_lens: 1 .. 64 lens interfaces");
+  for (uint32_t i = 0; i < n; i++) if (!(lines4[4 * i + 3] >= 0.0f)) return c->fail(HPT_ERR_ARG, "hpt_cam_set_lens: negative aperture radius");
+  (void)hipSetDevice(c->device);
+  std::vector<float4> l(n);
+  for (uint32_t i = 0; i < n; i++) l[i] = make_float4(lines4[4 * i], lines4[4 * i + 1], lines4[4 * i + 2], lines4[4 * i + 3]);
+  HIPCHK(c, hipDeviceSynchronize());                           // (a tile in flight may still read the old lines)
+  HIPCHK(c, cam->dLines.upload(l.data(), l.size()));
+  cam->lensCount = n; cam->physSize[0] = physSizeX; cam->physSize[1] = physSizeY;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_set_lens"); }
+
+extern "C" int hpt_cam_set_batch_size(hpt_cam* cam, uint32_t tile)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (tile == 0u || tile > (1u << 28)) return c->fail(HPT_ERR_ARG, "SetBatchSize: the tile must hold 1 .. 2^28 rays");
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, cam->dGens.alloc(tile)); HIPCHK(c, cam->dWaves.alloc(tile)); HIPCHK(c, cam->dCos4.alloc(tile));
+  HIPCHK(c, cam->dRayPos.alloc(tile)); HIPCHK(c, cam->dRayDir.alloc(tile)); HIPCHK(c, cam->dColors.alloc((size_t)tile * 4));
+  cam->batch = tile;
+  camInitGensKernel<<<dim3((tile + 255u) / 256u), dim3(256), 0, 0>>>(cam->dGens.p, tile);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemset(cam->dWaves.p, 0, (size_t)tile * 4));
+  HIPCHK(c, hipMemset(cam->dCos4.p, 0, (size_t)tile * 4));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_set_batch_size"); }
+
+extern "C" int hpt_cam_make_rays_block_dev(hpt_cam* cam, float* rayPosDev, float* rayDirDev, uint32_t n, int subPassId, void* stream)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (!rayPosDev || !rayDirDev) return c->fail(HPT_ERR_ARG, "MakeRaysBlock: a ray array is null");
+  if (int rc = camTileCheck(cam, "MakeRaysBlock", n, subPassId)) return rc;
+  if (cam->kind == CAM_TABLE_LENS && cam->lensCount == 0u) return c->fail(HPT_ERR_ARG, "MakeRaysBlock: the table-lens camera has no lens lines (hpt_cam_set_lens)");
+  if (n == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  cam->renderPending = false;
+  return camLaunchMake(cam, (float4*)rayPosDev, (float4*)rayDirDev, n, subPassId, (hipStream_t)stream, c->ev0, c->ev1);
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_make_rays_block_dev"); }
+extern "C" int hpt_cam_make_rays_block(hpt_cam* cam, float* rayPos, float* rayDir, uint32_t n, int subPassId)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (!rayPos || !rayDir) return c->fail(HPT_ERR_ARG, "MakeRaysBlock: a ray array is null");
+  if (int rc = camTileCheck(cam, "MakeRaysBlock", n, subPassId)) return rc;
+  if (cam->kind == CAM_TABLE_LENS && cam->lensCount == 0u) return c->fail(HPT_ERR_ARG, "MakeRaysBlock: the table-lens camera has no lens lines (hpt_cam_set_lens)");
+  if (n == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  return roundTrip(c, cam->tMake, KERNEL_EVENTS,                // every ray record is written: nothing goes up; the tile buffers serve as the device copies
+                   [&]() -> int { return HPT_OK; },
+                   [&]() -> int { return hpt_cam_make_rays_block_dev(cam, (float*)cam->dRayPos.p, (float*)cam->dRayDir.p, n, subPassId, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(rayPos, cam->dRayPos.p, (size_t)n * 16, hipMemcpyDeviceToHost)); HIPCHK(c, hipMemcpy(rayDir, cam->dRayDir.p, (size_t)n * 16, hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_make_rays_block"); }
+
+static int camContribCheck(hpt_cam* cam, const void* out, const void* colors, uint32_t n, uint32_t width, uint32_t height, int subPassId)
+{
+  hpt_ctx* c = cam->ctx;
+  if (!out) return c->fail(HPT_ERR_ARG, "AddSamplesContributionBlock: out_color4f is null");
+  if (!colors) return c->fail(HPT_ERR_ARG, "AddSamplesContributionBlock: colors is null");
+  if (int rc = camTileCheck(cam, "AddSamplesContributionBlock", n, subPassId)) return rc;
+  if (width != cam->width || height != cam->height) return c->fail(HPT_ERR_ARG, "AddSamplesContributionBlock: a_width / a_height differ from SetParameters");
+  return HPT_OK;
+}
+extern "C" int hpt_cam_add_samples_contribution_block_dev(hpt_cam* cam, float* outDev, const float* colorsDev, uint32_t n, uint32_t width, uint32_t height, int subPassId, void* stream)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (int rc = camContribCheck(cam, outDev, colorsDev, n, width, height, subPassId)) return rc;
+  if (n == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  cam->renderPending = false;
+  return camLaunchContrib(cam, (float4*)outDev, colorsDev, n, subPassId, (hipStream_t)stream, c->ev0, c->ev1);
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_add_samples_contribution_block_dev"); }
+extern "C" int hpt_cam_add_samples_contribution_block(hpt_cam* cam, float* out, const float* colors, uint32_t n, uint32_t width, uint32_t height, int subPassId)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (int rc = camContribCheck(cam, out, colors, n, width, height, subPassId)) return rc;
+  if (n == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  DevBuf<float> dOut;                                          // the frame goes up (it is added to) and comes back, as in RayTraceBlock's host form
+  const size_t nf = (size_t)width * height * 4, nc = (size_t)n * (cam->spectral ? 1u : 4u);
+  return roundTrip(c, cam->tContrib, KERNEL_EVENTS,
+                   [&]() -> int { HIPCHK(c, dOut.upload(out, nf)); HIPCHK(c, hipMemcpy(cam->dColors.p, colors, nc * 4, hipMemcpyHostToDevice)); return HPT_OK; },
+                   [&]() -> int { return hpt_cam_add_samples_contribution_block_dev(cam, dOut.p, cam->dColors.p, n, width, height, subPassId, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, dOut.p, nf * 4, hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_add_samples_contribution_block"); }
+
+extern "C" int hpt_cam_read_state(hpt_cam* cam, uint32_t* gens, float* waves, float* cos4, uint32_t n)
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (n > cam->batch) return c->fail(HPT_ERR_ARG, "hpt_cam_read_state: n exceeds the batch size");
+  if (n == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipDeviceSynchronize());
+  if (gens)  HIPCHK(c, hipMemcpy(gens, cam->dGens.p, (size_t)n * 8, hipMemcpyDeviceToHost));
+  if (waves) HIPCHK(c, hipMemcpy(waves, cam->dWaves.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  if (cos4)  HIPCHK(c, hipMemcpy(cos4, cam->dCos4.p, (size_t)n * 4, hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_read_state"); }
+
+// main_with_cam_gpu.cpp:230-266: per pass and tile vkCmdFillBuffer(rayCol), MakeRaysBlockCmd, PathTraceFromInputRaysCmd, AddSamplesContributionBlockCmd,
+// all on one stream; the host waits for nothing (the tile count rounds up: a short last tile instead of the reference's dropped remainder)
+extern "C" int hpt_cam_render_dev(hpt_ctx* c, hpt_cam* cam, float* frameDev, uint32_t passes, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (!cam || cam->ctx != c) return c->fail(HPT_ERR_ARG, "hpt_cam_render_dev: the camera is null or belongs to another context");
+  if (!frameDev) return c->fail(HPT_ERR_ARG, "hpt_cam_render_dev: the frame is null");
+  if (int rc = camTileCheck(cam, "hpt_cam_render_dev", 0u, 0)) return rc;
+  if (cam->kind == CAM_TABLE_LENS && cam->lensCount == 0u) return c->fail(HPT_ERR_ARG, "hpt_cam_render_dev: the table-lens camera has no lens lines (hpt_cam_set_lens)");
+  if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "hpt_cam_render_dev before CommitDeviceData / UpdateMembersPlainData");
+  if ((c->S.spectralMode != 0u) != (cam->spectral != 0)) return c->fail(HPT_ERR_ARG, "hpt_cam_render_dev: the camera's spectralMode and the integrator's m_spectral_mode differ");
+  if (c->dGens.n < cam->batch || c->gensCount < cam->batch) return c->fail(HPT_ERR_STATE, "hpt_cam_render_dev: m_randomGens smaller than the batch size (InitRandomGens)");
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const uint32_t channels = cam->spectral ? 1u : 4u;
+  const uint64_t pixels = (uint64_t)cam->width * cam->height;
+  const uint32_t tiles = (uint32_t)((pixels + cam->batch - 1u) / cam->batch);
+  const uint64_t total = (uint64_t)tiles * passes;
+  const uint32_t timed = (uint32_t)std::min<uint64_t>(total, CAM_TIMED_TILES);
+  while (cam->ev.size() < (size_t)timed * 4 + 2) { hipEvent_t e = nullptr; HIPCHK(c, hipEventCreate(&e)); cam->ev.push_back(e); }
+  cam->evTiles = timed; cam->renderPending = false;
+  cam->tRender[1] = (float)total; cam->tRender[2] = (float)timed;
+  if (total == 0u) return HPT_OK;
+  hipEvent_t evFirst = cam->ev[(size_t)timed * 4], evLast = cam->ev[(size_t)timed * 4 + 1];
+  HIPCHK(c, hipEventRecord(evFirst, st));
+  uint64_t k = 0;
+  for (uint32_t pass = 0; pass < passes; pass++)
+    for (uint32_t sp = 0; sp < tiles; sp++, k++) {
+      const uint32_t n = (uint32_t)std::min<uint64_t>(cam->batch, pixels - (uint64_t)sp * cam->batch);
+      hipEvent_t* e = k < timed ? &cam->ev[(size_t)k * 4] : nullptr;
+      HIPCHK(c, hipMemsetAsync(cam->dColors.p, 0, (size_t)n * channels * 4, st));
+      if (int rc = camLaunchMake(cam, cam->dRayPos.p, cam->dRayDir.p, n, (int)sp, st, e ? e[0] : nullptr, e ? e[1] : nullptr)) return rc;
+      if (int rc = hpt_path_trace_from_input_rays_block_dev(c, n, channels, (const float*)cam->dRayPos.p, (const float*)cam->dRayDir.p, cam->dColors.p, 1u, st)) return rc;
+      if (e) HIPCHK(c, hipEventRecord(e[2], st));
+      if (int rc = camLaunchContrib(cam, (float4*)frameDev, cam->dColors.p, n, (int)sp, st, nullptr, e ? e[3] : nullptr)) return rc;
+    }
+  HIPCHK(c, hipEventRecord(evLast, st));
+  cam->renderPending = true;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_cam_render_dev"); }
+
+extern "C" int hpt_cam_get_execution_time(hpt_cam* cam, const char* name, float out[4])
+try {
+  if (!cam) return HPT_ERR_ARG;
+  hpt_ctx* c = cam->ctx;
+  if (!name || !out) return c->fail(HPT_ERR_ARG, "GetExecutionTime: a null argument");
+  if (cam->renderPending) {                                    // the last loop's events: make = e0..e1, trace = e1..e2 (with its queue reset), contribute = e2..e3
+    (void)hipSetDevice(c->device);
+    const size_t t4 = (size_t)cam->evTiles * 4;
+    HIPCHK(c, hipEventSynchronize(cam->ev[t4 + 1]));
+    double make = 0.0, trace = 0.0, contrib = 0.0;
+    for (uint32_t k = 0; k < cam->evTiles; k++) {
+      float a = 0.0f, b = 0.0f, d = 0.0f; hipEvent_t* e = &cam->ev[(size_t)k * 4];
+      (void)hipEventElapsedTime(&a, e[0], e[1]); (void)hipEventElapsedTime(&b, e[1], e[2]); (void)hipEventElapsedTime(&d, e[2], e[3]);
+      make += a; trace += b; contrib += d;
+    }
+    float whole = 0.0f; (void)hipEventElapsedTime(&whole, cam->ev[t4], cam->ev[t4 + 1]);
+    cam->tMake[0] = (float)make; cam->tTrace[0] = (float)trace; cam->tContrib[0] = (float)contrib; cam->tRender[0] = whole;
+    for (int i = 1; i < 4; i++) cam->tMake[i] = cam->tTrace[i] = cam->tContrib[i] = 0.0f;
+    cam->renderPending = false;
+  }
+  const std::string n(name);
+  const float* src = nullptr;
+  if (n == "MakeRaysBlock" || n == "MakeRays") src = cam->tMake;
+  else if (n == "AddSamplesContributionBlock" || n == "AddSamplesContribution") src = cam->tContrib;
+  else if (n == "PathTraceFromInputRays" || n == "PathTraceFromInputRaysBlock") src = cam->tTrace;
+  else if (n == "Render") src = cam->tRender;
+  if (!src) return HPT_OK;
+  for (int i = 0; i < 4; i++) out[i] = src[i];
+  return HPT_OK;
+}
+catch (...) { return hptGuard(cam ? cam->ctx : nullptr, "hpt_cam_get_execution_time"); }
 
 // ---- IntegratorQMC::PathTraceBlock (mlt/integrator_qmc.cpp:284-315; hpt_qmc.hip) -----------------------------------------------------------------
 extern "C" int hpt_qmc_table(uint32_t out[341])

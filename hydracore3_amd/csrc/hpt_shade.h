@@ -56,6 +56,9 @@ HPT_DEV bool lensRefract(V3 wi, V3 n, float eta, V3& wt)
   wt = eta * (-1.0f) * wi + (eta * cosThetaI - cosThetaT) * n;
   return true;
 }
+// QUADRATIC: the root finder - lensQuadratic for the integrator; the camera plug-in's cameras carry their own (hpt_camrays.hip)
+struct LensQuadraticF { HPT_DEV bool operator()(float A, float B, float C, float& t0, float& t1) const { return lensQuadratic(A, B, C, t0, t1); } };
+template <class QUADRATIC>
 HPT_DEV bool intersectSphericalElement(float radius, float zCenter, V3 rayPos, V3 rayDir, float& t, V3& n)
 {
   const V3 o = rayPos - v3(0, 0, zCenter);
@@ -63,7 +66,7 @@ HPT_DEV bool intersectSphericalElement(float radius, float zCenter, V3 rayPos, V
   const float B = 2 * (rayDir.x * o.x + rayDir.y * o.y + rayDir.z * o.z);
   const float C = o.x * o.x + o.y * o.y + o.z * o.z - radius * radius;
   float t0, t1;
-  if (!lensQuadratic(A, B, C, t0, t1)) return false;
+  if (!QUADRATIC()(A, B, C, t0, t1)) return false;
   const bool useCloserT = (rayDir.z > 0.0f) != (radius < 0.0f);
   t = useCloserT ? smin(t0, t1) : smax(t0, t1);
   if (t < 0.0f) return false;
@@ -71,12 +74,13 @@ HPT_DEV bool intersectSphericalElement(float radius, float zCenter, V3 rayPos, V
   n = (dot(n, -1.0f * rayDir) < 0.f) ? (-1.0f) * n : n;               // faceforward
   return true;
 }
-HPT_DEV bool traceLensesFromFilm(const DevScene& S, V3& rayPos, V3& rayDir)
+template <class QUADRATIC>
+HPT_DEV bool traceLensesFromFilm(const float4* lensLines, const uint lensCount, V3& rayPos, V3& rayDir)
 {
   float elementZ = 0;
   V3 p = v3(rayPos.x, rayPos.y, -rayPos.z), d = v3(rayDir.x, rayDir.y, -rayDir.z);     // camera -> lens-system space
-  for (uint i = 0; i < S.lensCount; i++) {
-    const float4 e = S.lensLines[i];                                   // {curvatureRadius, thickness, eta, apertureRadius}
+  for (uint i = 0; i < lensCount; i++) {
+    const float4 e = lensLines[i];                                   // {curvatureRadius, thickness, eta, apertureRadius}
     elementZ -= e.y;
     float t; V3 n = v3(0, 0, 0);
     const bool isStop = (e.x == 0.0f);
@@ -84,14 +88,14 @@ HPT_DEV bool traceLensesFromFilm(const DevScene& S, V3& rayPos, V3& rayDir)
       if (d.z >= 0.0f) return false;
       t = (elementZ - p.z) / d.z;
     } else {
-      if (!intersectSphericalElement(e.x, elementZ + e.x, p, d, t, n)) return false;
+      if (!intersectSphericalElement<QUADRATIC>(e.x, elementZ + e.x, p, d, t, n)) return false;
     }
     const V3 pHit = p + t * d;
     if (pHit.x * pHit.x + pHit.y * pHit.y > e.w * e.w) return false;
     p = pHit;
     if (!isStop) {
       const float etaI = e.z;
-      float etaT = (i == S.lensCount - 1u) ? 1.0f : S.lensLines[i + 1u].z;
+      float etaT = (i == lensCount - 1u) ? 1.0f : lensLines[i + 1u].z;
       if (etaT == 0.0f) etaT = 1.0f;
       V3 wt;
       if (!lensRefract(normalize((-1.0f) * d), n, etaI / etaT, wt)) return false;
@@ -101,6 +105,7 @@ HPT_DEV bool traceLensesFromFilm(const DevScene& S, V3& rayPos, V3& rayDir)
   rayPos = v3(p.x, p.y, -p.z); rayDir = v3(d.x, d.y, -d.z);
   return true;
 }
+HPT_DEV bool traceLensesFromFilm(const DevScene& S, V3& rayPos, V3& rayDir) { return traceLensesFromFilm<LensQuadraticF>(S.lensLines, S.lensCount, rayPos, rayDir); }
 
 // SampleCameraRay + kernel_InitEyeRay2 (integrator_pt.cpp:44-157), RGB subset
 // LENS: the lens-simulation branch exists only in the kernels with every BSDF branch (the host routes scenes with m_enableOpticSim to them):

@@ -305,6 +305,56 @@ int  hpt_path_trace_qmc_block_dev(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t cha
 /* S of the two calls above for (pixelsNum, passNum): min(2^32 - 1, pixelsNum * passNum). Host code; no context. */
 uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum);
 
+/* ---- camera plug-in (cam_plugin/CamPluginAPI.h:39-77; CamPinHole.cpp, CamTableLens.cpp, main_with_cam_gpu.cpp) ----- */
+/* The two ICamRaysAPI2 cameras of the reference on the device, and the loop that feeds PathTraceFromInputRaysBlock from them with rays, colours
+ * and frame resident in device memory. A camera belongs to the context it was made from (its device, its error text: failures below are reported
+ * through that context's hpt_last_error) and must be destroyed before it. Lane tid of a tile serves pixel p = subPassId * batchSize + tid
+ * (x = p % width, y = p / width) and owns slot tid of the per-lane arrays m_randomGens, m_storedWaves, m_storedCos4, which chain from call to
+ * call as in the reference. Everywhere: n <= batchSize and subPassId * batchSize + n <= width * height, else HPT_ERR_ARG (a short last tile
+ * is allowed; the reference passes the batch size only); null pointers are HPT_ERR_ARG; rays or contributions before both
+ * hpt_cam_set_parameters and hpt_cam_set_batch_size are HPT_ERR_ARG; a refused call leaves the camera as it was. */
+typedef struct hpt_cam hpt_cam;
+/* CamPinHole::CamPinHole / CamTableLens::CamTableLens: kind 0 = pinhole, 1 = table lens */
+int  hpt_cam_create(hpt_ctx* ctx, int kind, hpt_cam** out);
+void hpt_cam_destroy(hpt_cam* cam);
+/* SetParameters(a_width, a_height, a_params) (CamPinHole.cpp:14-22, CamTableLens.cpp:60-68): projInv16 = inverse4x4(perspectiveMatrix(fov,
+ * aspect, near, far)), column-major like hpt_params::projInv, made by the caller's matrix code; spectralMode = CamParameters::spectralMode. */
+int  hpt_cam_set_parameters(hpt_cam* cam, uint32_t width, uint32_t height, const float* projInv16, int spectralMode);
+/* `lines` and m_physSize of CamTableLens::Init (CamTableLens.cpp:87-112): lines4 = n x {curvatureRadius, thickness, eta, apertureRadius}, film
+ * side first (the layout of hpt_set_optics; 1 .. 64 lines). A table-lens camera without lines makes no rays; a pinhole refuses the call. */
+int  hpt_cam_set_lens(hpt_cam* cam, const float* lines4, uint32_t n, float physSizeX, float physSizeY);
+/* SetBatchSize / Init(a_maxThreads) (CamPinHole.cpp:24-39, CamTableLens.cpp:70-85): allocates the per-lane arrays and the tile buffers on the
+ * device; m_randomGens[i] = RandomGenInit(i + 12345 * i), the seed formed with 32-bit wrap-around and taken as int (the reference's int
+ * overflows from i = 173 942: DESIGN.md 7); stored waves and cos4 start at 0. */
+int  hpt_cam_set_batch_size(hpt_cam* cam, uint32_t tile);
+/* MakeRaysBlock(out_rayPosAndNear4f, out_rayDirAndFar4f, in_blockSize, subPassId) (CamPinHole.cpp:41-96, CamTableLens.cpp:116-287): n camera-space
+ * rays, RayPosAndW / RayDirAndT of 16 bytes each. Pinhole: through the pixel centre, origin 0; in spectral mode one rndFloat1 of slot tid gives
+ * the wavelength. Table lens: one rndFloat4 of slot tid, a film point, a point on the rear element, the lens stack; a blocked ray is origin
+ * (0, -1e7, 0), direction (0, -1, 0). Host-pointer form, and device-pointer form asynchronous on stream (a hipStream_t, NULL = default stream). */
+int  hpt_cam_make_rays_block(hpt_cam* cam, float* rayPosAndW, float* rayDirAndT, uint32_t n, int subPassId);
+int  hpt_cam_make_rays_block_dev(hpt_cam* cam, float* rayPosAndWDev, float* rayDirAndTDev, uint32_t n, int subPassId, void* stream);
+/* AddSamplesContributionBlock(out_color4f, colors4f, in_blockSize, a_width, a_height, subPassId) (CamPinHole.cpp:46-50, 98-131,
+ * CamTableLens.cpp:121-125, 289-319): out_color4f[p].rgb += colour of ray tid (times the stored cos^4 for the table lens), alpha untouched.
+ * colors: 4 floats per ray; in spectral mode 1 float per ray, taken as four equal samples at the ray's stored wavelength through SpectrumToXYZ
+ * (360, 830, the context's m_cie_xyz or, without a spectral scene, the loaders' table) and XYZToRGB; CamTableLens.cpp:309 calls a seven-argument
+ * SpectrumToXYZ that does not exist: defined as the pinhole's call. width / height must be those of hpt_cam_set_parameters. */
+int  hpt_cam_add_samples_contribution_block(hpt_cam* cam, float* out_color4f, const float* colors, uint32_t n, uint32_t width, uint32_t height, int subPassId);
+int  hpt_cam_add_samples_contribution_block_dev(hpt_cam* cam, float* out_color4fDev, const float* colorsDev, uint32_t n, uint32_t width, uint32_t height,
+                                                int subPassId, void* stream);
+/* No counterpart in the reference: host copies of the first n slots of m_randomGens (uint32 pairs), m_storedWaves and m_storedCos4, for tests
+ * and callers that checkpoint. Any of the three may be NULL. Synchronises the device. */
+int  hpt_cam_read_state(hpt_cam* cam, uint32_t* gensUint2, float* waves, float* cos4, uint32_t n);
+/* The loop of main_with_cam_gpu.cpp:230-266, `passes` times over the ceil(width * height / batchSize) tiles: zero the tile's colours,
+ * MakeRaysBlock, PathTraceFromInputRaysBlock(n, channels, ..., a_passNum = 1), AddSamplesContributionBlock into frame4fDev (width * height * 4
+ * floats, added to). channels = 1 in spectral mode, else 4. Everything is enqueued on `stream`; nothing waits for the device. Needs
+ * hpt_init_random_gens(>= batchSize) and an integrator whose m_spectral_mode agrees with the camera's. */
+int  hpt_cam_render_dev(hpt_ctx* ctx, hpt_cam* cam, float* frame4fDev, uint32_t passes, void* stream);
+/* GetExecutionTime(a_funcName, a_out) (CamPluginAPI.h:76). "MakeRaysBlock" / "AddSamplesContributionBlock": the four slots of the last
+ * host-pointer call, as hpt_get_execution_time; after hpt_cam_render_dev (which this call waits for) out[0] = that stage's kernel time summed
+ * over the loop's first 256 tiles. "PathTraceFromInputRays": the same sum for the trace stage. "Render": out[0] = first to last event of the
+ * whole loop, out[1] = tiles rendered, out[2] = tiles timed per stage. Unknown names leave out untouched. */
+int  hpt_cam_get_execution_time(hpt_cam* cam, const char* funcName, float out[4]);
+
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
