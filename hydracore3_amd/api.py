@@ -66,6 +66,8 @@ ABI = {
     "hpt_reset_diff_tex": (_i, [_vp]),
     "hpt_path_trace_dr": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, C.POINTER(_f)]),
     "hpt_path_trace_dr_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "hpt_ray_trace_dr": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, C.POINTER(_f)]),
+    "hpt_ray_trace_dr_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "hpt_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
     "hpt_image2d4f_regularizer_dev": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "hpt_image2d4f_regularizer": (_i, [_vp, _i, _i, _vp, _vp]),
@@ -464,6 +466,33 @@ class HipIntegrator:
         self._chk(self.L.hpt_device_memset(self.h, grad.ptr, 0, grad.nbytes))
         self._chk(self.L.hpt_device_memset(self.h, loss.ptr, 0, 4))
         self._chk(self.L.hpt_path_trace_dr_dev(self.h, tid_begin, tid, channels, out.ptr, a_passNum, ref.ptr, data.ptr, grad.ptr, data.size, loss.ptr, None))
+
+    def RayTraceDR(self, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad):
+        """IntegratorDR::RayTraceDR(tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize): one pinhole ray per pixel,
+        base colour x texture, squared difference to a_refImg (float32 [winHeight, winWidth, channels], rows bottom-up, channels 3 or 4).
+        out_color float32 [winHeight, winWidth, 4]: hit pixels ASSIGNED (colour, 0), missed pixels and pixels past tid untouched. a_dataGrad
+        is overwritten. Returns the reference's value: the per-pixel losses / a_passNum, summed in float in tid order. a_data None: no
+        parameter texture is fetched."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and out_color.size == self.N * 4
+        a_refImg = np.ascontiguousarray(a_refImg, np.float32)
+        assert channels not in (3, 4) or a_refImg.size == self.N * channels          # (other channel counts: the library refuses them)
+        assert a_dataGrad is None or (a_dataGrad.dtype == np.float32 and a_dataGrad.flags["C_CONTIGUOUS"])
+        if a_data is not None:
+            a_data = np.ascontiguousarray(a_data, np.float32)
+            assert a_dataGrad is None or a_dataGrad.size == a_data.size             # (a_data without a_dataGrad: a_gradSize = 0, refused by the library when a texture is registered)
+        loss = C.c_float(0)
+        self._chk(self.L.hpt_ray_trace_dr(self.h, tid, channels, out_color.ctypes.data, a_passNum, a_refImg.ctypes.data,
+                                          None if a_data is None else a_data.ctypes.data, None if a_dataGrad is None else a_dataGrad.ctypes.data,
+                                          0 if a_dataGrad is None else a_dataGrad.size, C.byref(loss)))
+        return loss.value
+
+    def RayTraceDR_dev(self, out: "DevArray", a_passNum, ref: "DevArray", data: "DevArray", grad: "DevArray", loss_per_pixel: "DevArray" = None,
+                       loss: "DevArray" = None, tid=None, channels=4, stream=None):
+        """RayTraceDR with every array resident in HBM; asynchronous. `grad` is ACCUMULATED into (zero it yourself); loss_per_pixel [tid] is
+        assigned; `loss` (one float) is ADDED the sum of loss / a_passNum (one float atomic per wave: reproducible to rounding only)."""
+        self._chk(self.L.hpt_ray_trace_dr_dev(self.h, self.N if tid is None else tid, channels, out.ptr, a_passNum, ref.ptr, None if data is None else data.ptr,
+                                              None if grad is None else grad.ptr, 0 if grad is None else grad.size,
+                                              None if loss_per_pixel is None else loss_per_pixel.ptr, None if loss is None else loss.ptr, stream))
 
     def AdamStep_dev(self, state: "DevArray", grad: "DevArray", momentum: "DevArray", gsq: "DevArray", it: int):
         """AdamOptimizer<float>::step(state, grad, iter) (diff_render/adam.h:43-62) on device arrays."""

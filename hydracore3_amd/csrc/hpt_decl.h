@@ -198,6 +198,12 @@ template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) castSingleRayKernel(const DevScene S, const uint* packedXY, uint tidCount, float* outColor, uint* stackOverflow);
 template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) rayTraceKernel(const DevScene S, const uint* packedXY, uint tidCount, uint channels, float* outColor, uint* stackOverflow);
+// ---- IntegratorDR::RayTraceDR (hpt_raytrace_dr.hip) ------------------------------------------------------------------------------------
+// one lane per pixel of packedXY[0 .. tidCount); outColor: pixels of 4 floats (hits assigned, misses untouched); refImg: pixels of `channels` = 3 or 4
+// floats, bottom-up; GRAD: registered textures are fetched from `data` and `grad` is accumulated into; lossPerPixel [tidCount] and lossAccum may be null
+template <bool FLAT, bool MOTION, bool SWEEP, bool GRAD>
+__global__ void __launch_bounds__(256) rayTraceDrKernel(const DevScene S, const uint* packedXY, uint tidCount, uint channels, float passNum, float* outColor,
+                                                        const float* refImg, const float* data, float* grad, float* lossPerPixel, float* lossAccum, uint* stackOverflow);
 
 // ---- IntegratorQMC::PathTraceBlock (hpt_qmc.hip) ---------------------------------------------------------------------------------------
 static const uint QMC_DIMENSIONS = 11u, QMC_RESOLUTION = 31u;

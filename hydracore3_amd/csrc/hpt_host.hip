@@ -169,6 +169,7 @@ struct hpt_ctx
   void* rcclLib = nullptr; void* comm = nullptr; int commRanks = 0, commRank = 0;
   bool forceFull = false;                // diagnostic (hpt_set_option "force_full_materials")
   bool drSkipNonFinite = false;          // hpt_set_option "dr_skip_nonfinite": off = PixelLossPT as the reference has it
+  bool drGradMode = true;                // hpt_set_option "dr_grad_mode": IntegratorDR's m_gradMode, read by RayTraceDR only
   bool leanMaterials = false;            // every material is gltf or emissive: the kernels without the other BSDF branches are used
   int  schedule = 0;                     // 0 automatic, 1 megakernel, 2 wavefront, 3 megakernel with block-local ray repacking (hpt_set_schedule)
   int  bwWide = -1;                        // hpt_set_option("bw_wide"): -1 the 4-wide tree on heavy scenes only, 0 never, 1 whenever the scene has one
@@ -194,7 +195,7 @@ struct hpt_ctx
 
   // GetExecutionTime slots
   float tPathTrace[4] = {0, 0, 0, 0}, tNaive[4] = {0, 0, 0, 0}, tDR[4] = {0, 0, 0, 0}, tFromRays[4] = {0, 0, 0, 0};
-  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0};
+  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0}, tRayTraceDR[4] = {0, 0, 0, 0};
   float lastKernelMs = 0.0f;
 
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
@@ -2731,6 +2732,76 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_dr"); }
 
+// ---- IntegratorDR::RayTraceDR (integrator_dr.cpp:396-459; hpt_raytrace_dr.hip) ------------------------------------------------------------------------
+// what either form refuses, in the order the neighbouring entry points check: pointers, the calls made so far, tid, then the arguments of its own
+static int rtdr_check(hpt_ctx* c, uint32_t tid, uint32_t channels, const void* out, const void* ref, const void* grad, size_t gradSize)
+{
+  if (int rc = pixelPassCheck(c, "RayTraceDR", "out_color", out, "tid", tid)) return rc;
+  if (!ref) return c->fail(HPT_ERR_ARG, "RayTraceDR: a_refImg is null");
+  if (channels != 3u && channels != 4u) return c->fail(HPT_ERR_ARG, "RayTraceDR: channels must be 3 or 4 (three floats of a_refImg are read per pixel at that stride)");
+  if (gradSize < c->gradSize) return c->fail(HPT_ERR_ARG, "RayTraceDR: a_gradSize smaller than the registered differentiable textures");
+  if (!grad && gradSize != 0) return c->fail(HPT_ERR_ARG, "RayTraceDR: a_dataGrad is null");
+  return HPT_OK;
+}
+extern "C" int hpt_ray_trace_dr_dev(hpt_ctx* c, uint32_t tid, uint32_t channels, float* outDev, uint32_t passNum, const float* refDev, const float* dataDev,
+                                    float* gradDev, size_t gradSize, float* lossPerPixelDev, float* lossAccumDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = rtdr_check(c, tid, channels, outDev, refDev, gradDev, gradSize)) return rc;
+  if (tid == 0u) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const uint blocks = (tid + 255u) / 256u;
+  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
+  const bool withGrad = c->drGradMode && dataDev != nullptr && gradDev != nullptr;   // Tex2DFetchAD's condition (integrator_dr.cpp:99) but for the texture's registration
+  const float fPass = float(passNum);
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+    if (withGrad) rayTraceDrKernel<flat(), motion(), sweep(), true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, dataDev, gradDev, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
+    else          rayTraceDrKernel<flat(), motion(), sweep(), false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, nullptr, nullptr, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
+  });
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_ray_trace_dr_dev"); }
+// Host-pointer form: the frame goes up and comes back (missed pixels and pixels past tid keep the caller's floats), the gradient is zeroed on the
+// device and comes back whole, and the per-pixel losses come back to be summed here as the reference sums them: in tid order, in float, each divided
+// by a_passNum first (integrator_dr.cpp:417-430)
+extern "C" int hpt_ray_trace_dr(hpt_ctx* c, uint32_t tid, uint32_t channels, float* out, uint32_t passNum,
+                                const float* refImg, const float* data, float* dataGrad, size_t gradSize, float* outLoss)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = rtdr_check(c, tid, channels, out, refImg, dataGrad, gradSize)) return rc;
+  (void)hipSetDevice(c->device);
+  if (outLoss) *outLoss = 0.0f;
+  if (tid == 0u) { if (gradSize) std::memset(dataGrad, 0, gradSize * sizeof(float)); return HPT_OK; }   // memset(a_dataGrad, 0, ...) (integrator_dr.cpp:399), no pixel
+  const size_t nOut = (size_t)c->packedCount * 4u, nRef = (size_t)c->packedCount * channels;
+  DevBuf<float> dOut, dRefImg, dDat, dGr, dPix;
+  std::vector<float> pix(tid);
+  const int rc = roundTrip(c, c->tRayTraceDR, KERNEL_EVENTS,
+    [&]() -> int {
+      HIPCHK(c, dOut.upload(out, nOut)); HIPCHK(c, dRefImg.upload(refImg, nRef)); HIPCHK(c, dPix.alloc(tid));
+      if (data && gradSize) HIPCHK(c, dDat.upload(data, gradSize));
+      if (gradSize) { HIPCHK(c, dGr.alloc(gradSize)); HIPCHK(c, hipMemset(dGr.p, 0, gradSize * sizeof(float))); }
+      return HPT_OK;
+    },
+    [&]() -> int { return hpt_ray_trace_dr_dev(c, tid, channels, dOut.p, passNum, dRefImg.p, (data && gradSize) ? dDat.p : nullptr, gradSize ? dGr.p : nullptr, gradSize, dPix.p, nullptr, nullptr); },
+    [&]() -> int {
+      HIPCHK(c, hipMemcpy(out, dOut.p, nOut * sizeof(float), hipMemcpyDeviceToHost));
+      if (gradSize) HIPCHK(c, hipMemcpy(dataGrad, dGr.p, gradSize * sizeof(float), hipMemcpyDeviceToHost));
+      HIPCHK(c, hipMemcpy(pix.data(), dPix.p, (size_t)tid * sizeof(float), hipMemcpyDeviceToHost));
+      return HPT_OK;
+    });
+  if (rc != HPT_OK) return rc;
+  float avgLoss = 0.0f;
+  const float fPass = float(passNum);
+  for (uint32_t i = 0; i < tid; i++) { const float share = pix[i] / fPass; avgLoss += share; }
+  if (outLoss) *outLoss = avgLoss;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_ray_trace_dr"); }
+
 extern "C" int hpt_adam_step_dev(hpt_ctx* c, float* state, const float* grad, float* momentum, float* gsq, size_t n, int iter, void* stream)
 try {
   if (!c || !state || !grad || !momentum || !gsq) return HPT_ERR_ARG;
@@ -2866,6 +2937,7 @@ try {
   else if (n == "CastSingleRay" || n == "CastSingleRayBlock") src = c->tCastSingleRay;      // main.cpp:443
   else if (n == "PathTraceQMC" || n == "PathTraceBlockQMC") src = c->tPathTraceQmc;            // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
   else if (n == "RayTrace" || n == "RayTraceBlock") src = c->tRayTrace;                     // raytraceTime (integrator_pt_host.cpp:75-90)
+  else if (n == "RayTraceDR") src = c->tRayTraceDR;                                         // shadowPtTime (integrator_dr.cpp:441)
   if (!src) return HPT_OK;                                                                 // unknown names leave `out` untouched, as the reference does
   for (int i = 0; i < 4; i++) out[i] = src[i];
   return HPT_OK;
@@ -2921,6 +2993,7 @@ try {
   else if (k == "refit") c->refitEnabled = value != 0;                                  // 0: UpdateInstance / UpdateGeom + CommitScene always rebuild the tree on the host   // voted exit of the inner-node loop; takes effect at the next CommitScene
   else if (k == "dbg_no_normal_lerp") { if (c->S.motion) c->S.motion = value ? 3u : 1u; }   // diagnostic: moving instances without the reference's normal interpolation (bit 1 of DevScene::motion)
   else if (k == "dbg_wf_iter_cap") c->wfIterCap = (uint)value;                         // diagnostic: make the wavefront loop's safety net reachable in a test
+  else if (k == "dr_grad_mode") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_grad_mode: 0 forward only, 1 with the gradient"); c->drGradMode = value != 0; }   // IntegratorDR's a_gradMode: RayTraceDR only
   else if (k == "dr_skip_nonfinite") c->drSkipNonFinite = value != 0;                  // PathTraceDR: drop samples whose radiance is not finite (default 0: PixelLossPT as in the reference)
   else if (k == "shade_records") c->shadeTrisEnabled = value != 0;                     // 0: no DevScene::shadeTris (A/B, diagnosis)
   else if (k == "build_threads") c->buildThreads = std::min(value, 64);                // host threads CommitScene builds its trees with (0: the usable cores, at most 16)

@@ -6,7 +6,7 @@
 //                                  kernel_slicer-generated Integrator_Generated overrides (main.cpp:221-224) --
 //                                  PathTraceBlock, NaivePathTraceBlock, EvalGBuffer, CastSingleRayBlock, RayTraceBlock, PackXYBlock, CommitDeviceData,
 //                                  UpdateMembersPlainData, GetExecutionTime, Update_m_materials / Update_m_lights
-//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136)
+//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136): PutDiffTex2D, PathTraceDR, RayTraceDR
 //
 // The reference's headers cannot be included here (they need the absent LiteMath), so this header carries the same
 // member names over plain arrays; INTEGRATION.md shows the dozen lines that derive the real `Integrator` from it.
@@ -277,6 +277,17 @@ public:
     if (m_ctx) report(hpt_path_trace_dr(m_ctx, 0, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize, &loss), "PathTraceDR");
     return loss;
   }
+  // RayTraceDR (integrator_dr.h:39-40, integrator_dr.cpp:396-459; drmain.cpp:204): the noise-free pass - one pinhole ray per pixel, base colour x
+  // texture, a_dataGrad overwritten; out_color is winWidth * winHeight * 4 floats (hits assigned, misses untouched). Returns the summed loss / a_passNum.
+  float RayTraceDR(uint32_t tid, uint32_t channels, float* out_color, uint32_t a_passNum,
+                   const float* a_refImg, const float* a_data, float* a_dataGrad, size_t a_gradSize)
+  {
+    float loss = 0.0f;
+    if (m_ctx) report(hpt_ray_trace_dr(m_ctx, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize, &loss), "RayTraceDR");
+    return loss;
+  }
+  // m_gradMode (the constructor's a_gradMode in the reference): 0 = RayTraceDR renders and returns the loss without a gradient
+  void SetGradMode(int a_gradMode) { if (m_ctx) report(hpt_set_option(m_ctx, "dr_grad_mode", a_gradMode != 0 ? 1 : 0), "SetGradMode"); }
   // Image2D4fRegularizer (diff_render/integrator_dr.cpp:361-367; drmain.cpp:213-217): grad += d RegLossImage2D4f / d data
   void Image2D4fRegularizer(int w, int h, const float* data, float* grad)
   { if (m_ctx) report(hpt_image2d4f_regularizer(m_ctx, w, h, data, grad), "Image2D4fRegularizer"); }

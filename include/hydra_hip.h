@@ -367,6 +367,29 @@ int  hpt_path_trace_dr(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint3
  * (divide by W*H for the reference's return value); dataGradDev is ACCUMULATED into (zero it yourself). Asynchronous. */
 int  hpt_path_trace_dr_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color_dev, uint32_t passNum,
                            const float* refImgDev, const float* dataDev, float* dataGradDev, size_t gradSize, float* lossAccumDev, void* stream);
+/* IntegratorDR::RayTraceDR(tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize) (integrator_dr.h:39-40,
+ * integrator_dr.cpp:168-273, 372-459; drmain.cpp:204): the differentiable form of CastSingleRayBlock. Per pixel of the first tid entries of
+ * m_packedXY: the pinhole ray through the pixel centre, RayQuery_NearestHit (moving instances at time 0), colour = colors[GLTF_COLOR_BASE].w > 0 ?
+ * clamp(w, 0, 1) splat : colors[GLTF_COLOR_BASE] * texture - the texture fetched from a_data (Tex2DFetchAD) when it is registered with
+ * PutDiffTex2D, a_data is not NULL and dr_grad_mode is 1, else with CastSingleRayBlock's sampler - and loss = dot3(colour - ref, colour - ref)
+ * with ref = a_refImg[((winHeight - y - 1) * winWidth + x) * channels + 0..2]. A HIT assigns (colour, 0) to out_color[(y * winWidth + x) * 4 +
+ * 0..3], at a stride of FOUR whatever channels is: out_color = winWidth * winHeight * 4 floats. A MISS leaves its pixel of out_color untouched;
+ * its colour is 0 and its loss |ref|^2 (the reference returns before kernel_CalcRayColor: DESIGN.md 7). a_dataGrad (a_gradSize floats) is
+ * zeroed and receives d loss / d a_data summed over the pixels (not divided by a_passNum, as in the reference); *outLoss = the per-pixel
+ * losses, each divided by a_passNum, summed in float in tid order: the reference's return value, bit for bit. Host pointers.
+ * channels other than 3 or 4 are HPT_ERR_ARG (three floats of a_refImg are read per pixel at that stride), as are tid > winWidth * winHeight, a
+ * NULL out_color or a_refImg, a NULL a_dataGrad with a_gradSize > 0 and a_gradSize smaller than what is registered. tid = 0 zeroes the gradient
+ * and returns loss 0. State it needs, spectral mode, random numbers: as hpt_cast_single_ray_block. hpt_get_execution_time("RayTraceDR") gives
+ * its four slots. hpt_set_option("dr_grad_mode", 0) stands for the constructor's a_gradMode = 0: the pass renders and returns the loss through
+ * the ordinary sampler and the gradient stays zero (integrator_dr.cpp:432-438); PathTraceDR does not read the option. */
+int  hpt_ray_trace_dr(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* out_color, uint32_t passNum,
+                      const float* refImg, const float* data, float* dataGrad, size_t gradSize, float* outLoss);
+/* Device-pointer form, asynchronous on stream. dataGradDev is ACCUMULATED into with float atomics (zero it yourself; reproducible to rounding
+ * only where two pixels share an element). lossPerPixelDev (NULL or tid floats) receives pixel i's loss at index i, bit-reproducible;
+ * lossAccumDev (NULL or one float) is ADDED the sum of loss / passNum, reduced per wave and then by one float atomic per wave: reproducible to
+ * rounding only. dataDev may be NULL (no texture is then fetched from it and no gradient written). */
+int  hpt_ray_trace_dr_dev(hpt_ctx* ctx, uint32_t tid, uint32_t channels, float* outDev, uint32_t passNum, const float* refDev, const float* dataDev,
+                          float* dataGradDev, size_t gradSize, float* lossPerPixelDev, float* lossAccumDev, void* stream);
 /* AdamOptimizer<float>::step (diff_render/adam.h:43-62) on device arrays. */
 int  hpt_adam_step_dev(hpt_ctx* ctx, float* stateDev, const float* gradDev, float* momentumDev, float* gSquareDev, size_t n, int iter, void* stream);
 /* Image2D4fRegularizer(w, h, data, grad) (diff_render/integrator_dr.cpp:317-367; drmain.cpp:213-217): grad += d RegLossImage2D4f / d data,
@@ -421,6 +444,9 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               Only applied in rounds with at least 2 rays per lane of the trace grid.
  *   "refit"     1 (default): CommitScene after UpdateInstance / UpdateGeom_Triangles3f refits the single-level tree on the device; 0: rebuild.
  *   "node_min"  voted exit of the inner-node loop (0..63, applied at the next hpt_commit_scene; default chosen per scene).
+ * A member of the reference that is set in its constructor:
+ *   "dr_grad_mode"  IntegratorDR's a_gradMode (integrator_dr.h; default 1). 0: RayTraceDR renders and returns the loss through the ordinary
+ *               sampler and writes no gradient (integrator_dr.cpp:99, 432-438). PathTraceDR does not read it.
  * Diagnostic switches (these DO change which kernels run or what they compute; never set in production):
  *   "dr_skip_nonfinite"     PathTraceDR: 1 = a sample whose radiance is not finite contributes neither colour, loss nor gradient (what an
  *                           optimisation loop wants: one NaN poisons Adam's moments for good); 0 (default) = PixelLossPT as the reference
