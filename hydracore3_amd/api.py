@@ -66,6 +66,8 @@ ABI = {
     "hpt_reset_diff_tex": (_i, [_vp]),
     "hpt_path_trace_dr": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, C.POINTER(_f)]),
     "hpt_path_trace_dr_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _vp]),
+    "hpt_path_trace_vjp": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz]),
+    "hpt_path_trace_vjp_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp]),
     "hpt_ray_trace_dr": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, C.POINTER(_f)]),
     "hpt_ray_trace_dr_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _vp, _vp]),
     "hpt_adam_step_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _sz, _i, _vp]),
@@ -201,6 +203,8 @@ class HipIntegrator:
         if rc != 0:
             raise HydraHipError(f"hpt_create(device={device}) failed with code {rc}: no usable MI355X / HIP device")
         self.h = h
+        self.device = device
+        self.grad_size = 0               # floats of a_data the registered differentiable textures occupy (PutDiffTex2D)
         self.scene = None
         self.params = None
         self.W = self.H = self.N = 0
@@ -438,6 +442,7 @@ class HipIntegrator:
         if rc != 0 and size.value == 0 and off.value == 0xFFFFFFFFFFFFFFFF:
             return (off.value, 0)          # reference behaviour for a bad id: message + (size_t(-1), 0)
         self._chk(rc)
+        self.grad_size = off.value + size.value
         return (off.value, size.value)
 
     def PathTraceDR(self, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, tid_begin=0):
@@ -466,6 +471,28 @@ class HipIntegrator:
         self._chk(self.L.hpt_device_memset(self.h, grad.ptr, 0, grad.nbytes))
         self._chk(self.L.hpt_device_memset(self.h, loss.ptr, 0, 4))
         self._chk(self.L.hpt_path_trace_dr_dev(self.h, tid_begin, tid, channels, out.ptr, a_passNum, ref.ptr, data.ptr, grad.ptr, data.size, loss.ptr, None))
+
+    def PathTraceVJP(self, tid, channels, out_color, a_passNum, a_adjImg, a_data, a_dataGrad=None, tid_begin=0):
+        """The vector-Jacobian product of PathTraceDR's frame (no counterpart in the reference): the same paths, colours and generator steps as
+        PathTraceDR, out_color accumulated into, and a_dataGrad overwritten with sum over pixels, samples, c of a_adjImg[y, x, c] *
+        d colour_c / d a_data - a_adjImg float32 [winHeight, winWidth, channels] = dL/d(out_color), rows in out_color's order, nothing divided by
+        a_passNum. a_adjImg None: the frame only (a_dataGrad may be None and is not touched)."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"]
+        a_data = np.ascontiguousarray(a_data, np.float32)
+        if a_adjImg is not None:
+            a_adjImg = np.ascontiguousarray(a_adjImg, np.float32)
+            assert channels not in (3, 4) or a_adjImg.size == self.N * channels     # (other channel counts: the library refuses them)
+        assert a_dataGrad is None or (a_dataGrad.dtype == np.float32 and a_dataGrad.flags["C_CONTIGUOUS"] and a_dataGrad.size == a_data.size)
+        self._chk(self.L.hpt_path_trace_vjp(self.h, tid_begin, tid, channels, out_color.ctypes.data, a_passNum,
+                                            None if a_adjImg is None else a_adjImg.ctypes.data, a_data.ctypes.data,
+                                            None if a_dataGrad is None else a_dataGrad.ctypes.data, a_data.size))
+
+    def PathTraceVJP_dev(self, out: "DevArray", a_passNum, adj: "DevArray", data: "DevArray", grad: "DevArray", tid_begin=0, tid=None, channels=4, stream=None):
+        """PathTraceVJP with every array resident in HBM; asynchronous on `stream`. `grad` is ACCUMULATED into (zero it yourself); adj None
+        (grad may then be None too): the frame only."""
+        tid = self.N - tid_begin if tid is None else tid
+        self._chk(self.L.hpt_path_trace_vjp_dev(self.h, tid_begin, tid, channels, out.ptr, a_passNum, None if adj is None else adj.ptr, data.ptr,
+                                                None if grad is None else grad.ptr, data.size, stream))
 
     def RayTraceDR(self, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad):
         """IntegratorDR::RayTraceDR(tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize): one pinhole ray per pixel,

@@ -25,7 +25,7 @@
 
 namespace hpt {
 
-template <bool DR, bool LEAN, bool DEEP, bool FLAT, bool WIDE>
+template <bool DR, bool LEAN, bool DEEP, bool FLAT, bool WIDE, bool VJP>
 __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKernel(const DevScene S, const Job job, uint refillBelow, uint nodeMin)
 {
   __shared__ uint stackMem[LDS_STACK * 256];
@@ -56,7 +56,7 @@ __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKer
     // ================= S: results of the last round, shading, path ends, regeneration, new rays =================================
     bool wantShadow = false;
     V3 shPos = v3(0, 0, 0), shDir = v3(0, 0, 1); float shFar = 0.0f;
-    bool closing = false; uint sweepBounce = 0; V3 sweepDiff = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
+    bool closing = false; uint sweepBounce = 0; V3 sweepSeed = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
     DrRec lastRec = drEmptyRecord(); bool lastInRegs = false;
     V3 tailR = v3(0, 0, 0);
     // (6') the shadow ray traced in the last round: add the candidate contribution in the megakernel's order
@@ -96,13 +96,22 @@ __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKer
       const V3 env = ld3(S.envColor);
       accum = accum + thr * env;
       const uint XY = PIX_XY;
-      const uint yRef = (uint)S.winHeight - ((XY & 0xFFFF0000u) >> 16) - 1u;
-      const float* rp = job.refImg + ((size_t)yRef * (uint)S.winWidth + (XY & 0x0000FFFFu)) * job.channels;
-      const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
-      if (job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z)) {
-        lossLocal += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
+      const uint px = XY & 0x0000FFFFu, py = (XY & 0xFFFF0000u) >> 16;
+      bool sane, seeded = true; V3 seed = v3(0, 0, 0);                     // seed: dL/d(colour of this sample), see the megakernel
+      if (VJP) {                                                            // PathTraceVJP: the caller's adjoint of the pixel, no loss
+        sane = job.drSkipNonFinite == 0u || __builtin_isfinite(accum.x + accum.y + accum.z);
+        seeded = job.adjImg != nullptr;
+        if (seeded) { const float* ap = job.adjImg + ((size_t)py * (uint)S.winWidth + px) * job.channels; seed = v3(ap[0], ap[1], ap[2]); }
+      } else {
+        const float* rp = job.refImg + ((size_t)((uint)S.winHeight - py - 1u) * (uint)S.winWidth + px) * job.channels;
+        const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
+        sane = job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z);
+        if (sane) lossLocal += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
+        seed = v3(2.0f * diff.x, 2.0f * diff.y, 2.0f * diff.z);
+      }
+      if (sane) {
         PIX(0) += accum.x; PIX(1) += accum.y; PIX(2) += accum.z;
-        closing = true; sweepBounce = bounce; sweepDiff = diff; sweepTail = tailR + env;
+        if (seeded) { closing = true; sweepBounce = bounce; sweepSeed = seed; sweepTail = tailR + env; }
       }
     } else if (finalize) {                                                  // kernel_ContributeToImage (integrator_pt.cpp:598-657)
       const V3 c = accum * ld3(S.camRespoceRGB);
@@ -110,7 +119,7 @@ __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKer
       else { PIX(0) += S.exposureMult * c.x; PIX(1) += S.exposureMult * c.y; PIX(2) += S.exposureMult * c.z; }
     }
     if (DR && __any(closing))
-      drReverseSweep(S, job.record, job.recordLanes, glane, closing, sweepBounce, sweepTail, sweepDiff, job.grad, job.drSkipNonFinite != 0u,
+      drReverseSweep(S, job.record, job.recordLanes, glane, closing, sweepBounce, sweepTail, sweepSeed, job.grad, job.drSkipNonFinite != 0u,
                      stackMem + (threadIdx.x & ~63u), lastRec, lastInRegs, nullptr, 256u);
     const bool idle = !alive && !ending;                                    // no path in flight: next pass of the pixel, or next pixel
     // (1) a finished pixel goes back to HBM
@@ -198,14 +207,14 @@ __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKer
 #undef PIX_XY
 #undef PIX_TID
 #undef PIX_PASSES
-  if (DR) {
+  if (DR && !VJP) {
     float x = lossLocal;
     for (int o2 = 32; o2 > 0; o2 >>= 1) x += __shfl_down(x, o2);
     if ((threadIdx.x & 63) == 0) atomicAdd(job.lossAccum, x);
   }
 }
 
-// explicit instantiations (HPT_BW_INST: 1 forward, 2 PathTraceDR)
+// explicit instantiations (HPT_BW_INST: 1 forward, 2 PathTraceDR, 3 every BSDF branch, 4 PathTraceVJP)
 #ifndef HPT_BW_INST
 #define HPT_BW_INST 0
 #endif
@@ -221,6 +230,14 @@ HPT_BWI(false, true)
 #endif
 #if HPT_BW_INST == 0 || HPT_BW_INST == 2
 HPT_BWI(true, true)
+#endif
+#if HPT_BW_INST == 0 || HPT_BW_INST == 4
+  template __global__ void pathTraceBlockKernel<true, true, false, false, false, true>(const DevScene, const Job, uint, uint);
+  template __global__ void pathTraceBlockKernel<true, true, true,  false, false, true>(const DevScene, const Job, uint, uint);
+  template __global__ void pathTraceBlockKernel<true, true, false, true,  false, true>(const DevScene, const Job, uint, uint);
+  template __global__ void pathTraceBlockKernel<true, true, true,  true,  false, true>(const DevScene, const Job, uint, uint);
+  template __global__ void pathTraceBlockKernel<true, true, false, true,  true,  true>(const DevScene, const Job, uint, uint);
+  template __global__ void pathTraceBlockKernel<true, true, true,  true,  true,  true>(const DevScene, const Job, uint, uint);
 #endif
 #if HPT_BW_INST == 0 || HPT_BW_INST == 3
   template __global__ void pathTraceBlockKernel<false, false, false, false, false>(const DevScene, const Job, uint, uint);

@@ -33,6 +33,11 @@ struct Job
                                   // (0 = the reference's PixelLossPT, which adds them like any other)
   uint*  stackOverflow;           // HBM part of the traversal stacks: [depth - LDS_STACK][global lane]
   uint   gridLanes;
+  // PathTraceVJP (vjp != 0): the sweep of a path is seeded with the caller's dL/d(out_color) of its pixel instead of 2 (colour - ref): pixels of
+  // `channels` floats in out_color's row order (not flipped as a_refImg is). Null: the DR path is rendered and recorded, nothing is swept.
+  // No loss is computed; refImg and lossAccum are not read.
+  const float* adjImg;
+  uint   vjp;
   const float4* inRayPos;         // PathTraceFromInputRays: RayPosAndW[tid] / RayDirAndT[tid] in camera space (MODE 2)
   const float4* inRayDir;
 };
@@ -84,7 +89,9 @@ __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SP
 #define HPT_BW_FULL_WAVES 3      // every BSDF branch: 74 .. 98 VGPRs spilled at 4 waves per SIMD
 #endif
 #define HPT_BW_WAVES(DR, LEAN) ((DR) ? HPT_BW_DR_WAVES : ((LEAN) ? HPT_BW_FWD_WAVES : HPT_BW_FULL_WAVES))
-template <bool DR, bool LEAN, bool DEEP, bool FLAT, bool WIDE = false>   // WIDE: walk DevScene::nodes4 (heavy single-level scenes)
+// VJP (with DR): PathTraceVJP's form of the path end. A template parameter here, a run-time branch on Job::vjp in the other two DR kernels: this
+// kernel already spills at its four waves per SIMD and the branch raised that (18 -> 25 VGPRs on the single-level variant; profiles/dr_vjp.md)
+template <bool DR, bool LEAN, bool DEEP, bool FLAT, bool WIDE = false, bool VJP = false>   // WIDE: walk DevScene::nodes4 (heavy single-level scenes)
 __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKernel(const DevScene S, const Job job, uint refillBelow, uint nodeMin);
 
 // ---- wavefront schedule (hpt_wavefront.hip) --------------------------------------------------------------------------------------------
@@ -133,6 +140,7 @@ struct WfJob
   const uint* packedXY;
   // differentiable rendering (wfShadeKernel<DR = true>): a_refImg, a_data, a_dataGrad, loss accumulator, adjoint records [bounce][field][slot]
   const float* refImg; const float* data; float* grad; float* lossAccum; float* record;
+  const float* adjImg; uint vjp;  // PathTraceVJP: as in Job
 };
 
 #ifndef HPT_WF_SHADE_FULL_WAVES

@@ -195,7 +195,7 @@ struct hpt_ctx
 
   // GetExecutionTime slots
   float tPathTrace[4] = {0, 0, 0, 0}, tNaive[4] = {0, 0, 0, 0}, tDR[4] = {0, 0, 0, 0}, tFromRays[4] = {0, 0, 0, 0};
-  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0}, tRayTraceDR[4] = {0, 0, 0, 0};
+  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0}, tRayTraceDR[4] = {0, 0, 0, 0}, tVJP[4] = {0, 0, 0, 0};
   float lastKernelMs = 0.0f;
 
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
@@ -1566,13 +1566,13 @@ static void launchPT(const DevScene& S, const Job& job, int blocks, hipStream_t 
   }
 }
 
-template <bool DR, bool LEAN>
+template <bool DR, bool LEAN, bool VJP = false>
 static void launchBlock(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep, uint refillBelow, uint nodeMin, bool wide = false)
 {
   const dim3 g(blocks), b(256);
-  if (wide && LEAN) { if (deep) pathTraceBlockKernel<DR, true, true, true, true><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, true, false, true, true><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
-  else if (S.flatMode) { if (deep) pathTraceBlockKernel<DR, LEAN, true, true><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, LEAN, false, true><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
-  else            { if (deep) pathTraceBlockKernel<DR, LEAN, true, false><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, LEAN, false, false><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
+  if (wide && LEAN) { if (deep) pathTraceBlockKernel<DR, true, true, true, true, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, true, false, true, true, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
+  else if (S.flatMode) { if (deep) pathTraceBlockKernel<DR, LEAN, true, true, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, LEAN, false, true, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
+  else            { if (deep) pathTraceBlockKernel<DR, LEAN, true, false, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, LEAN, false, false, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
 }
 
 template <int WIDE>
@@ -1761,7 +1761,8 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     const bool bdeep = (bwide ? std::max(c->stackNeeded, c->stackNeeded4) : c->stackNeeded) > (uint)LDS_STACK;
     const uint bNodeMin = bwide ? std::max(c->bwNodeMin, 16u) : c->bwNodeMin;                           // (a 4-wide visit is three times the work: the vote pays earlier)
     c->lastSchedule = 3; c->lastWide = bwide ? 1u : 0u; c->lastDeep = bdeep ? 1u : 0u;
-    if (dr) launchBlock<true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
+    if (dr && job.vjp != 0u) launchBlock<true, true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);   // (a template parameter in this kernel: hpt_decl.h)
+    else if (dr) launchBlock<true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
     else if (lean) launchBlock<false, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
     else launchBlock<false, false>(c->S, job, std::min(blocks, c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : HPT_BW_FULL_WAVES)), st, bdeep, c->bwRefillBelow, c->bwNodeMin);
   }
@@ -1899,13 +1900,15 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   wj.passNum = job.passNum; wj.channels = job.channels; wj.outColor = job.outColor; wj.gens = job.gens; wj.packedXY = job.packedXY;
   wj.drSkipNonFinite = job.drSkipNonFinite;
   wj.refImg = job.refImg; wj.data = job.data; wj.grad = job.grad; wj.lossAccum = job.lossAccum; wj.record = nullptr;
+  wj.adjImg = job.adjImg; wj.vjp = job.vjp;
   // every path takes at most traceDepth shade passes after the one that generated it; the pass that ends it (or the next one, when a
   // shadow ray was outstanding) also generates the pixel's next path
   // safety net only (the loop ends when a round queues no ray): pixels whose rays were suspended sit rounds out, so there is no tight bound
   const unsigned long long iterCap = c->wfIterCap ? c->wfIterCap : 64ull * ((unsigned long long)job.passNum * (c->S.traceDepth + 2ull) + 4ull);
   c->lastWfIters = 0;
   unsigned long long capLeft = 0;                  // rays still queued when a group ran into iterCap
-  if (dr) { HIPCHK(c, c->dLossAcc.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dLossAcc.p, 0, sizeof(double), st)); }
+  const bool drLoss = dr && job.vjp == 0u;                  // (PathTraceVJP computes no loss: the slots stay zero and are not reduced)
+  if (drLoss) { HIPCHK(c, c->dLossAcc.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dLossAcc.p, 0, sizeof(double), st)); }
   HIPCHK(c, hipEventRecord(c->ev0, st));
   HIPCHK(c, hipEventRecord(c->wfFork, st));
 
@@ -1981,14 +1984,14 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
       }
       if (g.finished) {
         live--;
-        if (dr) wfLossReduceKernel<<<dim3(std::min((g.itemCount + 255u) / 256u, 1024u)), dim3(256), 0, g.stream>>>(pools[gi].lossSlot, g.itemCount, c->dLossAcc.p);
+        if (drLoss) wfLossReduceKernel<<<dim3(std::min((g.itemCount + 255u) / 256u, 1024u)), dim3(256), 0, g.stream>>>(pools[gi].lossSlot, g.itemCount, c->dLossAcc.p);
         HIPCHK(c, hipEventRecord(g.done, g.stream));
         HIPCHK(c, hipStreamWaitEvent(st, g.done, 0));
       }
     }
     HIPCHK(c, hipGetLastError());
   }
-  if (dr) wfLossFinishKernel<<<dim3(1), dim3(1), 0, st>>>(c->dLossAcc.p, job.lossAccum);
+  if (drLoss) wfLossFinishKernel<<<dim3(1), dim3(1), 0, st>>>(c->dLossAcc.p, job.lossAccum);
   HIPCHK(c, hipEventRecord(c->ev1, st));
   if (capLeft != 0ull)
     return c->fail(HPT_ERR_STATE, "wavefront schedule: stopped after " + std::to_string(iterCap) + " rounds with " + std::to_string(capLeft) +
@@ -2732,6 +2735,61 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_dr"); }
 
+// ---- PathTraceVJP: PathTraceDR's paths with the caller's image adjoint as the seed of the reverse sweep (no counterpart in the reference) ------------
+// dataGrad[j] += sum over pixels, samples, c of adjImg[pixel][c] * d C_s[c] / d data[j], C_s the sample's colour as it is added to out_color (not
+// divided by a_passNum). What either form refuses before anything is launched or copied; launch_path_trace then refuses what PathTraceDR refuses.
+static int vjp_check(hpt_ctx* c, uint32_t channels, const void* out, const void* adj, const void* data, const void* grad, size_t gradSize)
+{
+  if (!out || !data) return c->fail(HPT_ERR_ARG, "PathTraceVJP: out_color or a_data is null");
+  if (gradSize < c->gradSize) return c->fail(HPT_ERR_ARG, "PathTraceDR: a_gradSize smaller than the registered differentiable textures");
+  if (channels != 3u && channels != 4u) return c->fail(HPT_ERR_ARG, "PathTraceVJP: channels must be 3 or 4 (the stride of out_color and of the adjoint image)");
+  if (adj && (!grad || gradSize == 0)) return c->fail(HPT_ERR_ARG, "PathTraceVJP: an adjoint image needs a_dataGrad and a non-zero a_gradSize");
+  return HPT_OK;
+}
+extern "C" int hpt_path_trace_vjp_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum,
+                                      const float* adjDev, const float* dataDev, float* gradDev, size_t gradSize, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = vjp_check(c, channels, outDev, adjDev, dataDev, gradDev, gradSize)) return rc;
+  (void)hipSetDevice(c->device);
+  if (tidCount == 0 || passNum == 0) return HPT_OK;
+  Job job; std::memset(&job, 0, sizeof(job));
+  job.tidBegin = tidBegin; job.tidCount = tidCount; job.passNum = passNum; job.channels = channels; job.outColor = outDev;
+  job.vjp = 1u; job.adjImg = adjDev; job.data = dataDev; job.grad = adjDev ? gradDev : nullptr;   // (no adjoint: nothing is swept, a_dataGrad is not touched)
+  return launch_path_trace(c, job, false, true, (hipStream_t)stream);
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_vjp_dev"); }
+
+// host-pointer form: out_color goes up, is added to and comes back; with an adjoint image a_dataGrad is zeroed on the device and comes back whole
+extern "C" int hpt_path_trace_vjp(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, uint32_t passNum,
+                                  const float* adjImg, const float* data, float* dataGrad, size_t gradSize)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = vjp_check(c, channels, out, adjImg, data, dataGrad, gradSize)) return rc;
+  (void)hipSetDevice(c->device);
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceVJP before UpdateMembersPlainData");
+  const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
+  return roundTrip(c, c->tVJP, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+    [&]() -> int {
+      HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, c->dData.alloc(std::max<size_t>(gradSize, 1)));
+      HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));
+      HIPCHK(c, hipMemcpy(c->dData.p, data, gradSize * 4, hipMemcpyHostToDevice));
+      if (adjImg) {
+        HIPCHK(c, c->dRef.alloc(n)); HIPCHK(c, c->dGrad.alloc(gradSize));
+        HIPCHK(c, hipMemcpy(c->dRef.p, adjImg, n * 4, hipMemcpyHostToDevice));
+        HIPCHK(c, hipMemset(c->dGrad.p, 0, gradSize * 4));
+      }
+      return HPT_OK;
+    },
+    [&]() -> int { return hpt_path_trace_vjp_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, adjImg ? c->dRef.p : nullptr, c->dData.p, adjImg ? c->dGrad.p : nullptr, gradSize, nullptr); },
+    [&]() -> int {
+      HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost));
+      if (adjImg) HIPCHK(c, hipMemcpy(dataGrad, c->dGrad.p, gradSize * 4, hipMemcpyDeviceToHost));
+      return HPT_OK;
+    });
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_vjp"); }
+
 // ---- IntegratorDR::RayTraceDR (integrator_dr.cpp:396-459; hpt_raytrace_dr.hip) ------------------------------------------------------------------------
 // what either form refuses, in the order the neighbouring entry points check: pointers, the calls made so far, tid, then the arguments of its own
 static int rtdr_check(hpt_ctx* c, uint32_t tid, uint32_t channels, const void* out, const void* ref, const void* grad, size_t gradSize)
@@ -2937,6 +2995,7 @@ try {
   else if (n == "CastSingleRay" || n == "CastSingleRayBlock") src = c->tCastSingleRay;      // main.cpp:443
   else if (n == "PathTraceQMC" || n == "PathTraceBlockQMC") src = c->tPathTraceQmc;            // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
   else if (n == "RayTrace" || n == "RayTraceBlock") src = c->tRayTrace;                     // raytraceTime (integrator_pt_host.cpp:75-90)
+  else if (n == "PathTraceVJP") src = c->tVJP;                                              // no counterpart: PathTraceDR's slots for the VJP form
   else if (n == "RayTraceDR") src = c->tRayTraceDR;                                         // shadowPtTime (integrator_dr.cpp:441)
   if (!src) return HPT_OK;                                                                 // unknown names leave `out` untouched, as the reference does
   for (int i = 0; i < 4; i++) out[i] = src[i];

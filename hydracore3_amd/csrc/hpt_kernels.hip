@@ -150,7 +150,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     STAMP(3);
     // ---- (7) bookkeeping: adjoint record, end of path ------------------------------------------------------------------------------
     bool closing = false;                              // DR: this lane's path ended in this trip and its gradient is to be scattered
-    V3 sweepDiff = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
+    V3 sweepSeed = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
     DrRec lastRec = drEmptyRecord(); bool lastInRegs = false;
     if (alive) {
       if (didBounce) bounce++;
@@ -178,22 +178,32 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
           // PixelLossPT (integrator_dr.cpp:1103-1132) + hand-derived reverse sweep replacing __enzyme_autodiff (:1172-1183), see drReverseSweep
           const uint pitch = (uint)S.winWidth;
           const uint XY = PIX_XY;
-          const uint yRef = (uint)S.winHeight - ((XY & 0xFFFF0000u) >> 16) - 1u;
-          const float* rp = job.refImg + ((size_t)yRef * pitch + (XY & 0x0000FFFFu)) * job.channels;
-#ifdef HPT_DBG_DR_NOREF      // diagnostic builds only: the reference pixel's load at path end
-          const V3 diff = v3(accum.x - 0.25f, accum.y - 0.25f, accum.z - 0.25f); (void)rp;
-#else
-          const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
-#endif
+          const uint px = XY & 0x0000FFFFu, py = (XY & 0xFFFF0000u) >> 16;
           // PixelLossPT adds every sample, finite or not (integrator_dr.cpp:1124-1131): that is the default here too. One sample in ~1e8 on
           // the 1M-triangle scene comes out non-finite (a 0/0 in a grazing GGX term of the reference's formulas, unguarded there too) and in
           // an optimisation loop a single NaN gradient poisons Adam's moments for good, so hpt_set_option("dr_skip_nonfinite", 1) lets such
           // a sample contribute neither loss, colour nor gradient.
-          const bool sane = job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z);
+          bool sane, seeded = true; V3 seed = v3(0, 0, 0);                  // seed: dL/d(colour of this sample), what the sweep starts from
+          if (job.vjp != 0u) {
+            // PathTraceVJP (wave-uniform branch): the caller's adjoint of the path's pixel, rows in out_color's order; no loss. Without an
+            // adjoint image the sample is only rendered.
+            sane = job.drSkipNonFinite == 0u || __builtin_isfinite(accum.x + accum.y + accum.z);
+            seeded = job.adjImg != nullptr;
+            if (seeded) { const float* ap = job.adjImg + ((size_t)py * pitch + px) * job.channels; seed = v3(ap[0], ap[1], ap[2]); }
+          } else {
+            const float* rp = job.refImg + ((size_t)((uint)S.winHeight - py - 1u) * pitch + px) * job.channels;
+#ifdef HPT_DBG_DR_NOREF      // diagnostic builds only: the reference pixel's load at path end
+            const V3 diff = v3(accum.x - 0.25f, accum.y - 0.25f, accum.z - 0.25f); (void)rp;
+#else
+            const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
+#endif
+            sane = job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z);
+            if (sane) lossLocal += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
+            seed = v3(2.0f * diff.x, 2.0f * diff.y, 2.0f * diff.z);        // d (diff . diff) / d colour: doubling is exact
+          }
           if (sane) {
-            lossLocal += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
             PIX(0) += accum.x; PIX(1) += accum.y; PIX(2) += accum.z;           // out_color += colorRend (:1124-1126)
-            closing = true; sweepDiff = diff; sweepTail = tailR + env;
+            if (seeded) { closing = true; sweepSeed = seed; sweepTail = tailR + env; }
           }
         } else {
           // kernel_ContributeToImage (integrator_pt.cpp:598-657)
@@ -211,7 +221,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       if (__any(closing)) {
         if (STATS) { if (closing) { nSweepLanes++; nSweepBounces += bounce; } if (lane_id() == 0u) nSweepTrips++; }
 #ifndef HPT_DBG_DR_NOSWEEP   // diagnostic builds only
-        drReverseSweep(S, job.record, job.recordLanes, glane, closing, bounce, sweepTail, sweepDiff, job.grad, job.drSkipNonFinite != 0u,
+        drReverseSweep(S, job.record, job.recordLanes, glane, closing, bounce, sweepTail, sweepSeed, job.grad, job.drSkipNonFinite != 0u,
                        drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, lastRec, lastInRegs, STATS ? &nAtomInst : nullptr);
 #endif
       }
@@ -254,7 +264,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       if ((threadIdx.x & 63) == 0 && x) atomicAdd(&job.counters->v[i], x);
     }
   }
-  if (DR) {
+  if (DR && job.vjp == 0u) {
     float x = lossLocal;
     for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
     if ((threadIdx.x & 63) == 0) atomicAdd(job.lossAccum, x);

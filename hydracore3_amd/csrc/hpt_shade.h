@@ -521,8 +521,10 @@ HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce)
   q[8 * s + 1] = 0.0f; q[8 * s + 2] = 0.0f; q[8 * s + 3] = 0.0f;            // T*dS
 }
 // Hand-derived reverse sweep replacing __enzyme_autodiff (integrator_dr.cpp:1172-1183). With T_0 = 1, T_{b+1} = T_b A_b and
-// C = sum_b T_b S_b + T_n tail:  dC/dtex_b = T_b dS_b + T_b dA_b R_{b+1},  R_b = S_b + A_b R_{b+1},  R_n = tail;  the loss gradient
-// 2 (C - ref) dC/dtex_b is scattered to the four bilinear taps with float atomics.
+// C = sum_b T_b S_b + T_n tail:  dC/dtex_b = T_b dS_b + T_b dA_b R_{b+1},  R_b = S_b + A_b R_{b+1},  R_n = tail;  the gradient
+// seed dC/dtex_b is scattered to the four bilinear taps with float atomics. `seed` is dL/dC of the sample: 2 (C - ref) for PathTraceDR's
+// squared difference (the callers double the difference, which is exact, so (seed dC) w is the product it always was), the caller's
+// adjoint of the path's pixel for PathTraceVJP.
 //
 // Called by ALL lanes of a wave, in wave-uniform control flow; `closing`: this lane has a path to close. Float atomics execute at the
 // memory side, one request per 64-byte line an instruction touches, every instruction stays counted in vmcnt for ~3000 cycles with the chip
@@ -534,7 +536,7 @@ HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce)
 // instructions per wave-trip; 360 -> see profiles/r3_measurements.md.) `last`: the record of the closing lane's last bounce when it is
 // still in registers (lastInRegs; it was never stored). `stage`: the wave's 1024-dword LDS area. Same sums, another order.
 static const uint DR_STAGE_DWORDS = 16u * 64u;
-HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, size_t idx, const bool closing, const uint bounceIn, V3 Rn, const V3 diff,
+HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, size_t idx, const bool closing, const uint bounceIn, V3 Rn, const V3 seed,
                             float* grad, const bool skipNonFinite, uint* stage, const DrRec& last, const bool lastInRegs,
                             unsigned long long* statAtomics = nullptr, const uint ss = 64u, const bool defer = true)      // ss: dwords between the staging area's rows (64: an area of its own; 256: the wave's columns of a [16][256] array)
 {
@@ -589,7 +591,7 @@ HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, si
       const uint col = cnt + mbcnt64(hm);
       if (has) {
         const V3 dC = TdS + TdA * Rn;
-        V3 g = v3(2.0f * diff.x * dC.x, 2.0f * diff.y * dC.y, 2.0f * diff.z * dC.z);
+        V3 g = v3(seed.x * dC.x, seed.y * dC.y, seed.z * dC.z);
         if (skipNonFinite && !__builtin_isfinite(g.x + g.y + g.z)) g = v3(0, 0, 0);   // (only with dr_skip_nonfinite: the reference scatters whatever comes out)
         const bool four = (e0 & 0x80000000u) == 0u;
         const float fx1 = 1.0f - fx, fy1 = 1.0f - fy;

@@ -56,7 +56,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   const bool active = valid && (alive || pend || ending || passes != 0u);
   bool wantShadow = false;
   // DR: the reverse sweep runs after the divergent part, by the whole wave (drReverseSweep); what a closing lane hands over to it
-  bool closing = false; uint sweepBounce = 0; V3 sweepDiff = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
+  bool closing = false; uint sweepBounce = 0; V3 sweepSeed = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
   DrRec lastRec = drEmptyRecord(); bool lastInRegs = false;
 
   if (active) {
@@ -115,13 +115,22 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
       const V3 env = ld3(S.envColor);
       accum = accum + thr * env;
       const uint x = XY & 0x0000FFFFu, y = (XY & 0xFFFF0000u) >> 16;
-      const float* rp = job.refImg + ((size_t)((uint)S.winHeight - y - 1u) * (uint)S.winWidth + x) * job.channels;
-      const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
-      if (job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z)) {   // (non-finite samples: see the megakernel)
-        P.lossSlot[s] += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
+      bool sane, seeded = true; V3 seed = v3(0, 0, 0);                      // seed: dL/d(colour of this sample), see the megakernel
+      if (job.vjp != 0u) {                                                   // PathTraceVJP: the caller's adjoint of the pixel, no loss
+        sane = job.drSkipNonFinite == 0u || __builtin_isfinite(accum.x + accum.y + accum.z);
+        seeded = job.adjImg != nullptr;
+        if (seeded) { const float* ap = job.adjImg + ((size_t)y * (uint)S.winWidth + x) * job.channels; seed = v3(ap[0], ap[1], ap[2]); }
+      } else {
+        const float* rp = job.refImg + ((size_t)((uint)S.winHeight - y - 1u) * (uint)S.winWidth + x) * job.channels;
+        const V3 diff = v3(accum.x - rp[0], accum.y - rp[1], accum.z - rp[2]);
+        sane = job.drSkipNonFinite == 0u || __builtin_isfinite(diff.x + diff.y + diff.z);   // (non-finite samples: see the megakernel)
+        if (sane) P.lossSlot[s] += (diff.x * diff.x + diff.y * diff.y + diff.z * diff.z) / float(job.passNum);
+        seed = v3(2.0f * diff.x, 2.0f * diff.y, 2.0f * diff.z);
+      }
+      if (sane) {
         float* o = job.outColor + ((size_t)y * (uint)S.winWidth + x) * job.channels;
         o[0] += accum.x; o[1] += accum.y; o[2] += accum.z;
-        closing = true; sweepBounce = bounce; sweepDiff = diff; sweepTail = tailR + env;
+        if (seeded) { closing = true; sweepBounce = bounce; sweepSeed = seed; sweepTail = tailR + env; }
       }
     } else if (finalize) {                                                   // kernel_ContributeToImage (integrator_pt.cpp:598-657)
       const uint pixel = ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
@@ -153,7 +162,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   }
 #ifndef HPT_DBG_DR_NOSWEEP   // diagnostic builds only (profiles/dr_ab.sh)
   if (DR && __any(closing))
-    drReverseSweep(S, job.record, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepTail, sweepDiff, job.grad, job.drSkipNonFinite != 0u,
+    drReverseSweep(S, job.record, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepTail, sweepSeed, job.grad, job.drSkipNonFinite != 0u,
                    drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, lastRec, lastInRegs, nullptr, 64u, false);
 #endif
   // ray compaction: ballot + prefix sum, one atomic per wave and queue

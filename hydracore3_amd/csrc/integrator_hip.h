@@ -6,7 +6,7 @@
 //                                  kernel_slicer-generated Integrator_Generated overrides (main.cpp:221-224) --
 //                                  PathTraceBlock, NaivePathTraceBlock, EvalGBuffer, CastSingleRayBlock, RayTraceBlock, PackXYBlock, CommitDeviceData,
 //                                  UpdateMembersPlainData, GetExecutionTime, Update_m_materials / Update_m_lights
-//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136): PutDiffTex2D, PathTraceDR, RayTraceDR
+//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136): PutDiffTex2D, PathTraceDR, PathTraceVJP, RayTraceDR
 //
 // The reference's headers cannot be included here (they need the absent LiteMath), so this header carries the same
 // member names over plain arrays; INTEGRATION.md shows the dozen lines that derive the real `Integrator` from it.
@@ -276,6 +276,16 @@ public:
     float loss = 0.0f;
     if (m_ctx) report(hpt_path_trace_dr(m_ctx, 0, tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize, &loss), "PathTraceDR");
     return loss;
+  }
+  // PathTraceVJP (no counterpart in the reference): PathTraceDR's paths, the reverse sweep seeded with a_adjImg = dL/d(out_color), rows in out_color's
+  // order; a_dataGrad is overwritten with the vector-Jacobian product (not divided by a_passNum). a_adjImg null: the frame only. Returns false on an error.
+  bool PathTraceVJP(uint32_t tid, uint32_t channels, float* out_color, uint32_t a_passNum,
+                    const float* a_adjImg, const float* a_data, float* a_dataGrad, size_t a_gradSize)
+  {
+    if (!m_ctx) return false;
+    const int rc = hpt_path_trace_vjp(m_ctx, 0, tid, channels, out_color, a_passNum, a_adjImg, a_data, a_dataGrad, a_gradSize);
+    report(rc, "PathTraceVJP");
+    return rc == HPT_OK;
   }
   // RayTraceDR (integrator_dr.h:39-40, integrator_dr.cpp:396-459; drmain.cpp:204): the noise-free pass - one pinhole ray per pixel, base colour x
   // texture, a_dataGrad overwritten; out_color is winWidth * winHeight * 4 floats (hits assigned, misses untouched). Returns the summed loss / a_passNum.

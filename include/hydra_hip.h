@@ -367,6 +367,24 @@ int  hpt_path_trace_dr(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint3
  * (divide by W*H for the reference's return value); dataGradDev is ACCUMULATED into (zero it yourself). Asynchronous. */
 int  hpt_path_trace_dr_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color_dev, uint32_t passNum,
                            const float* refImgDev, const float* dataDev, float* dataGradDev, size_t gradSize, float* lossAccumDev, void* stream);
+/* PathTraceVJP: the vector-Jacobian product of PathTraceDR's frame, for losses computed by the caller. No counterpart in the reference, whose
+ * PathTraceDR differentiates the per-sample squared difference to a_refImg only. The call traces PathTraceDR's paths - the same random numbers,
+ * records and colours, out_color accumulated and m_randomGens advanced bit for bit as by hpt_path_trace_dr - and seeds each sample's reverse
+ * sweep with the caller's adjoint of the sample's pixel, a = adjImg[(y * winWidth + x) * channels + 0..2], rows in out_color's order (NOT
+ * flipped as a_refImg is), instead of 2 (colour - ref):
+ *   dataGrad[j] = sum over pixels, samples s and c = 0..2 of a_c * d C_s[c] / d data[j],  C_s the sample's colour as it is added to out_color.
+ * Nothing is divided by passNum: it is the VJP of the frame as out_color receives it. An adjoint equal to 2 (colour - ref) gives PathTraceDR's
+ * gradient term for term. No loss is computed. adjImg NULL: the frame is rendered through the DR kernels and nothing else happens - no sweep,
+ * dataGrad (which may then be NULL) untouched. With hpt_set_option("dr_skip_nonfinite", 1) a sample whose colour is not finite adds neither
+ * colour nor gradient. Host-pointer form: dataGrad (gradSize floats) is zeroed and overwritten, out_color accumulated into.
+ * Refusals: PathTraceDR's, with its codes and messages (lens stack, motion, environment maps, non-lean materials, spectral mode, gradSize
+ * smaller than what is registered); channels other than 3 or 4 (the stride of both out_color and adjImg), a NULL out_color or data, and an
+ * adjImg with a NULL dataGrad or gradSize 0 are HPT_ERR_ARG. Runs under every schedule; hpt_get_execution_time("PathTraceVJP") gives its slots. */
+int  hpt_path_trace_vjp(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color, uint32_t passNum,
+                        const float* adjImg, const float* data, float* dataGrad, size_t gradSize);
+/* Device-pointer form: dataGradDev is ACCUMULATED into with float atomics (zero it yourself). Asynchronous on stream. */
+int  hpt_path_trace_vjp_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color_dev, uint32_t passNum,
+                            const float* adjImgDev, const float* dataDev, float* dataGradDev, size_t gradSize, void* stream);
 /* IntegratorDR::RayTraceDR(tid, channels, out_color, a_passNum, a_refImg, a_data, a_dataGrad, a_gradSize) (integrator_dr.h:39-40,
  * integrator_dr.cpp:168-273, 372-459; drmain.cpp:204): the differentiable form of CastSingleRayBlock. Per pixel of the first tid entries of
  * m_packedXY: the pinhole ray through the pixel centre, RayQuery_NearestHit (moving instances at time 0), colour = colors[GLTF_COLOR_BASE].w > 0 ?
