@@ -255,4 +255,16 @@ __global__ void __launch_bounds__(256) camInitGensKernel(Rng* gens, uint n);   /
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);
 
+// ---- helper kernels (hpt_helpers.hip) ---------------------------------------------------------------------------------------------------
+__global__ void packXYKernel(uint* out, int W, int H, uint ts);
+__global__ void initRandomGensKernel(Rng* gens, uint n, uint firstSeed);
+template <bool FLAT, bool MOTION, bool SWEEP>                           // batched RayQuery_NearestHit / RayQuery_AnyHit; `time` is read by the MOTION variants
+__global__ void __launch_bounds__(256) rayQueryKernel(const DevScene S, const float4* posNear, const float4* dirFar, uint n, void* out, int anyHit, uint* stackOverflow, float time);
+__global__ void image2D4fRegularizerKernel(int w, int h, const float4* data, float4* grad);
+__global__ void adamStepKernel(float* state, const float* grad, float* momentum, float* gsq, size_t n, float gamma);
+__global__ void refitTriBoxesKernel(const BvhTri* tris, const float* instMat, uint n, float* triBox);
+__global__ void refitLevelKernel(BvhNode* nodes, const uint* ids, uint count, const float* triBox, float* bounds);
+__global__ void refitNodes4Kernel(BvhNode4* nodes4, const uint* src, const BvhNode* nodes2, uint count);
+__global__ void buildShadeTrisKernel(const DevScene S, uint n, float4* out);
+
 } // namespace hpt

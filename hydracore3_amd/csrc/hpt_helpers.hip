@@ -1,6 +1,6 @@
-// Small helper kernels of the C ABI (compiled into the host translation unit): PackXY, InitRandomGens, batched ray queries,
-// the texture regulariser's gradient and AdamOptimizer::step. The path-tracing kernels themselves live in hpt_kernels.hip /
-// hpt_wavefront.hip and are compiled as separate translation units (hpt_decl.h declares them).
+// Small helper kernels of the C ABI: PackXY, InitRandomGens, batched ray queries, the texture regulariser's gradient, AdamOptimizer::step,
+// the device refit of the single-level BVH and the shading records. A translation unit of its own like every other kernel file
+// (hpt_decl.h declares the kernels; hpt_host.hip launches them).
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 
@@ -29,8 +29,8 @@ __global__ void initRandomGensKernel(Rng* gens, uint n, uint firstSeed)
 }
 
 // batched RayQuery_NearestHit / RayQuery_AnyHit for the ISceneObject entry points
-template <bool FLAT, bool MOTION = false, bool SWEEP = false>
-__global__ void __launch_bounds__(256) rayQueryKernel(const DevScene S, const float4* posNear, const float4* dirFar, uint n, void* out, int anyHit, uint* stackOverflow, float time = 0.0f)
+template <bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256) rayQueryKernel(const DevScene S, const float4* posNear, const float4* dirFar, uint n, void* out, int anyHit, uint* stackOverflow, float time)
 {
   __shared__ uint stackMem[LDS_STACK * 256];
   const uint i = blockIdx.x * 256u + threadIdx.x;
@@ -54,6 +54,13 @@ __global__ void __launch_bounds__(256) rayQueryKernel(const DevScene S, const fl
     }
   }
 }
+
+#define HPT_RQ_INST(FLAT, MOTION, SWEEP) template __global__ void rayQueryKernel<FLAT, MOTION, SWEEP>(const DevScene, const float4*, const float4*, uint, void*, int, uint*, float);
+HPT_RQ_INST(false, false, true)     // the traversal variants traversalDispatch() picks (hpt_host.hip): sweep, single-level with motion, single-level,
+HPT_RQ_INST(true, true, false)      // two-level with motion, two-level
+HPT_RQ_INST(true, false, false)
+HPT_RQ_INST(false, true, false)
+HPT_RQ_INST(false, false, false)
 
 // Image2D4fRegularizer (diff_render/integrator_dr.cpp:317-367): grad += d/d data of  sum_{interior pixels} sqrt(sum_{4 neighbours} |p0 - p_k|^2_rgb).
 // Hand-derived instead of Enzyme, gather form (no atomics): texel q receives its own term (4 q - sum nb)/sqrt(S_q) when it is interior,

@@ -1,5 +1,5 @@
 // Host side of the C ABI (include/hydra_hip.h): context, BVH2 build + upload, scene tables, launches, timing.
-// Compiled by hipcc together with the kernels; exports only the extern "C" hpt_* symbols.
+// Compiled by hipcc and linked with the kernel units; exports only the extern "C" hpt_* symbols.
 #include "plastic_precompute.h"
 #include "film_precompute.h"
 #include "jpeg_decode.h"
@@ -23,7 +23,6 @@
 
 #include "../../include/hydra_hip.h"
 #include "hpt_decl.h"
-#include "hpt_helpers.hip"
 #include "bvh_build.h"
 #include "hpt_lbvh.h"
 
@@ -59,7 +58,9 @@ static const size_t SWEEP_MAX_TRIS = 32, SWEEP_MAX_INSTS = 8;
 #endif
 static const size_t MANY_INSTANCES = 6;                      // instances from which the single-level layout is chosen for light scenes too (see hpt_commit_scene)
 
-namespace {
+// What the sections of this file share besides the context: kept in a hidden namespace, so that none of it becomes a dynamic export when the
+// sections are compiled as units of their own (tests/test_cpu.py: test_library_exports_every_declared_symbol)
+namespace hpt { namespace host __attribute__((visibility("hidden"))) {
 
 struct Geom
 {
@@ -73,7 +74,7 @@ struct Geom
 struct Inst { uint geomId; float m[16]; bool motion = false; float m1[16] = {0}; };   // m1: the matrix at time 1 of a moving instance (AddInstanceMotion)
 
 template <class T>
-struct DevBuf                      // owning device array; freed on scope exit (locals on error paths) or by hpt_destroy (context members)
+struct DevBuf                      // owning device array; freed on scope exit (locals on error paths) or with its owner (the context, a wavefront group, a camera)
 {
   T* p = nullptr; size_t n = 0;
   DevBuf() = default;
@@ -91,7 +92,10 @@ struct DevBuf                      // owning device array; freed on scope exit (
 
 double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
-} // namespace
+} } // namespace hpt::host
+using namespace hpt::host;
+
+enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
 
 struct hpt_ctx
 {
@@ -159,6 +163,14 @@ struct hpt_ctx
     hipStream_t stream = nullptr; hipEvent_t ev[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr}; hipEvent_t done = nullptr;
     uint* progress = nullptr;            // pinned: rays queued after every WF_CHECK-th shade pass (0 = group finished)
     uint checkpoints = 0, itemBase = 0, itemCount = 0; unsigned long long it = 0; bool finished = false;
+    WfGroup() = default; WfGroup(const WfGroup&) = delete;
+    ~WfGroup()
+    {
+      if (progress) (void)hipHostFree(progress);
+      for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e);
+      if (done) (void)hipEventDestroy(done);
+      if (stream) (void)hipStreamDestroy(stream);
+    }
   };
   std::vector<WfGroup*> wfGroups;
   hipEvent_t wfFork = nullptr;
@@ -193,11 +205,17 @@ struct hpt_ctx
   bool instrument = false;
   uint64_t gradSize = 0;
 
-  // GetExecutionTime slots
-  float tPathTrace[4] = {0, 0, 0, 0}, tNaive[4] = {0, 0, 0, 0}, tDR[4] = {0, 0, 0, 0}, tFromRays[4] = {0, 0, 0, 0};
-  float tCastSingleRay[4] = {0, 0, 0, 0}, tRayTrace[4] = {0, 0, 0, 0}, tPathTraceQmc[4] = {0, 0, 0, 0}, tRayTraceDR[4] = {0, 0, 0, 0}, tVJP[4] = {0, 0, 0, 0};
+  float tSlots[T_SLOT_COUNT][4] = {};   // GetExecutionTime slots: kernel, copy in, copy out, overhead (ms) per TimeSlot
   float lastKernelMs = 0.0f;
 
+  hpt_ctx() = default; hpt_ctx(const hpt_ctx&) = delete;
+  ~hpt_ctx()                             // what the context owns that is not a DevBuf (hpt_destroy has set the device and waited for it)
+  {
+    lbvhDestroy(lbvh);
+    for (WfGroup* g : wfGroups) delete g;
+    for (void* p : texData) if (p) (void)hipFree(p);
+    for (hipEvent_t e : { ev0, ev1, wfFork }) if (e) (void)hipEventDestroy(e);
+  }
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
   int hipFail(hipError_t e, const char* what) { return fail(HPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
 };
@@ -255,27 +273,7 @@ try {
   (void)hipSetDevice(c->device);
   (void)hipDeviceSynchronize();
   (void)hpt_comm_destroy(c);
-  lbvhDestroy(c->lbvh); c->lbvh = nullptr;
-  c->dNodes.release(); c->dTris.release(); c->dInsts.release(); c->dSweepInsts.release(); c->dSweepTris.release(); c->dSweepBoxes.release(); c->dSweepPlanes.release(); c->dSweepPairBoxes.release(); c->dLevelNodes.release(); c->dShadeTris.release(); c->dNodes4.release(); c->dNodes4Src.release(); c->dTriBox.release(); c->dNodeBounds.release(); c->dInstO2W.release(); c->dTriIndices.release(); c->dMatIdByPrim.release();
-  c->dMatVertOffset.release(); c->dPackedXY.release(); c->dVData.release(); c->dNormMat.release(); c->dRemapInst.release();
-  c->dRemapLists.release(); c->dMaterials.release(); c->dLights.release(); c->dTextures.release(); c->dArrays1f.release(); c->dSpecValues.release(); c->dSpecOffsetSz.release(); c->dCieXYZ.release(); c->dFilmsEtaK.release(); c->dPrecompFilms.release(); c->dFilmsSpecId.release(); c->dSpecTexIdsWavelengths.release(); c->dSpecTexOffsetSz.release(); c->dGens.release(); c->dQmcTable.release();
-  c->dQueue.release(); c->dStackOvf.release(); c->dCounters.release(); c->dFrame.release(); c->dRecord.release(); c->dRef.release(); c->dData.release();
-  c->dGrad.release(); c->dLoss.release(); c->dLossAcc.release();
-  for (hpt_ctx::WfGroup* g : c->wfGroups) {
-    for (auto& b : g->f4) b.release();
-    for (auto& b : g->u) b.release();
-    g->rec.release(); g->lossSlot.release(); g->time.release();
-    if (g->progress) (void)hipHostFree(g->progress);
-    for (auto& e : g->ev) if (e) (void)hipEventDestroy(e);
-    if (g->done) (void)hipEventDestroy(g->done);
-    if (g->stream) (void)hipStreamDestroy(g->stream);
-    delete g;
-  }
-  if (c->wfFork) (void)hipEventDestroy(c->wfFork);
-  for (void* p : c->texData) if (p) (void)hipFree(p);
-  if (c->ev0) (void)hipEventDestroy(c->ev0);
-  if (c->ev1) (void)hipEventDestroy(c->ev1);
-  delete c;
+  delete c;                                                    // (~hpt_ctx and its members free what the context owns)
 }
 catch (...) { (void)hptGuard(c, "hpt_destroy"); }
 
@@ -636,8 +634,6 @@ static int refit_flat(hpt_ctx* c)
   return HPT_OK;
 }
 
-static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0);
-
 extern "C" int hpt_commit_scene(hpt_ctx* c, uint32_t options)
 try {
   if (!c) return HPT_ERR_ARG;
@@ -976,6 +972,19 @@ static void traversalDispatch(const hpt_ctx* c, F f)
   else                                    f(N, N, N);
 }
 
+// The frame of a launch of `lanes` lanes on `st`: size the HBM part of the traversal stacks, record ev0, launch(), check, record ev1. Whatever
+// reads c->dStackOvf.p (a kernel argument, Job::stackOverflow) belongs into launch(). EVENTS = false: the same without the event pair.
+template <bool EVENTS = true, class Launch>
+static int launchFrame(hpt_ctx* c, size_t lanes, hipStream_t st, Launch launch)
+{
+  HIPCHK(c, ensureStackOverflow(c, lanes));
+  if (EVENTS) HIPCHK(c, hipEventRecord(c->ev0, st));
+  launch();
+  HIPCHK(c, hipGetLastError());
+  if (EVENTS) HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+
 static int ray_query(hpt_ctx* c, const float* posNear, const float* dirFar, uint32_t n, void* out, int any, float time = 0.0f)
 {
   if (!c || !posNear || !dirFar || !out) return HPT_ERR_ARG;
@@ -988,11 +997,11 @@ static int ray_query(hpt_ctx* c, const float* posNear, const float* dirFar, uint
   HIPCHK(c, dd.upload((const float4*)dirFar, n));
   HIPCHK(c, dout.alloc(outWords));
   const uint blocks = (n + 255) / 256;
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {           // the time goes to the motion variants only
-    rayQueryKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p, motion() ? time : 0.0f);
-  });
-  HIPCHK(c, hipGetLastError());
+  if (int rc = launchFrame<false>(c, (size_t)blocks * 256, nullptr, [&]() {
+    traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {         // the time goes to the motion variants only
+      rayQueryKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, 0>>>(c->S, dp.p, dd.p, n, dout.p, any, c->dStackOvf.p, motion() ? time : 0.0f);
+    });
+  })) return rc;
   HIPCHK(c, hipMemcpy(out, dout.p, outWords * 4, hipMemcpyDeviceToHost));
   return HPT_OK;
 }
@@ -1366,7 +1375,7 @@ try {
   // a new scene invalidates the environment ids of the previous UpdateMembersPlainData until the next one
   S.envTexId = S.envLightId = S.envCamBackId = 0xFFFFFFFFu; S.envEnableSam = 0;
   c->sceneUploaded = true; c->shadeTrisDirty = true;
-  c->tPathTrace[1] = c->tNaive[1] = c->tDR[1] = float(now_ms() - t0);   // host -> device time of the scene commit
+  c->tSlots[T_PATH_TRACE][1] = c->tSlots[T_NAIVE][1] = c->tSlots[T_DR][1] = float(now_ms() - t0);   // host -> device time of the scene commit
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_upload_scene"); }
@@ -1546,11 +1555,6 @@ static int gridBlocks(hpt_ctx* c, bool dr, bool fullMaterials = false)
   return c->numCUs * bpc;
 }
 
-static bool useWavefront(hpt_ctx* c, bool naive, bool dr, bool stats, uint tidCount);
-static bool wfWide(const hpt_ctx* c);
-static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1);
-static int launch_stream(hpt_ctx* c, const Job& job, hipStream_t st);
-
 // DEEP: the scene's BVH can need more than LDS_STACK stack entries, so pushes / pops check for the HBM overflow part
 // FLAT: single-level world-space BVH (static scenes within FLAT_TRI_BUDGET) vs two-level TLAS/BLAS
 template <bool STATS, bool DR, int NAIVE>
@@ -1629,180 +1633,6 @@ static int ensureShadeTris(hpt_ctx* c, hipStream_t st)
   return HPT_OK;
 }
 
-static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st)
-{
-  const bool inRays = job.inRayPos != nullptr;
-  if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before CommitDeviceData / UpdateMembersPlainData");
-  if (!inRays && c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlock before PackXYBlock");
-  job.tidStride = c->tidStride > 1 ? c->tidStride : 1u;
-  job.tidChunk = (job.tidStride > 1 && c->tidChunk > 0) ? c->tidChunk : 0x40000000u;
-  job.tidEnd = inRays ? job.tidBegin + job.tidCount : c->packedCount;
-  if (inRays) { job.tidStride = 1; job.tidChunk = 0x40000000u; }
-  if (!inRays && job.tidStride == 1 && (size_t)job.tidBegin + job.tidCount > c->packedCount) return c->fail(HPT_ERR_ARG, "PathTraceBlock: tid range exceeds the viewport");
-  if (c->dGens.n < (inRays ? (size_t)job.tidEnd : (size_t)c->packedCount)) return c->fail(HPT_ERR_STATE, "PathTraceBlock: m_randomGens smaller than the thread range (InitRandomGens)");
-  if (job.channels < 1 || (job.channels > 4 && c->S.spectralMode == 0u)) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlock: channels must be 1..4 (more are the wavelength layers of spectral rendering)");
-  // two channels: kernel_ContributeToImage writes three components at pixel * channels (integrator_pt.cpp:636-641), i.e. into the next pixel and,
-  // for the last one, past the buffer - refused rather than restated
-  if (job.channels == 2) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlock: a two-channel framebuffer cannot hold the three components written per pixel (1, 3 or 4 channels)");
-  if (dr && (c->S.traceDepth == 0 || c->S.traceDepth > 16)) return c->fail(HPT_ERR_ARG, "PathTraceDR: trace depth must be 1..16");
-  if (dr && c->S.lensCount) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the lens simulation is not differentiated");
-  if (dr && c->S.motion) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: motion blur is not differentiated");
-  // the DR kernels add the constant m_envColor unweighted; the reference's replay evaluates EnvironmentColor() with the map and the
-  // env-sampling MIS weight (integrator_dr.cpp:1077-1098): such scenes are refused rather than differentiated differently
-  if (dr && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u || c->S.envCamBackId != 0xFFFFFFFFu))
-    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: environment maps, their sampling and camera back plates are not differentiated (constant m_envColor only)");
-  if (dr && !c->leanMaterials) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: gltf and emissive materials without normal maps only (what the reference's replay differentiates, integrator_dr.cpp:461-612)");
-  // never more lanes than pixels: with fewer, the hardware's round-robin block placement spreads them evenly over the CUs, whereas a
-  // full grid would let whichever waves ask first take all the work (a small multi-GPU share of a frame)
-  if (c->S.spectralMode != 0u) {                               // four wavelengths per path: its own (plain) kernel
-    if (dr) return c->fail(HPT_ERR_UNSUPPORTED, "spectral rendering: not the differentiable integrator");
-    if (inRays && job.channels != 1u && job.channels != 4u) return c->fail(HPT_ERR_ARG, "PathTraceFromInputRays in spectral mode: 1 or 4 channels (kernel_CopyColorToOutput)");
-    job.naive = naive ? 1u : 0u;
-    if (c->hasFilm && !c->filmTablesSpectral) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)");
-    job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
-    // the scope the scene needs (hpt_spectral.hip: SCOPE): the narrowest instantiations that hold it
-    bool heavy = c->S.lensCount != 0u || c->S.envTexId != 0xFFFFFFFFu || c->S.envCamBackId != 0xFFFFFFFFu || c->spectralHeavyMats;
-    for (const uint g : c->hLightGeom) heavy = heavy || g == LIGHT_GEOM_ENV;
-    const int scope = (heavy && c->fewMaterialTypes) ? 3 : (heavy ? 2 : (c->spectralGltfMats ? 1 : 0));
-    // Schedule: scenes whose rays walk a real tree (SAH estimate >= 8: the reference's spectral fixture, interiors) run the block-local kernel -
-    // persistent blocks on the work queue, rays repacked per block, the 4-wide tree on heavy scenes; the others, input-ray batches, moving
-    // instances and sweep scenes keep the one-thread-per-pixel kernel. hpt_set_schedule(1) / (3) force either.
-    const bool specBlock = !inRays && c->S.motion == 0u && c->S.sweep == 0u && (c->S.traceDepth > 0u || naive) &&
-                           (c->schedule == 3 || (c->schedule == 0 && c->sahVisits >= BLOCK_SAH_VISITS));
-    // ... and heavy scenes in calls with enough pixels the wavefront schedule (wfShadeSpecKernel + the shared trace kernel), as their RGB rendering does
-    const bool specWave = !inRays && !naive && c->S.motion == 0u && c->S.sweep == 0u && c->S.traceDepth > 0u && !c->instrument &&
-                          (c->schedule == 2 || (c->schedule == 0 && c->sahVisits >= HEAVY_SAH_VISITS && job.tidCount >= WF_AUTO_PIXELS));
-    if (specWave) {
-      c->lastSchedule = 2; c->lastWide = wfWide(c) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u; c->lastShadeRecords = 0u;
-      return launch_wavefront(c, job, st, false, scope == 0 ? 1 : scope);
-    }
-    if (specBlock) {
-      const bool bwide = c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u;
-      const bool bdeep = (bwide ? std::max(c->stackNeeded, c->stackNeeded4) : c->stackNeeded) > (uint)LDS_STACK;
-      const int bpc = c->blocksPerCU > 0 ? c->blocksPerCU : (scope == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES);
-      const int blocks = (int)std::min<size_t>((size_t)c->numCUs * bpc, ((size_t)job.tidCount + 255) / 256);
-      HIPCHK(c, c->dQueue.alloc(1));
-      HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
-      job.queue = c->dQueue.p;
-      HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-      job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
-      const uint bNodeMin = bwide ? std::max(c->bwNodeMin, 16u) : c->bwNodeMin;
-      c->lastSchedule = 3; c->lastWide = bwide ? 1u : 0u; c->lastDeep = bdeep ? 1u : 0u; c->lastShadeRecords = 0u;
-      HIPCHK(c, hipEventRecord(c->ev0, st));
-      if (scope == 3) launchSpectralBlock<3>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
-      else if (scope == 2) launchSpectralBlock<2>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
-      else if (scope == 1) launchSpectralBlock<1>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
-      else launchSpectralBlock<0>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
-      HIPCHK(c, hipGetLastError());
-      HIPCHK(c, hipEventRecord(c->ev1, st));
-      return HPT_OK;
-    }
-    const int sblocks = (int)(((size_t)job.tidCount + 255) / 256);
-    HIPCHK(c, ensureStackOverflow(c, (size_t)sblocks * 256));
-    job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)sblocks * 256u;
-    const bool sdeep = megaStackNeeded(c) > (uint)LDS_STACK;
-    c->lastSchedule = 1; c->lastWide = (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u; c->lastDeep = sdeep ? 1u : 0u; c->lastShadeRecords = 0u;
-    HIPCHK(c, hipEventRecord(c->ev0, st));
-    if (scope == 3) launchSpectral<3>(c->S, job, sblocks, st, sdeep);
-    else if (scope == 2) launchSpectral<2>(c->S, job, sblocks, st, sdeep); else if (scope == 1) launchSpectral<1>(c->S, job, sblocks, st, sdeep); else launchSpectral<0>(c->S, job, sblocks, st, sdeep);
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipEventRecord(c->ev1, st));
-    return HPT_OK;
-  }
-  { const int rcS = ensureShadeTris(c, st); if (rcS != HPT_OK) return rcS; }
-  const bool motion = c->S.motion != 0;
-  const bool film = c->hasFilm;                                // MODE 4 / 5 / 6 kernels, wfShadeKernel<.., FILM>
-  if (film && !c->filmTablesRGB) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)");
-  if (film && c->instrument && !dr) return c->fail(HPT_ERR_UNSUPPORTED, "thin films: the instrumented probe has no film variant");
-  const bool fullMaterials = film || motion || !dr && !(c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && !naive && !inRays && !(c->instrument && !dr));   // MODE 0 / 1 / 2 / STATS kernels
-  // MODE 7: the kernel with every BSDF branch built for one more wave per SIMD, for scenes with few material types (hpt_decl.h)
-  const bool mode7 = fullMaterials && c->fewMaterialTypes && !c->forceFull && !film && !motion && !dr && !inRays && !naive && !(c->instrument && !dr);
-  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, dr, fullMaterials && !mode7), ((size_t)job.tidCount + 255) / 256);
-  HIPCHK(c, c->dQueue.alloc(1));
-  HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
-  job.queue = c->dQueue.p;
-  job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
-  job.counters = nullptr;
-  job.drSkipNonFinite = c->drSkipNonFinite ? 1u : 0u;
-  const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
-  c->lastSchedule = 1;
-  c->lastShadeRecords = c->S.shadeTris != nullptr ? 1u : 0u;
-  // schedule 4 (experimental, never chosen automatically): the block-owned streaming form of the wavefront schedule - heavy static scenes with gltf / emissive materials
-  if (c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u) {
-    c->lastSchedule = 4; c->lastWide = 1u; c->lastDeep = c->stackNeeded4 > (uint)LDS_STACK ? 1u : 0u;
-    return launch_stream(c, job, st);
-  }
-  if (!inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount)) {
-    c->lastSchedule = 2; c->lastWide = (wfWide(c) && !c->instrument) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
-    return launch_wavefront(c, job, st, dr);
-  }
-  c->lastWide = (!stats && !motion && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
-  c->lastDeep = megaStackNeeded(c) > (uint)LDS_STACK ? 1u : 0u;
-  if (stats) { HIPCHK(c, c->dCounters.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dCounters.p, 0, sizeof(Counters), st)); job.counters = c->dCounters.p; }
-  if (dr) {
-    job.recordLanes = (uint)blocks * 256u;
-    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1)));
-    job.record = c->dRecord.p;
-  }
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-  job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
-  // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
-  // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
-  // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
-  // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
-  const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
-  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
-  const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
-  if (blockLocal) {
-    const bool lean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
-    const bool bwide = lean && (c->bwWide == 1 || (c->bwWide < 0 && c->S.megaWide != 0u)) && c->S.flatMode != 0u && c->nodes4Count != 0u && c->wideEnabled;      // heavy scenes: the 4-wide compressed tree, as the megakernel walks it
-    const bool bdeep = (bwide ? std::max(c->stackNeeded, c->stackNeeded4) : c->stackNeeded) > (uint)LDS_STACK;
-    const uint bNodeMin = bwide ? std::max(c->bwNodeMin, 16u) : c->bwNodeMin;                           // (a 4-wide visit is three times the work: the vote pays earlier)
-    c->lastSchedule = 3; c->lastWide = bwide ? 1u : 0u; c->lastDeep = bdeep ? 1u : 0u;
-    if (dr && job.vjp != 0u) launchBlock<true, true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);   // (a template parameter in this kernel: hpt_decl.h)
-    else if (dr) launchBlock<true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
-    else if (lean) launchBlock<false, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
-    else launchBlock<false, false>(c->S, job, std::min(blocks, c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : HPT_BW_FULL_WAVES)), st, bdeep, c->bwRefillBelow, c->bwNodeMin);
-  }
-  else if (motion && film) {
-    if (inRays) launchPTMotion<6>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<5>(c->S, job, blocks, st, deep); else launchPTMotion<4>(c->S, job, blocks, st, deep);
-  }
-  else if (motion) {
-    if (inRays) launchPTMotion<2>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<1>(c->S, job, blocks, st, deep); else launchPTMotion<0>(c->S, job, blocks, st, deep);
-  }
-  else if (dr) {
-    // the DR kernel's waves are emptier than the forward kernel's (lane utilisation 0.25), so leaving the inner-node loop when fewer than four
-    // lanes still walk pays even on light scenes: test_228 class 346 -> 364 Mpaths/s (forward: 698 -> 699; profiles/vote_medium.sh)
-    DevScene Sd = c->S;
-    if (c->nodeMinOverride < 0 && Sd.nodeMin < 4u) Sd.nodeMin = 4u;
-    if (stats) {                                                 // the counting probe follows the walk an uninstrumented call would do (see the forward probe below)
-      Sd.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;
-      launchPT<true, true, 0>(Sd, job, blocks, st, deep || (Sd.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
-    } else launchPT<false, true, 0>(Sd, job, blocks, st, deep);
-  }
-  else if (film) {
-    if (inRays) launchPT<false, false, 6>(c->S, job, blocks, st, deep); else if (naive) launchPT<false, false, 5>(c->S, job, blocks, st, deep); else launchPT<false, false, 4>(c->S, job, blocks, st, deep);
-  }
-  else if (inRays) launchPT<false, false, 2>(c->S, job, blocks, st, deep);
-  else if (naive)  launchPT<false, false, 1>(c->S, job, blocks, st, deep);
-  else if (stats) {
-    // the counting probe follows the walk an uninstrumented call would do: where that is the wavefront trace kernel on the 4-wide tree, the
-    // probe's single-level traversal walks that tree too (node visits = 64-byte lines of the tree actually used)
-    DevScene Sp = c->S;
-    Sp.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;   // "stats_wide": the caller says the measured call ran there
-    launchPT<true, false, 0>(Sp, job, blocks, st, deep || (Sp.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
-  }
-  else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) launchPT<false, false, 3>(c->S, job, blocks, st, deep);
-  else if (mode7)  launchPT<false, false, 7>(c->S, job, blocks, st, deep);
-  else             launchPT<false, false, 0>(c->S, job, blocks, st, deep);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  return HPT_OK;
-}
-
-
 // ---- wavefront schedule ---------------------------------------------------------------------------------------------------------------
 // Heavy scenes (HEAVY_SAH_VISITS) are rendered by the shade / trace kernel pair; on light ones the path state's trip through HBM costs more
 // than the ray replacement gains (measured crossover: see DESIGN.md, "two schedules").
@@ -1853,7 +1683,7 @@ static void launchWfTrace(hpt_ctx* c, const DevScene& S, const WfPool& P, uint i
   }
 }
 
-static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
+static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
 {
   const bool spec = specScope >= 0;
   DevScene Sw = c->S;
@@ -2020,7 +1850,6 @@ static int launch_stream(hpt_ctx* c, const Job& job, hipStream_t st)
   for (int i = 0; i < 3; i++) HIPCHK(c, g.u[i].alloc(n));
   HIPCHK(c, g.u[6].alloc(n));
   HIPCHK(c, g.u[3].alloc((size_t)blocks * 2u * spb));            // the blocks' ray queues
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
   WfPool P; std::memset(&P, 0, sizeof(P));
   P.rayO = g.f4[0].p; P.rayD = g.f4[1].p; P.thr = g.f4[2].p; P.acc = g.f4[3].p;
   P.shO = g.f4[4].p; P.shD = g.f4[5].p; P.contrib = g.f4[6].p; P.hit = g.f4[7].p;
@@ -2028,14 +1857,177 @@ static int launch_stream(hpt_ctx* c, const Job& job, hipStream_t st)
   WfJob wj; std::memset(&wj, 0, sizeof(wj));
   wj.itemBase = 0; wj.itemCount = n; wj.tidBegin = job.tidBegin; wj.tidChunk = job.tidChunk; wj.tidStride = job.tidStride; wj.tidEnd = job.tidEnd;
   wj.passNum = job.passNum; wj.channels = job.channels; wj.outColor = job.outColor; wj.gens = job.gens; wj.packedXY = job.packedXY;
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  wfInitKernel<<<dim3((n + 255u) / 256u), dim3(256), 0, st>>>(P, n, job.passNum);
-  if (c->stackNeeded4 > (uint)LDS_STACK) streamKernel<true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, P, wj, spb, c->wfRefillBelow, g.u[3].p, c->dStackOvf.p, blocks * 256u);
-  else                                   streamKernel<false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, P, wj, spb, c->wfRefillBelow, g.u[3].p, c->dStackOvf.p, blocks * 256u);
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  c->lastWfIters = 0;
-  return HPT_OK;
+  const int rc = launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    wfInitKernel<<<dim3((n + 255u) / 256u), dim3(256), 0, st>>>(P, n, job.passNum);
+    if (c->stackNeeded4 > (uint)LDS_STACK) streamKernel<true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, P, wj, spb, c->wfRefillBelow, g.u[3].p, c->dStackOvf.p, blocks * 256u);
+    else                                   streamKernel<false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, P, wj, spb, c->wfRefillBelow, g.u[3].p, c->dStackOvf.p, blocks * 256u);
+  });
+  if (rc == HPT_OK) c->lastWfIters = 0;
+  return rc;
+}
+
+static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st)
+{
+  const bool inRays = job.inRayPos != nullptr;
+  if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before CommitDeviceData / UpdateMembersPlainData");
+  if (!inRays && c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlock before PackXYBlock");
+  job.tidStride = c->tidStride > 1 ? c->tidStride : 1u;
+  job.tidChunk = (job.tidStride > 1 && c->tidChunk > 0) ? c->tidChunk : 0x40000000u;
+  job.tidEnd = inRays ? job.tidBegin + job.tidCount : c->packedCount;
+  if (inRays) { job.tidStride = 1; job.tidChunk = 0x40000000u; }
+  if (!inRays && job.tidStride == 1 && (size_t)job.tidBegin + job.tidCount > c->packedCount) return c->fail(HPT_ERR_ARG, "PathTraceBlock: tid range exceeds the viewport");
+  if (c->dGens.n < (inRays ? (size_t)job.tidEnd : (size_t)c->packedCount)) return c->fail(HPT_ERR_STATE, "PathTraceBlock: m_randomGens smaller than the thread range (InitRandomGens)");
+  if (job.channels < 1 || (job.channels > 4 && c->S.spectralMode == 0u)) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlock: channels must be 1..4 (more are the wavelength layers of spectral rendering)");
+  // two channels: kernel_ContributeToImage writes three components at pixel * channels (integrator_pt.cpp:636-641), i.e. into the next pixel and,
+  // for the last one, past the buffer - refused rather than restated
+  if (job.channels == 2) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlock: a two-channel framebuffer cannot hold the three components written per pixel (1, 3 or 4 channels)");
+  if (dr && (c->S.traceDepth == 0 || c->S.traceDepth > 16)) return c->fail(HPT_ERR_ARG, "PathTraceDR: trace depth must be 1..16");
+  if (dr && c->S.lensCount) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the lens simulation is not differentiated");
+  if (dr && c->S.motion) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: motion blur is not differentiated");
+  // the DR kernels add the constant m_envColor unweighted; the reference's replay evaluates EnvironmentColor() with the map and the
+  // env-sampling MIS weight (integrator_dr.cpp:1077-1098): such scenes are refused rather than differentiated differently
+  if (dr && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u || c->S.envCamBackId != 0xFFFFFFFFu))
+    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: environment maps, their sampling and camera back plates are not differentiated (constant m_envColor only)");
+  if (dr && !c->leanMaterials) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: gltf and emissive materials without normal maps only (what the reference's replay differentiates, integrator_dr.cpp:461-612)");
+  // never more lanes than pixels: with fewer, the hardware's round-robin block placement spreads them evenly over the CUs, whereas a
+  // full grid would let whichever waves ask first take all the work (a small multi-GPU share of a frame)
+  if (c->S.spectralMode != 0u) {                               // four wavelengths per path: its own (plain) kernel
+    if (dr) return c->fail(HPT_ERR_UNSUPPORTED, "spectral rendering: not the differentiable integrator");
+    if (inRays && job.channels != 1u && job.channels != 4u) return c->fail(HPT_ERR_ARG, "PathTraceFromInputRays in spectral mode: 1 or 4 channels (kernel_CopyColorToOutput)");
+    job.naive = naive ? 1u : 0u;
+    if (c->hasFilm && !c->filmTablesSpectral) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)");
+    job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+    // the scope the scene needs (hpt_spectral.hip: SCOPE): the narrowest instantiations that hold it
+    bool heavy = c->S.lensCount != 0u || c->S.envTexId != 0xFFFFFFFFu || c->S.envCamBackId != 0xFFFFFFFFu || c->spectralHeavyMats;
+    for (const uint g : c->hLightGeom) heavy = heavy || g == LIGHT_GEOM_ENV;
+    const int scope = (heavy && c->fewMaterialTypes) ? 3 : (heavy ? 2 : (c->spectralGltfMats ? 1 : 0));
+    // Schedule: scenes whose rays walk a real tree (SAH estimate >= 8: the reference's spectral fixture, interiors) run the block-local kernel -
+    // persistent blocks on the work queue, rays repacked per block, the 4-wide tree on heavy scenes; the others, input-ray batches, moving
+    // instances and sweep scenes keep the one-thread-per-pixel kernel. hpt_set_schedule(1) / (3) force either.
+    const bool specBlock = !inRays && c->S.motion == 0u && c->S.sweep == 0u && (c->S.traceDepth > 0u || naive) &&
+                           (c->schedule == 3 || (c->schedule == 0 && c->sahVisits >= BLOCK_SAH_VISITS));
+    // ... and heavy scenes in calls with enough pixels the wavefront schedule (wfShadeSpecKernel + the shared trace kernel), as their RGB rendering does
+    const bool specWave = !inRays && !naive && c->S.motion == 0u && c->S.sweep == 0u && c->S.traceDepth > 0u && !c->instrument &&
+                          (c->schedule == 2 || (c->schedule == 0 && c->sahVisits >= HEAVY_SAH_VISITS && job.tidCount >= WF_AUTO_PIXELS));
+    if (specWave) {
+      c->lastSchedule = 2; c->lastWide = wfWide(c) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u; c->lastShadeRecords = 0u;
+      return launch_wavefront(c, job, st, false, scope == 0 ? 1 : scope);
+    }
+    if (specBlock) {
+      const bool bwide = c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u;
+      const bool bdeep = (bwide ? std::max(c->stackNeeded, c->stackNeeded4) : c->stackNeeded) > (uint)LDS_STACK;
+      const int bpc = c->blocksPerCU > 0 ? c->blocksPerCU : (scope == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES);
+      const int blocks = (int)std::min<size_t>((size_t)c->numCUs * bpc, ((size_t)job.tidCount + 255) / 256);
+      HIPCHK(c, c->dQueue.alloc(1));
+      HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
+      job.queue = c->dQueue.p;
+      const uint bNodeMin = bwide ? std::max(c->bwNodeMin, 16u) : c->bwNodeMin;
+      return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+        c->lastSchedule = 3; c->lastWide = bwide ? 1u : 0u; c->lastDeep = bdeep ? 1u : 0u; c->lastShadeRecords = 0u;
+        job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
+        if (scope == 3) launchSpectralBlock<3>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
+        else if (scope == 2) launchSpectralBlock<2>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
+        else if (scope == 1) launchSpectralBlock<1>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
+        else launchSpectralBlock<0>(c->S, job, blocks, st, bdeep, bwide, c->bwRefillBelow, bNodeMin);
+      });
+    }
+    const int sblocks = (int)(((size_t)job.tidCount + 255) / 256);
+    const bool sdeep = megaStackNeeded(c) > (uint)LDS_STACK;
+    return launchFrame(c, (size_t)sblocks * 256, st, [&]() {
+      c->lastSchedule = 1; c->lastWide = (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u; c->lastDeep = sdeep ? 1u : 0u; c->lastShadeRecords = 0u;
+      job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)sblocks * 256u;
+      if (scope == 3) launchSpectral<3>(c->S, job, sblocks, st, sdeep);
+      else if (scope == 2) launchSpectral<2>(c->S, job, sblocks, st, sdeep); else if (scope == 1) launchSpectral<1>(c->S, job, sblocks, st, sdeep); else launchSpectral<0>(c->S, job, sblocks, st, sdeep);
+    });
+  }
+  { const int rcS = ensureShadeTris(c, st); if (rcS != HPT_OK) return rcS; }
+  const bool motion = c->S.motion != 0;
+  const bool film = c->hasFilm;                                // MODE 4 / 5 / 6 kernels, wfShadeKernel<.., FILM>
+  if (film && !c->filmTablesRGB) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)");
+  if (film && c->instrument && !dr) return c->fail(HPT_ERR_UNSUPPORTED, "thin films: the instrumented probe has no film variant");
+  const bool fullMaterials = film || motion || !dr && !(c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && !naive && !inRays && !(c->instrument && !dr));   // MODE 0 / 1 / 2 / STATS kernels
+  // MODE 7: the kernel with every BSDF branch built for one more wave per SIMD, for scenes with few material types (hpt_decl.h)
+  const bool mode7 = fullMaterials && c->fewMaterialTypes && !c->forceFull && !film && !motion && !dr && !inRays && !naive && !(c->instrument && !dr);
+  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, dr, fullMaterials && !mode7), ((size_t)job.tidCount + 255) / 256);
+  HIPCHK(c, c->dQueue.alloc(1));
+  HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
+  job.queue = c->dQueue.p;
+  job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+  job.counters = nullptr;
+  job.drSkipNonFinite = c->drSkipNonFinite ? 1u : 0u;
+  const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
+  c->lastSchedule = 1;
+  c->lastShadeRecords = c->S.shadeTris != nullptr ? 1u : 0u;
+  // schedule 4 (experimental, never chosen automatically): the block-owned streaming form of the wavefront schedule - heavy static scenes with gltf / emissive materials
+  if (c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u) {
+    c->lastSchedule = 4; c->lastWide = 1u; c->lastDeep = c->stackNeeded4 > (uint)LDS_STACK ? 1u : 0u;
+    return launch_stream(c, job, st);
+  }
+  if (!inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount)) {
+    c->lastSchedule = 2; c->lastWide = (wfWide(c) && !c->instrument) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
+    return launch_wavefront(c, job, st, dr);
+  }
+  c->lastWide = (!stats && !motion && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
+  c->lastDeep = megaStackNeeded(c) > (uint)LDS_STACK ? 1u : 0u;
+  if (stats) { HIPCHK(c, c->dCounters.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dCounters.p, 0, sizeof(Counters), st)); job.counters = c->dCounters.p; }
+  if (dr) {
+    job.recordLanes = (uint)blocks * 256u;
+    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1)));
+    job.record = c->dRecord.p;
+  }
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
+    const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
+    // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
+    // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
+    // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
+    // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
+    const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
+    const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
+    const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
+    if (blockLocal) {
+      const bool lean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
+      const bool bwide = lean && (c->bwWide == 1 || (c->bwWide < 0 && c->S.megaWide != 0u)) && c->S.flatMode != 0u && c->nodes4Count != 0u && c->wideEnabled;      // heavy scenes: the 4-wide compressed tree, as the megakernel walks it
+      const bool bdeep = (bwide ? std::max(c->stackNeeded, c->stackNeeded4) : c->stackNeeded) > (uint)LDS_STACK;
+      const uint bNodeMin = bwide ? std::max(c->bwNodeMin, 16u) : c->bwNodeMin;                           // (a 4-wide visit is three times the work: the vote pays earlier)
+      c->lastSchedule = 3; c->lastWide = bwide ? 1u : 0u; c->lastDeep = bdeep ? 1u : 0u;
+      if (dr && job.vjp != 0u) launchBlock<true, true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);   // (a template parameter in this kernel: hpt_decl.h)
+      else if (dr) launchBlock<true, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
+      else if (lean) launchBlock<false, true>(c->S, job, blocks, st, bdeep, c->bwRefillBelow, bNodeMin, bwide);
+      else launchBlock<false, false>(c->S, job, std::min(blocks, c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : HPT_BW_FULL_WAVES)), st, bdeep, c->bwRefillBelow, c->bwNodeMin);
+    }
+    else if (motion && film) {
+      if (inRays) launchPTMotion<6>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<5>(c->S, job, blocks, st, deep); else launchPTMotion<4>(c->S, job, blocks, st, deep);
+    }
+    else if (motion) {
+      if (inRays) launchPTMotion<2>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<1>(c->S, job, blocks, st, deep); else launchPTMotion<0>(c->S, job, blocks, st, deep);
+    }
+    else if (dr) {
+      // the DR kernel's waves are emptier than the forward kernel's (lane utilisation 0.25), so leaving the inner-node loop when fewer than four
+      // lanes still walk pays even on light scenes: test_228 class 346 -> 364 Mpaths/s (forward: 698 -> 699; profiles/vote_medium.sh)
+      DevScene Sd = c->S;
+      if (c->nodeMinOverride < 0 && Sd.nodeMin < 4u) Sd.nodeMin = 4u;
+      if (stats) {                                                 // the counting probe follows the walk an uninstrumented call would do (see the forward probe below)
+        Sd.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;
+        launchPT<true, true, 0>(Sd, job, blocks, st, deep || (Sd.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
+      } else launchPT<false, true, 0>(Sd, job, blocks, st, deep);
+    }
+    else if (film) {
+      if (inRays) launchPT<false, false, 6>(c->S, job, blocks, st, deep); else if (naive) launchPT<false, false, 5>(c->S, job, blocks, st, deep); else launchPT<false, false, 4>(c->S, job, blocks, st, deep);
+    }
+    else if (inRays) launchPT<false, false, 2>(c->S, job, blocks, st, deep);
+    else if (naive)  launchPT<false, false, 1>(c->S, job, blocks, st, deep);
+    else if (stats) {
+      // the counting probe follows the walk an uninstrumented call would do: where that is the wavefront trace kernel on the 4-wide tree, the
+      // probe's single-level traversal walks that tree too (node visits = 64-byte lines of the tree actually used)
+      DevScene Sp = c->S;
+      Sp.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;   // "stats_wide": the caller says the measured call ran there
+      launchPT<true, false, 0>(Sp, job, blocks, st, deep || (Sp.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
+    }
+    else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) launchPT<false, false, 3>(c->S, job, blocks, st, deep);
+    else if (mode7)  launchPT<false, false, 7>(c->S, job, blocks, st, deep);
+    else             launchPT<false, false, 0>(c->S, job, blocks, st, deep);
+  });
 }
 
 extern "C" int hpt_path_trace_block_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum, int naive, void* stream)
@@ -2090,7 +2082,7 @@ static int path_trace_host(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uin
   (void)hipSetDevice(c->device);
   if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before UpdateMembersPlainData");
   const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
-  return roundTrip(c, naive ? c->tNaive : c->tPathTrace, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+  return roundTrip(c, naive ? c->tSlots[T_NAIVE] : c->tSlots[T_PATH_TRACE], (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
                    [&]() -> int { HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice)); return HPT_OK; },   // the callee ACCUMULATES into the caller's buffer
                    [&]() -> int { return hpt_path_trace_block_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, naive, nullptr); },
                    [&]() -> int { HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost)); return HPT_OK; });
@@ -2115,7 +2107,7 @@ try {
   if (tid == 0 || passNum == 0) return HPT_OK;
   DevBuf<float> dp, dd, dout;
   const size_t n = (size_t)tid * channels;
-  return roundTrip(c, c->tFromRays, KERNEL_EVENTS,                        // fromRaysPtTime (integrator_pt_host.cpp:92-103) in GetExecutionTime's four slots
+  return roundTrip(c, c->tSlots[T_FROM_RAYS], KERNEL_EVENTS,                        // fromRaysPtTime (integrator_pt_host.cpp:92-103) in GetExecutionTime's four slots
                    [&]() -> int { HIPCHK(c, dp.upload(rayPos, (size_t)tid * 4)); HIPCHK(c, dd.upload(rayDir, (size_t)tid * 4)); HIPCHK(c, dout.upload(out, n)); return HPT_OK; },
                    [&]() -> int { return hpt_path_trace_from_input_rays_block_dev(c, tid, channels, dp.p, dd.p, dout.p, passNum, nullptr); },
                    [&]() -> int { HIPCHK(c, hipMemcpy(out, dout.p, n * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
@@ -2154,15 +2146,12 @@ try {
   (void)hipSetDevice(c->device);
   hipStream_t st = (hipStream_t)stream;
   const uint blocks = (uint)(((size_t)blockNum * 16u + 255u) / 256u);
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
   GBufferPixel* o = (GBufferPixel*)outDev; GBufferPixel* sm = (GBufferPixel*)samplesDev;
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
-    gbufferKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+      gbufferKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, blockNum, o, sm, c->dStackOvf.p);
+    });
   });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_eval_gbuffer_dev"); }
 // Integrator::EvalGBuffer(blockNum, out_gbuffer) (integrator_pt.h:251; main.cpp:269-277): host pointer to winWidth * winHeight records. The
@@ -2192,15 +2181,12 @@ static int rt_launch(hpt_ctx* c, uint32_t tid, uint32_t channels, float* outDev,
 {
   (void)hipSetDevice(c->device);
   const uint blocks = (tid + 255u) / 256u;
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
-    if (channels == 0u) castSingleRayKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, outDev, c->dStackOvf.p);
-    else                rayTraceKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, outDev, c->dStackOvf.p);
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+      if (channels == 0u) castSingleRayKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, outDev, c->dStackOvf.p);
+      else                rayTraceKernel<flat(), motion(), sweep()><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, outDev, c->dStackOvf.p);
+    });
   });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  return HPT_OK;
 }
 // Host-pointer form of either pass: the caller's frame goes up (RayTraceBlock adds to it; CastSingleRayBlock leaves the pixels past tid as
 // they are) and comes back
@@ -2227,7 +2213,7 @@ try {
   (void)passNum;
   if (int rc = pixelPassCheck(c, "CastSingleRayBlock", "out_color", out, "tid", tid)) return rc;
   if (tid == 0u) return HPT_OK;
-  return rt_host(c, tid, 0u, out, c->tCastSingleRay);
+  return rt_host(c, tid, 0u, out, c->tSlots[T_CAST_SINGLE_RAY]);
 }
 catch (...) { return hptGuard(c, "hpt_cast_single_ray_block"); }
 
@@ -2249,7 +2235,7 @@ try {
   if (int rc = pixelPassCheck(c, "RayTraceBlock", "out_color", out, "tid", tid)) return rc;
   if (int rc = rt_check_channels(c, channels)) return rc;
   if (tid == 0u || channels > 4u) return HPT_OK;
-  return rt_host(c, tid, channels, out, c->tRayTrace);
+  return rt_host(c, tid, channels, out, c->tSlots[T_RAY_TRACE]);
 }
 catch (...) { return hptGuard(c, "hpt_ray_trace_block"); }
 
@@ -2626,23 +2612,20 @@ try {
   HIPCHK(c, c->dQueue.alloc(1));
   HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
   job.queue = c->dQueue.p;
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
-  job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
   const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
-  c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
-  c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
   const dim3 g(blocks), b(256);
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  if (c->S.motion != 0u) {
-    if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, true, false><<<g, b, 0, st>>>(Sq, job, q); }
-    else               { if (deep) pathTraceQmcKernel<true, false, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, true, false><<<g, b, 0, st>>>(Sq, job, q); }
-  }
-  else if (c->S.sweep)    pathTraceQmcKernel<false, false, false, true><<<g, b, 0, st>>>(Sq, job, q);
-  else if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, false, false><<<g, b, 0, st>>>(Sq, job, q); }
-  else                    { if (deep) pathTraceQmcKernel<true, false, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, false, false><<<g, b, 0, st>>>(Sq, job, q); }
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  return HPT_OK;
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
+    c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
+    job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
+    if (c->S.motion != 0u) {
+      if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, true, false><<<g, b, 0, st>>>(Sq, job, q); }
+      else               { if (deep) pathTraceQmcKernel<true, false, true, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, true, false><<<g, b, 0, st>>>(Sq, job, q); }
+    }
+    else if (c->S.sweep)    pathTraceQmcKernel<false, false, false, true><<<g, b, 0, st>>>(Sq, job, q);
+    else if (c->S.flatMode) { if (deep) pathTraceQmcKernel<true, true, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, true, false, false><<<g, b, 0, st>>>(Sq, job, q); }
+    else                    { if (deep) pathTraceQmcKernel<true, false, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, false, false><<<g, b, 0, st>>>(Sq, job, q); }
+  });
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block_dev"); }
 // host-pointer form: the caller's frame goes up, is added to and comes back; slots as path_trace_host fills them
@@ -2652,7 +2635,7 @@ try {
   if (int rc = qmc_check(c, channels, out, nullptr, nullptr)) return rc;
   (void)hipSetDevice(c->device);
   if (hpt_qmc_sample_count(pixelsNum, passNum) == 0u) return HPT_OK;
-  return roundTrip(c, c->tPathTraceQmc, out, (size_t)c->packedCount * channels, true,
+  return roundTrip(c, c->tSlots[T_PATH_TRACE_QMC], out, (size_t)c->packedCount * channels, true,
                    [&](float* d) { return hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, d, passNum, nullptr, nullptr, nullptr); });
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block"); }
@@ -2713,7 +2696,7 @@ try {
   if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceDR before UpdateMembersPlainData");
   const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
   float lossSum = 0.0f;
-  const int rc = roundTrip(c, c->tDR, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+  const int rc = roundTrip(c, c->tSlots[T_DR], (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
     [&]() -> int {
       HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, c->dRef.alloc(n)); HIPCHK(c, c->dData.alloc(gradSize)); HIPCHK(c, c->dGrad.alloc(gradSize)); HIPCHK(c, c->dLoss.alloc(1));
       HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));
@@ -2769,7 +2752,7 @@ try {
   (void)hipSetDevice(c->device);
   if (!c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceVJP before UpdateMembersPlainData");
   const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
-  return roundTrip(c, c->tVJP, (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
+  return roundTrip(c, c->tSlots[T_VJP], (tidCount && passNum) ? KERNEL_EVENTS : KERNEL_NONE,
     [&]() -> int {
       HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, c->dData.alloc(std::max<size_t>(gradSize, 1)));
       HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice));
@@ -2810,17 +2793,14 @@ try {
   (void)hipSetDevice(c->device);
   hipStream_t st = (hipStream_t)stream;
   const uint blocks = (tid + 255u) / 256u;
-  HIPCHK(c, ensureStackOverflow(c, (size_t)blocks * 256));
   const bool withGrad = c->drGradMode && dataDev != nullptr && gradDev != nullptr;   // Tex2DFetchAD's condition (integrator_dr.cpp:99) but for the texture's registration
   const float fPass = float(passNum);
-  HIPCHK(c, hipEventRecord(c->ev0, st));
-  traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
-    if (withGrad) rayTraceDrKernel<flat(), motion(), sweep(), true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, dataDev, gradDev, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
-    else          rayTraceDrKernel<flat(), motion(), sweep(), false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, nullptr, nullptr, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    traversalDispatch(c, [&](auto flat, auto motion, auto sweep) {
+      if (withGrad) rayTraceDrKernel<flat(), motion(), sweep(), true><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, dataDev, gradDev, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
+      else          rayTraceDrKernel<flat(), motion(), sweep(), false><<<dim3(blocks), dim3(256), 0, st>>>(c->S, c->dPackedXY.p, tid, channels, fPass, outDev, refDev, nullptr, nullptr, lossPerPixelDev, lossAccumDev, c->dStackOvf.p);
+    });
   });
-  HIPCHK(c, hipGetLastError());
-  HIPCHK(c, hipEventRecord(c->ev1, st));
-  return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_ray_trace_dr_dev"); }
 // Host-pointer form: the frame goes up and comes back (missed pixels and pixels past tid keep the caller's floats), the gradient is zeroed on the
@@ -2837,7 +2817,7 @@ try {
   const size_t nOut = (size_t)c->packedCount * 4u, nRef = (size_t)c->packedCount * channels;
   DevBuf<float> dOut, dRefImg, dDat, dGr, dPix;
   std::vector<float> pix(tid);
-  const int rc = roundTrip(c, c->tRayTraceDR, KERNEL_EVENTS,
+  const int rc = roundTrip(c, c->tSlots[T_RAY_TRACE_DR], KERNEL_EVENTS,
     [&]() -> int {
       HIPCHK(c, dOut.upload(out, nOut)); HIPCHK(c, dRefImg.upload(refImg, nRef)); HIPCHK(c, dPix.alloc(tid));
       if (data && gradSize) HIPCHK(c, dDat.upload(data, gradSize));
@@ -2983,22 +2963,22 @@ try {
 catch (...) { return hptGuard(c, "hpt_allreduce_grad"); }
 
 // ---- timing / instrumentation --------------------------------------------------------------------------------------------------------
+static const struct { const char* name; const char* alias; TimeSlot slot; } TIME_NAMES[] = {   // all the names GetExecutionTime answers to
+  { "PathTrace", "PathTraceBlock", T_PATH_TRACE },                        // integrator_pt_lgt.cpp:241-251
+  { "NaivePathTrace", "NaivePathTraceBlock", T_NAIVE },
+  { "PathTraceFromInputRays", "PathTraceFromInputRaysBlock", T_FROM_RAYS },
+  { "PathTraceDR", "PathTraceDRBlock", T_DR },                            // integrator_dr2.cpp:82-88
+  { "CastSingleRay", "CastSingleRayBlock", T_CAST_SINGLE_RAY },           // main.cpp:443
+  { "PathTraceQMC", "PathTraceBlockQMC", T_PATH_TRACE_QMC },              // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
+  { "RayTrace", "RayTraceBlock", T_RAY_TRACE },                           // raytraceTime (integrator_pt_host.cpp:75-90)
+  { "PathTraceVJP", nullptr, T_VJP },                                     // no counterpart: PathTraceDR's slots for the VJP form
+  { "RayTraceDR", nullptr, T_RAY_TRACE_DR },                              // shadowPtTime (integrator_dr.cpp:441)
+};
 extern "C" int hpt_get_execution_time(hpt_ctx* c, const char* name, float out[4])
 try {
   if (!c || !name || !out) return HPT_ERR_ARG;
-  const std::string n(name);
-  const float* src = nullptr;
-  if (n == "PathTrace" || n == "PathTraceBlock") src = c->tPathTrace;                       // integrator_pt_lgt.cpp:241-251
-  else if (n == "NaivePathTrace" || n == "NaivePathTraceBlock") src = c->tNaive;
-  else if (n == "PathTraceFromInputRays" || n == "PathTraceFromInputRaysBlock") src = c->tFromRays;
-  else if (n == "PathTraceDR" || n == "PathTraceDRBlock") src = c->tDR;                     // integrator_dr2.cpp:82-88
-  else if (n == "CastSingleRay" || n == "CastSingleRayBlock") src = c->tCastSingleRay;      // main.cpp:443
-  else if (n == "PathTraceQMC" || n == "PathTraceBlockQMC") src = c->tPathTraceQmc;            // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
-  else if (n == "RayTrace" || n == "RayTraceBlock") src = c->tRayTrace;                     // raytraceTime (integrator_pt_host.cpp:75-90)
-  else if (n == "PathTraceVJP") src = c->tVJP;                                              // no counterpart: PathTraceDR's slots for the VJP form
-  else if (n == "RayTraceDR") src = c->tRayTraceDR;                                         // shadowPtTime (integrator_dr.cpp:441)
-  if (!src) return HPT_OK;                                                                 // unknown names leave `out` untouched, as the reference does
-  for (int i = 0; i < 4; i++) out[i] = src[i];
+  for (const auto& t : TIME_NAMES)                                                           // unknown names leave `out` untouched, as the reference does
+    if (std::strcmp(name, t.name) == 0 || (t.alias && std::strcmp(name, t.alias) == 0)) { for (int i = 0; i < 4; i++) out[i] = c->tSlots[t.slot][i]; break; }
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_execution_time"); }

@@ -214,6 +214,10 @@ def test_library_exports_every_declared_symbol():
     nm = subprocess.run(["nm", "-D", "--defined-only", api.LIB_PATH], capture_output=True, text=True).stdout
     exported = set(re.findall(r" T (hpt_[a-z0-9_]+)", nm))
     assert declared <= exported
+    # what the host side shares internally (hpt_host.hip: namespace hpt::host, hidden) stays inside the library
+    nmc = subprocess.run(["nm", "-DC", "--defined-only", api.LIB_PATH], capture_output=True, text=True).stdout
+    internal = [l for l in nmc.splitlines() if "hpt::host::" in l]
+    assert " hpt_create" in nmc and not internal, internal[:8]
 
 
 def test_no_gpu_means_loud_failure_not_fallback():
