@@ -102,6 +102,11 @@ ABI = {
     "hpt_qmc_sample_count": (_u32, [_u32, _u32]),
     "hpt_path_trace_qmc_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
     "hpt_path_trace_qmc_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "hpt_kmlt_state_size": (_u32, [_u32]),
+    "hpt_path_trace_pss_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "hpt_kmlt_chain_count": (_i, [_vp, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
+    "hpt_path_trace_kmlt_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
+    "hpt_path_trace_kmlt_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _i, _vp, _vp, _vp]),
     "hpt_cam_create": (_i, [_vp, _i, C.POINTER(_vp)]),
     "hpt_cam_destroy": (None, [_vp]),
     "hpt_cam_set_parameters": (_i, [_vp, _u32, _u32, _vp, _i]),
@@ -163,6 +168,16 @@ def qmc_layout(dof, spectral, motion):
 def qmc_sample_count(pixels_num, pass_num):
     """Samples of one PathTraceBlockQMC call: min(2^32 - 1, pixelsNum * a_passNum)."""
     return int(load_library().hpt_qmc_sample_count(pixels_num, pass_num))
+
+
+def kmlt_state_size(trace_depth):
+    """IntegratorKMLT's m_randsPerThread: AlignedSize(10 * traceDepth + 6, 16) floats per primary-sample-space vector. Host code: no GPU."""
+    return int(load_library().hpt_kmlt_state_size(trace_depth))
+
+
+class KmltRecords(C.Structure):
+    """hpt_kmlt_records: device pointers, each may be null."""
+    _fields_ = [(n, _vp) for n in ("isLarge", "accepted", "a", "color", "pixel", "oldPixel", "initColor", "initPixel", "proposals", "contribAtX", "contribAtY")]
 
 
 COUNTER_NAMES = ("rays", "nodes", "tris", "surface_hits", "shadow_rays", "paths", "instances_entered", "tex_fetches",
@@ -362,6 +377,101 @@ class HipIntegrator:
             for p in ptrs:
                 self.L.hpt_device_free(self.h, p)
         return img, col, pix
+
+    # ---- IntegratorKMLT (mlt/integrator_kmlt.cpp) ---------------------------------------------------------------------
+    def _dev_scope(self):
+        """(alloc, free_all) over hpt_device_malloc: alloc(nbytes) -> device pointer."""
+        ptrs = []
+
+        def dev(nbytes):
+            p = _vp()
+            self._chk(self.L.hpt_device_malloc(self.h, max(int(nbytes), 16), C.byref(p)))
+            ptrs.append(p)
+            return p
+
+        def free_all():
+            for p in ptrs:
+                self.L.hpt_device_free(self.h, p)
+        return dev, free_all
+
+    def path_trace_pss(self, x):
+        """IntegratorKMLT::PathTraceF for the vectors x, float32 [n, stride] with stride >= kmlt_state_size(traceDepth): returns
+        (colours float32 [n, 4], pixel indices uint32 [n]). Every random number of path i is read from x[i]; m_randomGens is not touched."""
+        x = np.ascontiguousarray(x, np.float32)
+        assert x.ndim == 2
+        n, stride = x.shape
+        col, pix = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32)
+        dev, free_all = self._dev_scope()
+        try:
+            d_x, d_col, d_pix = dev(x.nbytes), dev(col.nbytes), dev(pix.nbytes)
+            if n:
+                self._chk(self.L.hpt_device_copy(self.h, d_x, x.ctypes.data, x.nbytes, 1))
+            self._chk(self.L.hpt_path_trace_pss_dev(self.h, d_x, n, stride, d_col, d_pix, None))
+            if n:
+                self._chk(self.L.hpt_device_copy(self.h, col.ctypes.data, d_col, col.nbytes, 2))
+                self._chk(self.L.hpt_device_copy(self.h, pix.ctypes.data, d_pix, pix.nbytes, 2))
+        finally:
+            free_all()
+        return col, pix
+
+    def PathTraceBlockKMLT(self, pixelsNum, channels, out_color, a_passNum):
+        """IntegratorKMLT::PathTraceBlock(pixelsNum, channels, out_color, a_passNum): Markov chains in primary sample space, then the brightness
+        normalisation; out_color float32 [winHeight, winWidth, 4], zero-filled by the caller."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and (channels != 4 or out_color.size == self.N * 4)
+        self._chk(self.L.hpt_path_trace_kmlt_block(self.h, pixelsNum, channels, out_color.ctypes.data, a_passNum))
+
+    def kmlt_chain_count(self, spp, pixels_num=None):
+        """(C, steps) of a PathTraceBlockKMLT call made now: the library's answer (hpt_kmlt_chain_count) for the option "kmlt_chains" or the
+        default, one chain per lane of the resident grid, at most pixelsNum * spp. Raises where the call would refuse the chain count."""
+        chains, steps = _u32(0), _u32(0)
+        self._chk(self.L.hpt_kmlt_chain_count(self.h, self.N if pixels_num is None else pixels_num, spp, C.byref(chains), C.byref(steps)))
+        return int(chains.value), int(steps.value)
+
+    def render_kmlt(self, spp, chains=None, normalize=True, records=False, proposals=False, unnormalised=False):
+        """One PathTraceBlockKMLT call through the device-pointer form, on a zero-filled frame. chains: sets the option "kmlt_chains" (None: as the
+        context has it). Returns a dict: "frame" [H, W, 4]; "stats" = [avgBrightness, actualBrightness, acceptance rate, normConst]; "chains",
+        "steps"; with records: "isLarge", "accepted" (uint8 [C, steps]), "a" [C, steps], "color" [C, steps, 4], "pixel", "oldPixel" (uint32
+        [C, steps]), "initColor" [C, 4], "initPixel" [C], "contribAtX", "contribAtY" [C, steps, 4] (.w: 1 when added to the frame); with proposals: "proposals" [C, steps, state size]; with unnormalised (and normalize):
+        "frame_unnormalised", the raw sums of the same run (the normalisation is then made by a second call, normalize = 2)."""
+        if chains is not None:
+            self.set_option("kmlt_chains", int(chains))
+        Cn, steps = self.kmlt_chain_count(spp)                   # the record arrays are sized by what the library will run
+        n = kmlt_state_size(self.params.traceDepth)
+        img = np.zeros((self.H, self.W, 4), np.float32)
+        stats = np.zeros(4, np.float64)
+        host = {}
+        if records:
+            host.update(isLarge=np.zeros((Cn, steps), np.uint8), accepted=np.zeros((Cn, steps), np.uint8), a=np.zeros((Cn, steps), np.float32),
+                        color=np.zeros((Cn, steps, 4), np.float32), pixel=np.zeros((Cn, steps), np.uint32), oldPixel=np.zeros((Cn, steps), np.uint32),
+                        initColor=np.zeros((Cn, 4), np.float32), initPixel=np.zeros(Cn, np.uint32),
+                        contribAtX=np.zeros((Cn, steps, 4), np.float32), contribAtY=np.zeros((Cn, steps, 4), np.float32))
+        if proposals:
+            host["proposals"] = np.zeros((Cn, steps, n), np.float32)
+        out = {"chains": Cn, "steps": steps}
+        dev, free_all = self._dev_scope()
+        try:
+            d_img, d_stats = dev(img.nbytes), dev(stats.nbytes)
+            self._chk(self.L.hpt_device_copy(self.h, d_img, img.ctypes.data, img.nbytes, 1))
+            rec = KmltRecords()
+            d_rec = {k: dev(v.nbytes) for k, v in host.items()}
+            for k, p in d_rec.items():
+                setattr(rec, k, p)
+            two = bool(normalize) and unnormalised
+            self._chk(self.L.hpt_path_trace_kmlt_block_dev(self.h, self.N, 4, d_img, spp, 0 if two else int(bool(normalize)), C.byref(rec) if host else None, d_stats, None))
+            if two:
+                raw = np.zeros_like(img)
+                self._chk(self.L.hpt_device_copy(self.h, raw.ctypes.data, d_img, img.nbytes, 2))
+                out["frame_unnormalised"] = raw
+                self._chk(self.L.hpt_path_trace_kmlt_block_dev(self.h, self.N, 4, d_img, spp, 2, None, d_stats, None))
+            self._chk(self.L.hpt_device_copy(self.h, img.ctypes.data, d_img, img.nbytes, 2))
+            self._chk(self.L.hpt_device_copy(self.h, stats.ctypes.data, d_stats, stats.nbytes, 2))
+            for k, v in host.items():
+                if v.nbytes:
+                    self._chk(self.L.hpt_device_copy(self.h, v.ctypes.data, d_rec[k], v.nbytes, 2))
+        finally:
+            free_all()
+        out.update(frame=img, stats=stats, **host)
+        return out
 
     def render(self, spp, channels=4, naive=False):
         img = np.zeros((self.H, self.W, channels), np.float32)

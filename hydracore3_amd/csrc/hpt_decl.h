@@ -229,6 +229,38 @@ struct QmcJob
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q);
 
+// ---- IntegratorKMLT (mlt/integrator_kmlt.cpp; hpt_kmlt.hip) ------------------------------------------------------------------------------
+// PathTraceF over caller-supplied number vectors: lane i < n reads vector i at x[i * vecStride + slot] and writes color[i], pixel[i]
+struct PssJob
+{
+  const float* x; uint n, vecStride, stateSize;
+  float4* color; uint* pixel;
+  const uint* packedXY; uint packedCount;    // the camera back plate reads m_packedXY[tid], tid = the lane (past the vector's end: 0)
+  uint* stackOverflow; uint gridLanes;
+};
+template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTracePssKernel(const DevScene S, const PssJob job);
+// the Markov chains: lane c < chains runs chain c for `steps` steps; cur / prop: the chain's current vector and its proposal, [slot][chain]
+struct KmltJob
+{
+  uint chains, steps, stateSize;
+  float* cur; float* prop;
+  float* outColor;                           // winWidth * winHeight * 4 floats, added to with float atomics
+  const uint* packedXY; uint packedCount;
+  uint* stackOverflow; uint gridLanes;
+  double* accumBrightness; uint* largeSteps; uint* accept;   // per chain
+  // records (hpt_kmlt_records; each may be null): per chain and step [c * steps + i], per chain [c], per chain, step and slot
+  unsigned char* recLarge; unsigned char* recAccepted; float* recA; float4* recColor; uint* recPixel; uint* recOldPixel;
+  float4* recInitColor; uint* recInitPixel; float* recProposals;
+  float4* recContribX; float4* recContribY;   // the two contributions of a step as formed, .w = 1 when the step added it to the film (the > 1e-12 test)
+};
+template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
+__global__ void __launch_bounds__(256, HPT_FILM_WAVES) kmltChainKernel(const DevScene S, const KmltJob job);
+// stats4 = { avgBrightness, actualBrightness, acceptance rate, normConst } from the per-chain sums and the frame (one block); then frame *= normConst
+__global__ void __launch_bounds__(256) kmltStatsKernel(const float4* frame, uint pixelsNum, uint passNum, uint chains, const double* accumBrightness,
+                                                       const uint* largeSteps, const uint* accept, double* stats4);
+__global__ void __launch_bounds__(256) kmltScaleKernel(float* frame, size_t n, const double* stats4);
+
 // ---- camera plug-in: CamPinHole / CamTableLens (cam_plugin/CamPinHole.cpp, CamTableLens.cpp; hpt_camrays.hip) -----------------------------
 // One lane per ray of a tile: lane tid serves pixel p = firstPixel + tid (x = p % width, y = p / width: the reference's pitch-linear split) and
 // owns slot tid of the three per-lane arrays. The scalars and the lens lines are the same for every lane (scalar loads).

@@ -95,7 +95,7 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 } } // namespace hpt::host
 using namespace hpt::host;
 
-enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
+enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_KMLT, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
 
 struct hpt_ctx
 {
@@ -153,6 +153,10 @@ struct hpt_ctx
   uint gensCount = 0;                                    // m_randomGens.size() as the last InitRandomGens / hpt_set_random_gens left it (the buffer never shrinks)
   DevBuf<uint> dQueue, dStackOvf; DevBuf<Counters> dCounters;
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
+  // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
+  DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
+  uint kmltChains = 0;                                   // hpt_set_option("kmlt_chains", n): 0 = one chain per lane of the resident grid
+  uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // wavefront schedule (hpt_wavefront.hip): the pixels of a call are cut into groups, each with its own path pool, ray queue and
@@ -2570,18 +2574,27 @@ try {
 }
 catch (...) { (void)hptGuard(nullptr, "hpt_qmc_sample_count"); return 0u; }
 // what the call needs, in the order the reference's driver makes its calls; `out` / records: at least one destination
+// The state refusals the QMC and KMLT entries share, one condition each, so that both say the same thing in the same words
+static int needCommitted(hpt_ctx* c, const std::string& who)
+{ return (!c->sceneUploaded || !c->paramsSet) ? c->fail(HPT_ERR_STATE, who + " before CommitDeviceData / UpdateMembersPlainData") : HPT_OK; }
+static int refuseSpectral(hpt_ctx* c, const std::string& who, const char* note)
+{ return c->S.spectralMode != 0u ? c->fail(HPT_ERR_UNSUPPORTED, who + ": m_spectral_mode is not served (" + note + ")") : HPT_OK; }
+static int needPacked(hpt_ctx* c, const std::string& who)
+{ return c->packedCount != (uint)(c->S.winWidth * c->S.winHeight) ? c->fail(HPT_ERR_STATE, who + " before PackXYBlock") : HPT_OK; }
+static int needFilmTablesRGB(hpt_ctx* c)
+{ return (c->hasFilm && !c->filmTablesRGB) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)") : HPT_OK; }
 static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void* sampleColor, const void* samplePixel)
 {
+  const std::string who("PathTraceBlockQMC");
   if (!out && !sampleColor && !samplePixel) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: no frame and no sample records to write");
   if ((sampleColor == nullptr) != (samplePixel == nullptr)) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: the sample records come as a pair (colours and pixel indices)");
-  if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlockQMC before CommitDeviceData / UpdateMembersPlainData");
-  if (c->S.spectralMode != 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: m_spectral_mode is not served (the spectral kernels are a separate family; hpt_qmc_layout still answers for it)");
+  if (int rc = needCommitted(c, who)) return rc;
+  if (int rc = refuseSpectral(c, who, "the spectral kernels are a separate family; hpt_qmc_layout still answers for it")) return rc;
   if (channels > 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: channels above 4 are the wavelength layers of spectral rendering");
   if (channels == 2u || channels == 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: a framebuffer of 1, 3 or 4 channels (three components are written per pixel)");
-  if (c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlockQMC before PackXYBlock");
+  if (int rc = needPacked(c, who)) return rc;
   if (c->gensCount == 0u) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC before InitRandomGens: sample s runs on generator s % m_randomGens.size()");
-  if (c->hasFilm && !c->filmTablesRGB) return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)");
-  return HPT_OK;
+  return needFilmTablesRGB(c);
 }
 extern "C" int hpt_path_trace_qmc_block_dev(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
                                             float* sampleColorDev, uint32_t* samplePixelDev, void* stream)
@@ -2639,6 +2652,169 @@ try {
                    [&](float* d) { return hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, d, passNum, nullptr, nullptr, nullptr); });
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block"); }
+
+// ---- IntegratorKMLT (mlt/integrator_kmlt.cpp; hpt_kmlt.hip) ---------------------------------------------------------------------------------
+// m_randsPerThread = AlignedSize(PER_BOUNCE * m_traceDepth + BOUNCE_START, 16) (:33-40, 235-244, 262)
+extern "C" uint32_t hpt_kmlt_state_size(uint32_t traceDepth)
+try {
+  const unsigned long long n = 10ull * traceDepth + 6ull;
+  return (uint32_t)((n + 15ull) / 16ull * 16ull);
+}
+catch (...) { (void)hptGuard(nullptr, "hpt_kmlt_state_size"); return 0u; }
+
+// what both entries need of the context, in the order of qmc_check
+static int kmlt_check(hpt_ctx* c, const char* who)
+{
+  const std::string w(who);
+  if (int rc = needCommitted(c, w)) return rc;
+  if (int rc = refuseSpectral(c, w, "spectral MLT stays in the reference")) return rc;
+  if (int rc = needPacked(c, w)) return rc;
+  return needFilmTablesRGB(c);
+}
+// the traversal variants pathTraceQmcKernel is dispatched over; f gets (DEEP, FLAT, MOTION, SWEEP) as compile-time constants
+template <class F>
+static void kmltDispatch(const hpt_ctx* c, bool deep, F f)
+{
+  const std::true_type T; const std::false_type N;
+  if (c->S.motion != 0u) {
+    if (c->S.flatMode) { if (deep) f(T, T, T, N); else f(N, T, T, N); }
+    else               { if (deep) f(T, N, T, N); else f(N, N, T, N); }
+  }
+  else if (c->S.sweep)    f(N, N, N, T);
+  else if (c->S.flatMode) { if (deep) f(T, T, N, N); else f(N, T, N, N); }
+  else                    { if (deep) f(T, N, N, N); else f(N, N, N, N); }
+}
+static void kmltNoteLaunch(hpt_ctx* c, bool deep)
+{
+  c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
+  c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
+}
+
+extern "C" int hpt_path_trace_pss_dev(hpt_ctx* c, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (!xDev || !color4fDev || !pixelDev) return c->fail(HPT_ERR_ARG, "PathTracePSS: null pointer (the vectors, the colours and the pixel indices are all needed)");
+  if (int rc = kmlt_check(c, "PathTracePSS")) return rc;
+  const uint32_t stateSize = hpt_kmlt_state_size(c->S.traceDepth);
+  if (strideFloats < stateSize) return c->fail(HPT_ERR_ARG, "PathTracePSS: strideFloats is below hpt_kmlt_state_size(traceDepth) = " + std::to_string(stateSize));
+  (void)hipSetDevice(c->device);
+  if (n == 0u) return HPT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  DevScene Sq = c->S; Sq.shadeTris = nullptr;                             // every BSDF branch gathers through the index chain
+  PssJob job; std::memset(&job, 0, sizeof(job));
+  job.x = xDev; job.n = n; job.vecStride = strideFloats; job.stateSize = stateSize;
+  job.color = (float4*)color4fDev; job.pixel = pixelDev; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+  const uint blocks = (uint)(((size_t)n + 255) / 256);
+  const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
+  const dim3 g(blocks), b(256);
+  return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+    kmltNoteLaunch(c, deep);
+    job.stackOverflow = c->dStackOvf.p; job.gridLanes = blocks * 256u;
+    kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { pathTracePssKernel<dp(), flat(), motion(), sweep()><<<g, b, 0, st>>>(Sq, job); });
+  });
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_pss_dev"); }
+
+// C of a call: the option, or one chain per lane of the resident grid, reduced until every chain has a step
+static int kmlt_chain_count(hpt_ctx* c, unsigned long long total, uint& chains)
+{
+  if (c->kmltChains != 0u) {
+    if ((unsigned long long)c->kmltChains > total) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: kmlt_chains exceeds pixelsNum * a_passNum (a chain would have no step)");
+    chains = c->kmltChains;
+  } else chains = (uint)std::min<unsigned long long>((unsigned long long)gridBlocks(c, false, true) * 256ull, total);
+  return HPT_OK;
+}
+
+extern "C" int hpt_kmlt_chain_count(hpt_ctx* c, uint32_t pixelsNum, uint32_t passNum, uint32_t* chainsOut, uint32_t* stepsOut)
+try {
+  if (!c || !chainsOut || !stepsOut) return HPT_ERR_ARG;
+  *chainsOut = *stepsOut = 0u;
+  const unsigned long long total = (unsigned long long)pixelsNum * (unsigned long long)passNum;
+  if (total == 0ull) return HPT_OK;
+  uint chains = 0;
+  if (int rc = kmlt_chain_count(c, total, chains)) return rc;
+  if (total / chains > 0xFFFFFFFEull) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: more than 2^32 - 2 steps per chain: raise kmlt_chains");
+  *chainsOut = chains; *stepsOut = (uint32_t)(total / chains);
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_kmlt_chain_count"); }
+
+extern "C" int hpt_path_trace_kmlt_block_dev(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                             int normalize, hpt_kmlt_records* rec, double* stats4Dev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (c->paramsSet && c->S.renderLayer == FB_DIRECT)                       // :250-251
+    return hpt_path_trace_qmc_block_dev(c, pixelsNum, channels, outDev, passNum, nullptr, nullptr, stream);
+  if (!outDev) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: null frame");
+  if (channels != 4u) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: channels must be 4 (the contributions are written at pixel * 4 whatever it is)");
+  if (normalize < 0 || normalize > 2) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: normalize is 0 (chains only), 1 (chains, then the normalisation) or 2 (the normalisation of the last call's chains only)");
+  if (int rc = kmlt_check(c, "PathTraceBlockKMLT")) return rc;
+  if (pixelsNum > c->packedCount) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: pixelsNum exceeds winWidth * winHeight");
+  (void)hipSetDevice(c->device);
+  const unsigned long long total = (unsigned long long)pixelsNum * (unsigned long long)passNum;
+  if (total == 0ull) return HPT_OK;
+  hipStream_t st = (hipStream_t)stream;
+  uint chains = 0;
+  if (normalize == 2) {
+    if (c->kmltLastChains == 0u) return c->fail(HPT_ERR_STATE, "PathTraceBlockKMLT: normalize = 2 before any chains were run on this context");
+    chains = c->kmltLastChains;
+  } else if (int rc = kmlt_chain_count(c, total, chains)) return rc;
+  const unsigned long long steps64 = total / chains;                       // samplesPerPass: the integer quotient, the remainder is dropped (:268)
+  if (steps64 > 0xFFFFFFFEull) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: more than 2^32 - 2 steps per chain: raise kmlt_chains");
+  const uint steps = (uint)steps64;
+  HIPCHK(c, c->dKmltStats.alloc(4));
+  double* stats = stats4Dev ? stats4Dev : c->dKmltStats.p;
+  auto normalise = [&]() {
+    kmltStatsKernel<<<dim3(1), dim3(256), 0, st>>>((const float4*)outDev, pixelsNum, passNum, chains, c->dKmltAccum.p, c->dKmltLarge.p, c->dKmltAccept.p, stats);
+    const size_t n = (size_t)pixelsNum * 4u;
+    if (normalize != 0) kmltScaleKernel<<<dim3((uint)((n + 255) / 256)), dim3(256), 0, st>>>(outDev, n, stats);
+  };
+  if (normalize != 2) {
+    const uint32_t stateSize = hpt_kmlt_state_size(c->S.traceDepth);
+    HIPCHK(c, c->dKmltCur.alloc((size_t)stateSize * chains)); HIPCHK(c, c->dKmltProp.alloc((size_t)stateSize * chains));
+    HIPCHK(c, c->dKmltAccum.alloc(chains)); HIPCHK(c, c->dKmltLarge.alloc(chains)); HIPCHK(c, c->dKmltAccept.alloc(chains));
+    DevScene Sq = c->S; Sq.shadeTris = nullptr;
+    KmltJob job; std::memset(&job, 0, sizeof(job));
+    job.chains = chains; job.steps = steps; job.stateSize = stateSize; job.cur = c->dKmltCur.p; job.prop = c->dKmltProp.p; job.outColor = outDev;
+    job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+    job.accumBrightness = c->dKmltAccum.p; job.largeSteps = c->dKmltLarge.p; job.accept = c->dKmltAccept.p;
+    if (rec) {
+      job.recLarge = rec->isLarge; job.recAccepted = rec->accepted; job.recA = rec->a; job.recColor = (float4*)rec->color; job.recPixel = rec->pixel;
+      job.recOldPixel = rec->oldPixel; job.recInitColor = (float4*)rec->initColor; job.recInitPixel = rec->initPixel; job.recProposals = rec->proposals;
+      job.recContribX = (float4*)rec->contribAtX; job.recContribY = (float4*)rec->contribAtY;
+    }
+    const uint blocks = (chains + 255u) / 256u;
+    const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
+    const dim3 g(blocks), b(256);
+    if (int rc = launchFrame(c, (size_t)blocks * 256, st, [&]() {           // the event pair spans the chains and the normalisation
+      kmltNoteLaunch(c, deep);
+      job.stackOverflow = c->dStackOvf.p; job.gridLanes = blocks * 256u;
+      kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { kmltChainKernel<dp(), flat(), motion(), sweep()><<<g, b, 0, st>>>(Sq, job); });
+      normalise();
+    })) return rc;
+    c->kmltLastChains = chains;
+    return HPT_OK;
+  }
+  return launchFrame(c, 256, st, normalise);
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_kmlt_block_dev"); }
+// host-pointer form: the caller's frame (zero-filled, as main.cpp has it) goes up, is added to and scaled, and comes back
+extern "C" int hpt_path_trace_kmlt_block(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* out, uint32_t passNum)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (c->paramsSet && c->S.renderLayer == FB_DIRECT) return hpt_path_trace_qmc_block(c, pixelsNum, channels, out, passNum);
+  if (!out) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: null frame");
+  if (channels != 4u) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: channels must be 4 (the contributions are written at pixel * 4 whatever it is)");
+  if (int rc = kmlt_check(c, "PathTraceBlockKMLT")) return rc;
+  if (pixelsNum > c->packedCount) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: pixelsNum exceeds winWidth * winHeight");
+  (void)hipSetDevice(c->device);
+  if ((unsigned long long)pixelsNum * passNum == 0ull) return HPT_OK;
+  uint chains = 0;
+  if (int rc = kmlt_chain_count(c, (unsigned long long)pixelsNum * passNum, chains)) return rc;   // (refused before the frame is copied)
+  return roundTrip(c, c->tSlots[T_KMLT], out, (size_t)c->packedCount * 4u, true,
+                   [&](float* d) { return hpt_path_trace_kmlt_block_dev(c, pixelsNum, channels, d, passNum, 1, nullptr, nullptr, nullptr); });
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_kmlt_block"); }
 
 // ---- differentiable rendering ---------------------------------------------------------------------------------------------------------
 extern "C" int hpt_reset_diff_tex(hpt_ctx* c)
@@ -2970,6 +3146,7 @@ static const struct { const char* name; const char* alias; TimeSlot slot; } TIME
   { "PathTraceDR", "PathTraceDRBlock", T_DR },                            // integrator_dr2.cpp:82-88
   { "CastSingleRay", "CastSingleRayBlock", T_CAST_SINGLE_RAY },           // main.cpp:443
   { "PathTraceQMC", "PathTraceBlockQMC", T_PATH_TRACE_QMC },              // IntegratorQMC::PathTraceBlock's shadowPtTime (integrator_qmc.cpp:314)
+  { "PathTraceKMLT", "PathTraceBlockKMLT", T_KMLT },                      // IntegratorKMLT::PathTraceBlock's shadowPtTime (integrator_kmlt.cpp:477)
   { "RayTrace", "RayTraceBlock", T_RAY_TRACE },                           // raytraceTime (integrator_pt_host.cpp:75-90)
   { "PathTraceVJP", nullptr, T_VJP },                                     // no counterpart: PathTraceDR's slots for the VJP form
   { "RayTraceDR", nullptr, T_RAY_TRACE_DR },                              // shadowPtTime (integrator_dr.cpp:441)
@@ -3044,6 +3221,7 @@ try {
   else if (k == "bw_node_min") { if (value < 0 || value > 64) return c->fail(HPT_ERR_ARG, "bw_node_min: 0..64"); c->bwNodeMin = (uint)value; }
   else if (k == "device_build") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "device_build: -1 by CommitScene's options, 0 never, 1 always"); c->deviceBuild = value; c->accelCommitted = false; c->flatRefittable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
+  else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
   else return c->fail(HPT_ERR_ARG, "hpt_set_option: unknown option " + k);
   return HPT_OK;

@@ -43,6 +43,7 @@ struct QmcRands
     if (bounce == 0u && matDim != 0u) { r.x = qmcFloat(table, s, matDim); r.y = qmcFloat(table, s, matDim + 1u); }
     return r;
   }
+  HPT_DEV float blend(Rng& gen, uint /*bounce*/, uint /*layer*/) const { return rng_float1(gen); }   // IntegratorQMC::GetRandomNumbersMatB: pseudo
 };
 
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>

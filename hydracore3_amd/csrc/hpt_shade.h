@@ -235,12 +235,14 @@ HPT_DEV void blendTreeEval(const DevScene& S, uint rootId, V2 uv, V3 l, V3 v, V3
 }
 
 // Where a vertex's light and material numbers come from. The default is the pseudo generator in the base class's order (GetRandomNumbersLgts:
-// the light-selection float, then the float4; GetRandomNumbersMats: one float4 - integrator_pt.cpp:29-35); the QMC integrator passes its
-// own source (hpt_qmc.hip: QmcRands).
+// the light-selection float, then the float4; GetRandomNumbersMats: one float4; GetRandomNumbersMatB: one float per blend layer -
+// integrator_pt.cpp:29-37); the QMC integrator passes its own source (hpt_qmc.hip: QmcRands), the primary-sample-space pass reads all three
+// from the caller's vector (hpt_kmlt.hip: PssRands).
 struct PseudoRands
 {
   HPT_DEV V4 lights(Rng& gen, uint /*bounce*/, float& rndId) const { rndId = rng_float1(gen); return rng_float4(gen); }
   HPT_DEV V4 mats(Rng& gen, uint /*bounce*/) const { return rng_float4(gen); }
+  HPT_DEV float blend(Rng& gen, uint /*bounce*/, uint /*layer*/) const { return rng_float1(gen); }
 };
 
 // Shades the vertex a closest-hit query returned for one path.  All path registers are passed by reference and the
@@ -410,13 +412,14 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
       // reference, whose leaf samplers assign them
       const MaterialRec* lm = &m; uint lt = mtype; V3 ltex3 = tex3, lfour = four;
       if (!(DR || LEAN) && mtype == MAT_TYPE_BLEND) {
+        uint layer = 0u;
         while (lt == MAT_TYPE_BLEND) {
           const V4 wd = texSample(S.textures, lm->texid[0], mulRows2x4(lm->row0[0], lm->row1[0], uv));
           const float weight = lm->data[0] * wd.x;
-          const float select = rng_float1(gen);                        // GetRandomNumbersMatB (integrator_pt.cpp:37)
+          const float select = rands_.blend(gen, bounce, layer);       // GetRandomNumbersMatB (integrator_pt.cpp:37)
           if (select < weight) { ms.pdf *= weight; ms.val = ms.val * weight; lm = &S.materials[lm->datai[1]]; }
           else                 { ms.pdf *= 1.0f - weight; ms.val = ms.val * (1.0f - weight); lm = &S.materials[lm->datai[0]]; }
-          lt = lm->mtype;
+          lt = lm->mtype; layer++;
         }
         leafTextures(S, *lm, uv, ltex3, lfour);
       }

@@ -258,6 +258,16 @@ public:
   { if (m_ctx) report(hpt_path_trace_qmc_block(m_ctx, pixelsNum, channels, out_color, a_passNum), "PathTraceBlockQMC"); }
 };
 
+// IntegratorKMLT (mlt/integrator_kmlt.cpp): Kelemen MLT; derives from the QMC integrator as in the reference, whose FB_DIRECT layer it forwards to
+// (the C entry does that itself). out_color: zero-filled, 4 channels; the chain count is hpt_set_option(ctx, "kmlt_chains", n) or the default.
+class IntegratorKMLTHIP : public IntegratorQMCHIP
+{
+public:
+  using IntegratorQMCHIP::IntegratorQMCHIP;
+  void PathTraceBlock(uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t a_passNum) override
+  { if (m_ctx) report(hpt_path_trace_kmlt_block(m_ctx, pixelsNum, channels, out_color, a_passNum), "PathTraceBlockKMLT"); }
+};
+
 class IntegratorDRHIP : public IntegratorHIP
 {
 public:

@@ -305,6 +305,60 @@ int  hpt_path_trace_qmc_block_dev(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t cha
 /* S of the two calls above for (pixelsNum, passNum): min(2^32 - 1, pixelsNum * passNum). Host code; no context. */
 uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum);
 
+/* ---- Kelemen MLT in primary sample space (mlt/integrator_kmlt.cpp; `hydra`'s MLT mode) ---------------------------------- */
+/* m_randsPerThread: floats of one primary-sample-space vector = AlignedSize(10 * traceDepth + 6, 16). Slots 0..3: the lens float4 (0 and 1
+ * are the film position in [0,1]); 4: the wavelength sample (unused in RGB); 5: the time; 6 + 10 b + 0..3: bounce b's light float4 (.w selects
+ * the light); 6 + 10 b + 4..7: its material float4; 6 + 10 b + 8 + layer: its blend numbers (layer 2 and up overlaps the next bounce's light
+ * numbers, as in the reference; a slot past the vector's end reads 0). Host code; no context, no GPU. */
+uint32_t hpt_kmlt_state_size(uint32_t traceDepth);
+/* IntegratorKMLT::PathTraceF for n vectors in device memory, vector i at xDev + i * strideFloats: the path whose every random number is read
+ * from the vector. color4fDev[i] = accumColor * m_exposureMult and a fourth float 0 (no camRespoceRGB: PathTraceF applies none in RGB mode),
+ * pixelDev[i] = y * winWidth + x with x = min(uint(x[0] * winWidth), winWidth - 1), y likewise from x[1] (IntegratorQMC::SampleCameraRay).
+ * m_randomGens is neither read nor written. Asynchronous on stream. HPT_ERR_ARG for a null pointer or strideFloats below
+ * hpt_kmlt_state_size(traceDepth); HPT_ERR_UNSUPPORTED with m_spectral_mode on; HPT_ERR_STATE before CommitDeviceData, UpdateMembersPlainData
+ * or PackXYBlock. Megakernel schedule only. */
+int  hpt_path_trace_pss_dev(hpt_ctx* ctx, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev, void* stream);
+/* Records of the chains, all in device memory, each pointer NULL or long enough: per chain c and step i at [c * steps + i] - whether the step
+ * was a large one and whether it was accepted (bytes), the acceptance probability a, the proposal's colour (4 floats) and pixel, the pixel of
+ * the state it was compared with; per chain the initial state's colour and pixel; every proposal vector, [c][i][state size] floats; and
+ * per chain and step the two contributions as formed, contribAtX (at the compared state) and contribAtY (at the proposal), 4 floats each, the
+ * fourth 1 when the step added it to the frame (its squared length passed the 1e-12 test) and 0 when not.
+ * C = the chain count, steps = (pixelsNum * passNum) / C. */
+typedef struct hpt_kmlt_records {
+  uint8_t*  isLarge;
+  uint8_t*  accepted;
+  float*    a;
+  float*    color;
+  uint32_t* pixel;
+  uint32_t* oldPixel;
+  float*    initColor;
+  uint32_t* initPixel;
+  float*    proposals;
+  float*    contribAtX;
+  float*    contribAtY;
+} hpt_kmlt_records;
+/* IntegratorKMLT::PathTraceBlock(pixelsNum, channels, out_color, a_passNum) (integrator_kmlt.cpp:248-478): C Markov chains of
+ * (pixelsNum * a_passNum) / C steps each, every step adding its two contributions to the frame with float atomics, then the brightness
+ * normalisation multiplies the first pixelsNum * 4 floats by normConst: pass a zero-filled frame of winWidth * winHeight * 4 floats. C is
+ * hpt_set_option("kmlt_chains", n), by default one chain per lane of the resident grid, at most pixelsNum * a_passNum (DESIGN.md 7 has this
+ * and the other definitions the reference ties to its thread count). m_randomGens is left untouched. m_renderLayer == FB_DIRECT forwards to
+ * hpt_path_trace_qmc_block and returns what it returns. HPT_ERR_ARG for a null frame, channels other than 4, pixelsNum above winWidth *
+ * winHeight and kmlt_chains above pixelsNum * a_passNum; HPT_ERR_UNSUPPORTED with m_spectral_mode on; HPT_ERR_STATE as hpt_path_trace_pss_dev;
+ * a_passNum = 0 is HPT_OK and touches nothing. hpt_get_execution_time("PathTraceBlockKMLT") gives its four slots; the kernel slot spans the chains and the normalisation. */
+/* C and steps = (pixelsNum * passNum) / C of a hpt_path_trace_kmlt_block call made now with these arguments (the option kmlt_chains, or the
+ * resident grid of the present launch configuration, at most pixelsNum * passNum): what a caller sizes its record arrays by. Both 0 when
+ * pixelsNum * passNum is 0; HPT_ERR_ARG where the call would refuse the chain count. Host code; no GPU work. */
+int  hpt_kmlt_chain_count(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t passNum, uint32_t* chains, uint32_t* steps);
+int  hpt_path_trace_kmlt_block(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t passNum);
+/* The same on device memory, asynchronous on stream. normalize: 0 = the chains only (the frame holds the raw sums), 1 = the chains and the
+ * normalisation, 2 = the normalisation alone, of the frame as it is and the chains of the last call on this context (so a caller can keep the
+ * raw sums of the same run). recDev: host struct of device pointers, or NULL. stats4Dev, if not NULL, receives { avgBrightness (mean over the
+ * chains that made a large step of their mean F over large steps), actualBrightness (mean contribFunc of the first pixelsNum pixels before
+ * scaling), accepted steps / (pixelsNum * passNum), normConst }; normConst is 1 and nothing is scaled when no chain made a large step or the
+ * frame is black. */
+int  hpt_path_trace_kmlt_block_dev(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                   int normalize, hpt_kmlt_records* recDev, double* stats4Dev, void* stream);
+
 /* ---- camera plug-in (cam_plugin/CamPluginAPI.h:39-77; CamPinHole.cpp, CamTableLens.cpp, main_with_cam_gpu.cpp) ----- */
 /* The two ICamRaysAPI2 cameras of the reference on the device, and the loop that feeds PathTraceFromInputRaysBlock from them with rays, colours
  * and frame resident in device memory. A camera belongs to the context it was made from (its device, its error text: failures below are reported
