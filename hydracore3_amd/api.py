@@ -93,6 +93,8 @@ ABI = {
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
     "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
+    "hpt_denoise_frame": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hpt_denoise_frame_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "hpt_cast_single_ray_block": (_i, [_vp, _u32, _vp, _u32]),
     "hpt_cast_single_ray_block_dev": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "hpt_ray_trace_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
@@ -126,6 +128,18 @@ GBUFFER_SAMPLES = 16
 GBUFFER_DTYPE = np.dtype([("depth", np.float32), ("norm", np.float32, (3,)), ("texc", np.float32, (2,)), ("rgba", np.float32, (4,)),
                           ("shadow", np.float32), ("coverage", np.float32), ("matId", np.int32), ("objId", np.int32), ("instId", np.int32)])
 assert GBUFFER_DTYPE.itemsize == 60
+
+
+
+class DENOISE_PARAMS(C.Structure):
+    """hpt_denoise_params (include/hydra_hip.h): 7 dwords."""
+    _fields_ = [("iterations", _u32), ("normalSquarings", _u32), ("flags", _u32),
+                ("normConst", _f), ("sigmaColor", _f), ("sigmaDepth", _f), ("sigmaAlbedo", _f)]
+
+
+DENOISE_DEMODULATE = 1
+# the defaults of HipIntegrator.denoise, as the header states them (chosen on the quality check of profiles/denoise.md)
+DENOISE_DEFAULTS = {"iterations": 5, "normal_squarings": 7, "sigma_color": 0.6, "sigma_depth": 0.05, "sigma_albedo": 0.1, "demodulate": True}
 
 _LIB = None
 
@@ -505,6 +519,37 @@ class HipIntegrator:
         finally:
             self.L.hpt_device_free(self.h, d_out)
         return out, raw
+
+    @staticmethod
+    def denoise_params(norm_const=1.0, iterations=None, normal_squarings=None, sigma_color=None, sigma_depth=None, sigma_albedo=None, demodulate=None):
+        """A DENOISE_PARAMS; None takes the default of DENOISE_DEFAULTS."""
+        d = DENOISE_DEFAULTS
+        pick = lambda v, k: d[k] if v is None else v
+        return DENOISE_PARAMS(int(pick(iterations, "iterations")), int(pick(normal_squarings, "normal_squarings")),
+                              DENOISE_DEMODULATE if pick(demodulate, "demodulate") else 0, float(norm_const),
+                              float(pick(sigma_color, "sigma_color")), float(pick(sigma_depth, "sigma_depth")), float(pick(sigma_albedo, "sigma_albedo")))
+
+    def denoise(self, frame, gbuffer=None, norm_const=1.0, iterations=None, normal_squarings=None, sigma_color=None, sigma_depth=None,
+                sigma_albedo=None, demodulate=None):
+        """DenoiseFrame: the a-trous filter over frame, float32 [height, width, 4] (scaled by norm_const, e.g. 1 / spp), guided by
+        gbuffer, a GBUFFER_DTYPE array [height, width]; None: EvalGBuffer() of the loaded scene. Returns a new float32 [height, width, 4]."""
+        frame = np.ascontiguousarray(frame, np.float32)
+        assert frame.ndim == 3 and frame.shape[2] == 4
+        if gbuffer is None:
+            gbuffer = self.EvalGBuffer()
+        gbuffer = np.ascontiguousarray(gbuffer)
+        assert gbuffer.dtype == GBUFFER_DTYPE and gbuffer.shape == frame.shape[:2]
+        p = self.denoise_params(norm_const, iterations, normal_squarings, sigma_color, sigma_depth, sigma_albedo, demodulate)
+        out = np.zeros_like(frame)
+        self._chk(self.L.hpt_denoise_frame(self.h, frame.shape[1], frame.shape[0], frame.ctypes.data, gbuffer.ctypes.data, C.byref(p), out.ctypes.data))
+        return out
+
+    def denoise_dev(self, color_ptr, gbuffer_ptr, out_ptr, width=None, height=None, params=None, stream=None, **kw):
+        """DenoiseFrame on device pointers (frame of width * height * 4 floats, width * height G-buffer records, output frame); asynchronous on
+        `stream`. params: a DENOISE_PARAMS, or the keyword arguments of denoise_params."""
+        p = params if params is not None else self.denoise_params(**kw)
+        self._chk(self.L.hpt_denoise_frame_dev(self.h, self.W if width is None else width, self.H if height is None else height,
+                                               color_ptr, gbuffer_ptr, C.byref(p), out_ptr, stream))
 
     def GetExecutionTime(self, name):
         out = (C.c_float * 4)(0, 0, 0, 0)

@@ -200,6 +200,30 @@ static_assert(sizeof(GBufferPixel) == 60, "GBufferPixel is 15 dwords");
 // one lane per (pixel, sample): 16 * blockNum lanes in blocks of 256; `samples` (null or 16 * blockNum records) receives the records before the reduction
 template <bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256) gbufferKernel(const DevScene S, const uint* packedXY, uint blockNum, GBufferPixel* out, GBufferPixel* samples, uint* stackOverflow);
+// ---- DenoiseFrame (hpt_denoise.hip) -----------------------------------------------------------------------------------------
+// The pack kernel reads color / gbuffer and writes cin, planeN, planeA; a pass reads cin, planeN, planeA and writes cout (the last pass: the
+// caller's frame, with the alpha from color). Planes: C = {r, g, b, instId}, N = {n.xyz, depth}, A = {albedo.rgb, matId}.
+struct DenoiseJob
+{
+  const float4* color; const GBufferPixel* gbuffer;   // the caller's frame and records (pack kernel; color also by the last pass)
+  float4* cin; float4* cout; float4* planeN; float4* planeA;
+  size_t pixels; uint width, height;
+  uint  step;                     // s = 1 << i
+  uint  normalSquarings, flags;
+  uint  terms;                    // bit 0 / 1 / 2: sigmaDepth / sigmaColor / sigmaAlbedo is not 0
+  float normConst;
+  float sigmaDepthStep;           // sigmaDepth * float(s)
+  float sigmaColor2;              // sc * sc, sc = sigmaColor * 2^-i
+  float sigmaAlbedo2;             // sigmaAlbedo * sigmaAlbedo
+};
+__global__ void __launch_bounds__(256) denoisePackKernel(const DenoiseJob job);                   // one lane per pixel, blocks of 256
+// one lane per pixel, a block = 32 x 8 pixels; TILE 0: taps loaded from memory; 1 / 2: from an LDS tile with a halo of 2 * TILE pixels, for step TILE.
+// Measured at 1920 x 1080 (profiles/denoise.md): the passes at steps 1 and 2 take 0.185 / 0.122 ms from the tile against 0.227 / 0.151 ms with direct
+// loads, the call 0.783 against 0.859 ms, the results equal bit for bit. -DHPT_DENOISE_LDS=0 builds the direct-load form for A/B.
+#ifndef HPT_DENOISE_LDS
+#define HPT_DENOISE_LDS 1
+#endif
+template <bool LAST, int TILE = 0> __global__ void __launch_bounds__(256) denoisePassKernel(const DenoiseJob job);
 // ---- CastSingleRayBlock / RayTraceBlock (hpt_raytrace.hip) -----------------------------------------------------------------------------
 // one lane per pixel of packedXY[0 .. tidCount); outColor: winWidth * winHeight pixels of 4 floats (assigned) / of `channels` = 3 or 4 floats (added to)
 template <bool FLAT, bool MOTION, bool SWEEP>

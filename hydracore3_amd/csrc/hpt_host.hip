@@ -95,7 +95,7 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 } } // namespace hpt::host
 using namespace hpt::host;
 
-enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_KMLT, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
+enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_KMLT, T_DENOISE, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
 
 struct hpt_ctx
 {
@@ -158,6 +158,7 @@ struct hpt_ctx
   uint kmltChains = 0;                                   // hpt_set_option("kmlt_chains", n): 0 = one chain per lane of the resident grid
   uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
+  DevBuf<float4> dDenoiseN, dDenoiseA, dDenoiseC[2];     // DenoiseFrame (hpt_denoise.hip): the guide planes and the two ping-pong colour planes; grown on demand
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // wavefront schedule (hpt_wavefront.hip): the pixels of a call are cut into groups, each with its own path pool, ray queue and
   // stream, so that the tail of one group's trace pass overlaps the other groups' work
@@ -2172,6 +2173,87 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_eval_gbuffer"); }
 
+// ---- DenoiseFrame (no counterpart in the reference; DESIGN.md 2.12, hpt_denoise.hip) -------------------------------------------------------------
+static_assert(sizeof(hpt_denoise_params) == 28, "hpt_denoise_params is 7 dwords");
+// The refusals both forms share; each names its argument. `a`, `b`: the two frames of n pixels that must not overlap.
+static int denoiseCheck(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer, const hpt_denoise_params* p, const float* out)
+{
+  const std::string w("DenoiseFrame: ");
+  if (!color) return c->fail(HPT_ERR_ARG, w + "color is null");
+  if (!gbuffer) return c->fail(HPT_ERR_ARG, w + "gbuffer is null");
+  if (!p) return c->fail(HPT_ERR_ARG, w + "params is null");
+  if (!out) return c->fail(HPT_ERR_ARG, w + "out is null");
+  if (width == 0u || width > 32768u) return c->fail(HPT_ERR_ARG, w + "width must be 1 .. 32768");
+  if (height == 0u || height > 32768u) return c->fail(HPT_ERR_ARG, w + "height must be 1 .. 32768");
+  if (p->iterations < 1u || p->iterations > 8u) return c->fail(HPT_ERR_ARG, w + "iterations must be 1 .. 8");
+  if (p->normalSquarings > 8u) return c->fail(HPT_ERR_ARG, w + "normalSquarings must be 0 .. 8");
+  if (p->flags & ~HPT_DENOISE_DEMODULATE) return c->fail(HPT_ERR_ARG, w + "flags has unknown bits (bit 0: demodulate albedo)");
+  const struct { const char* name; float v; } f[] = { { "normConst", p->normConst }, { "sigmaColor", p->sigmaColor }, { "sigmaDepth", p->sigmaDepth }, { "sigmaAlbedo", p->sigmaAlbedo } };
+  for (const auto& a : f) if (!(a.v >= 0.0f) || !(a.v <= 3.402823466e38f)) return c->fail(HPT_ERR_ARG, w + a.name + " must be finite and not negative");
+  const size_t bytes = (size_t)width * height * 4 * sizeof(float);
+  const char* a = (const char*)color; const char* b = (const char*)out;
+  if (a < b + bytes && b < a + bytes) return c->fail(HPT_ERR_ARG, w + "out aliases color");
+  return HPT_OK;
+}
+// Device-pointer form: the pack kernel, then `iterations` passes between the two colour planes, the last one into the caller's frame; one event
+// pair around them. Asynchronous on stream (growing the scratch planes frees the old ones, which waits for the device).
+extern "C" int hpt_denoise_frame_dev(hpt_ctx* c, uint32_t width, uint32_t height, const float* colorDev, const hpt_gbuffer_pixel* gbufferDev,
+                                     const hpt_denoise_params* p, float* outDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = denoiseCheck(c, width, height, colorDev, gbufferDev, p, outDev)) return rc;
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)width * height;
+  HIPCHK(c, c->dDenoiseN.alloc(n)); HIPCHK(c, c->dDenoiseA.alloc(n)); HIPCHK(c, c->dDenoiseC[0].alloc(n));
+  if (p->iterations > 1u) HIPCHK(c, c->dDenoiseC[1].alloc(n));
+  DenoiseJob job; std::memset(&job, 0, sizeof(job));
+  job.color = (const float4*)colorDev; job.gbuffer = (const GBufferPixel*)gbufferDev;
+  job.planeN = c->dDenoiseN.p; job.planeA = c->dDenoiseA.p;
+  job.pixels = n; job.width = width; job.height = height;
+  job.normalSquarings = p->normalSquarings; job.flags = p->flags; job.normConst = p->normConst;
+  job.terms = (p->sigmaDepth != 0.0f ? 1u : 0u) | (p->sigmaColor != 0.0f ? 2u : 0u) | (p->sigmaAlbedo != 0.0f ? 4u : 0u);
+  job.sigmaAlbedo2 = p->sigmaAlbedo * p->sigmaAlbedo;
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+  job.cin = c->dDenoiseC[0].p;
+  denoisePackKernel<<<dim3((uint)((n + 255u) / 256u)), dim3(256), 0, st>>>(job);
+  const dim3 grid((width + 31u) / 32u, (height + 7u) / 8u);
+  for (uint32_t i = 0; i < p->iterations; i++) {
+    const bool last = i + 1u == p->iterations;
+    job.step = 1u << i;
+    job.sigmaDepthStep = p->sigmaDepth * float(job.step);
+    const float sc = p->sigmaColor * (1.0f / float(job.step));                // 2^-i: an exact scaling
+    job.sigmaColor2 = sc * sc;
+    job.cin = c->dDenoiseC[i & 1u].p;
+    job.cout = last ? (float4*)outDev : c->dDenoiseC[(i & 1u) ^ 1u].p;
+#if HPT_DENOISE_LDS                                                          // steps 1 and 2 read their taps from an LDS tile (hpt_decl.h)
+    if (job.step == 1u) { if (last) denoisePassKernel<true, 1><<<grid, dim3(256), 0, st>>>(job); else denoisePassKernel<false, 1><<<grid, dim3(256), 0, st>>>(job); continue; }
+    if (job.step == 2u) { if (last) denoisePassKernel<true, 2><<<grid, dim3(256), 0, st>>>(job); else denoisePassKernel<false, 2><<<grid, dim3(256), 0, st>>>(job); continue; }
+#endif
+    if (last) denoisePassKernel<true><<<grid, dim3(256), 0, st>>>(job);
+    else      denoisePassKernel<false><<<grid, dim3(256), 0, st>>>(job);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_denoise_frame_dev"); }
+// Host-pointer form: the frame and the records go up, the filtered frame comes back
+extern "C" int hpt_denoise_frame(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer,
+                                 const hpt_denoise_params* p, float* out)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = denoiseCheck(c, width, height, color, gbuffer, p, out)) return rc;
+  (void)hipSetDevice(c->device);
+  const size_t n = (size_t)width * height;
+  DevBuf<float> dColor, dOut; DevBuf<hpt_gbuffer_pixel> dGb;
+  return roundTrip(c, c->tSlots[T_DENOISE], KERNEL_EVENTS,
+                   [&]() -> int { HIPCHK(c, dColor.upload(color, n * 4)); HIPCHK(c, dGb.upload(gbuffer, n)); HIPCHK(c, dOut.alloc(n * 4)); return HPT_OK; },
+                   [&]() -> int { return hpt_denoise_frame_dev(c, width, height, dColor.p, dGb.p, p, dOut.p, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, dOut.p, n * 4 * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+catch (...) { return hptGuard(c, "hpt_denoise_frame"); }
+
 // ---- CastSingleRayBlock / RayTraceBlock (integrator_pt.h:254, 263; integrator_rt.cpp:420-461; integrator_pt_host.cpp:29-36, 75-90) ----------------
 // channels of RayTraceBlock: 1 and 2 are refused (the reference writes three floats at that stride: over the next pixel and, for the last
 // one, past the buffer - DESIGN.md 7); above 4 its kernel_ContributeToImage3 writes nothing, so there is nothing to launch
@@ -3150,6 +3232,7 @@ static const struct { const char* name; const char* alias; TimeSlot slot; } TIME
   { "RayTrace", "RayTraceBlock", T_RAY_TRACE },                           // raytraceTime (integrator_pt_host.cpp:75-90)
   { "PathTraceVJP", nullptr, T_VJP },                                     // no counterpart: PathTraceDR's slots for the VJP form
   { "RayTraceDR", nullptr, T_RAY_TRACE_DR },                              // shadowPtTime (integrator_dr.cpp:441)
+  { "DenoiseFrame", nullptr, T_DENOISE },                                 // no counterpart
 };
 extern "C" int hpt_get_execution_time(hpt_ctx* c, const char* name, float out[4])
 try {

@@ -190,6 +190,15 @@ public:
   static_assert(sizeof(GBufferPixel) == sizeof(hpt_gbuffer_pixel), "GBufferPixel and hpt_gbuffer_pixel are the same 15 dwords");
   virtual void EvalGBuffer(uint32_t blockNum, GBufferPixel* out_gbuffer)
   { if (m_ctx) report(hpt_eval_gbuffer(m_ctx, blockNum, reinterpret_cast<hpt_gbuffer_pixel*>(out_gbuffer)), "EvalGBuffer"); }
+  // DenoiseFrame (no counterpart in the reference; include/hydra_hip.h): the a-trous filter over a width x height frame of 4 floats per pixel, guided
+  // by the records of EvalGBuffer; out4f must not overlap color4f. Needs no scene. Returns false on an error.
+  bool DenoiseFrame(uint32_t width, uint32_t height, const float* color4f, const GBufferPixel* gbuffer, const hpt_denoise_params& params, float* out4f)
+  {
+    if (!m_ctx) return false;
+    const int rc = hpt_denoise_frame(m_ctx, width, height, color4f, reinterpret_cast<const hpt_gbuffer_pixel*>(gbuffer), &params, out4f);
+    report(rc, "DenoiseFrame");
+    return rc == HPT_OK;
+  }
   // cam_plugin/CamPluginAPI.h:27-37: both structs are 16 bytes (origin + wavelength, direction + time), camera space
   struct RayPosAndW { float origin[3]; float wave; };
   struct RayDirAndT { float direction[3]; float time; };

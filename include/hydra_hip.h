@@ -253,6 +253,31 @@ int  hpt_eval_gbuffer(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* out);
  * 16 * blockNum records that receive every sample's record as it is before the reduction (sample k of packed pixel b at [16 * b + k]). */
 int  hpt_eval_gbuffer_dev(hpt_ctx* ctx, uint32_t blockNum, hpt_gbuffer_pixel* outDev, hpt_gbuffer_pixel* samplesDev, void* stream);
 
+/* DenoiseFrame: an edge-avoiding a-trous wavelet filter over a frame, guided by the records of EvalGBuffer. No counterpart in the reference
+ * (it writes the records to images for an external denoiser); DESIGN.md 2.12 defines it operation by operation and
+ * tests/denoise_reference.py restates it in numpy float32, bit for bit.
+ *   iterations       1..8 passes of the 5 x 5 B3 kernel at tap distance 1, 2, 4, ... (default 5: a 125-pixel footprint)
+ *   normalSquarings  0..8: the normal weight max(0, n_p . n_q) is squared this many times (default 7: power 128)
+ *   flags            bit 0: divide the colour by max(albedo, 1e-3) before the filter and multiply it back after it (default on)
+ *   normConst        scales the frame on the way in (1 / spp for an accumulated frame)
+ *   sigmaColor, sigmaDepth, sigmaAlbedo   widths of the rational edge stops 1 / (1 + x); 0 switches a term off. Defaults 0.6, 0.05, 0.1:
+ *                    chosen on the 4-spp Cornell box against its 512-spp frame (profiles/denoise.md).
+ * A tap counts only where instId and matId equal the centre's; non-finite colours are skipped and rebuilt from their neighbours. */
+typedef struct hpt_denoise_params { uint32_t iterations, normalSquarings, flags; float normConst, sigmaColor, sigmaDepth, sigmaAlbedo; } hpt_denoise_params;
+#define HPT_DENOISE_DEMODULATE 1u
+/* color4f: width * height pixels of 4 floats, row-major; gbuffer: width * height records in the same order (EvalGBuffer's for a full
+ * window); out4f: width * height * 4 floats, rgb filtered, alpha = color alpha * normConst. Host pointers. Needs a created context only: no
+ * scene, no PackXYBlock, no generators. HPT_ERR_ARG with a message naming the argument: a null pointer; width or height 0 (or above 32768);
+ * iterations outside 1..8; normalSquarings above 8; a negative or non-finite sigma or normConst; unknown flag bits; out4f overlapping
+ * color4f. hpt_get_execution_time("DenoiseFrame") gives its four slots. The scratch planes belong to the context and grow on demand. */
+int  hpt_denoise_frame(hpt_ctx* ctx, uint32_t width, uint32_t height, const float* color4f, const hpt_gbuffer_pixel* gbuffer,
+                       const hpt_denoise_params* params, float* out4f);
+/* The same with the three arrays resident in device memory (params stays a host pointer); asynchronous on stream (a hipStream_t, NULL =
+ * default stream): PathTraceBlock at low spp, EvalGBuffer and this call can follow each other on one stream. hpt_last_kernel_ms gives the
+ * time of the pack kernel and the passes together. */
+int  hpt_denoise_frame_dev(hpt_ctx* ctx, uint32_t width, uint32_t height, const float* color4fDev, const hpt_gbuffer_pixel* gbufferDev,
+                           const hpt_denoise_params* params, float* out4fDev, void* stream);
+
 /* ---- primary-ray preview and Whitted ray tracing (integrator_rt.cpp) ------------------------------------------------- */
 /* Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254, integrator_pt_host.cpp:29-36, integrator_rt.cpp:33-53,
  * 116-161, 420-430; main.cpp:435-446; hydra_api/hydra_cpu.cpp:105): for each of the first tid pixels of m_packedXY one pinhole ray through
