@@ -493,6 +493,9 @@ HPT_DEV V3 ld3(const float* p) { return v3(p[0], p[1], p[2]); }
 
 // include/cmat_gltf.h:6-90
 // (Mcol, coatCol: the material's metal and coat colours - the spectral kernel runs the routine a second time on their fourth components)
+// CHOOSE_FIRST: a vertex computes only what the lobe it takes reads (below). Only the lean forward kernels ask for it (shadeVertex: LEAN && !DR):
+// their scenes are the ones with waves of a single lobe. The other kernels compute everything before the choice, as the reference does.
+template <bool CHOOSE_FIRST = false>
 HPT_DEV void gltfSampleAndEvalC(const MaterialRec& m, const V3 Mcol, const V3 coatCol, V4 rands, V3 v, V3 n, V3 baseColor, V3 fourParams, BsdfS& r)
 {
   const uint cflags = m.cflags;
@@ -503,24 +506,44 @@ HPT_DEV void gltfSampleAndEvalC(const MaterialRec& m, const V3 Mcol, const V3 co
   const float fresnelIOR = m.data[GLTF_FLOAT_IOR];
   if (cflags == GLTF_COMPONENT_METAL) metalness = 1.0f;
 
-  V3 ggxDir; float ggxPdf, ggxVal;
-  if (roughness == 0.0f) {
-    const V3 pefReflDir = reflect((-1.0f) * v, n);
-    const float cosThetaOut = dot(pefReflDir, n);
-    ggxDir = pefReflDir;
-    ggxVal = (cosThetaOut <= 1e-6f) ? 0.0f : (1.0f / smax(cosThetaOut, 1e-6f));
-    ggxPdf = 1.0f;
-  } else {
-    ggxDir = ggxSample(v2(rands.x, rands.y), v, n, roughness);
-    ggxPdf = ggxEvalPDF(ggxDir, v, n, roughness);
-    ggxVal = ggxEvalBSDF(ggxDir, v, n, roughness);
+  // The lobe depends on rands.z, rands.w, metalness and coatValue only, so it is known before anything is evaluated. With CHOOSE_FIRST the
+  // GGX / mirror triple is computed by the metal and coat lobes, the Lambert direction by the diffuse one, f_i by the coat lobe and by a coated
+  // diffuse one - each ONCE, under the union of its readers, not inside the three branches, so that a wave with mixed lobes runs the GGX code
+  // once; a wave whose lanes all take one lobe (Lambert scenes) skips the rest. A mixed wave skips nothing and pays for the extra branches and
+  // merges: the thin-film fixture ran 1.4 % slower with this form in its kernel (profiles/r6_shade_lean.md), hence the flag. Without it:
+  // everything but f_i for every lane, f_i for the lanes that are not metal, as it always was.
+  const float prob_specular = 0.5f * coatValue;
+  const float prob_diffuse = 1.0f - prob_specular;
+  const bool lobeMetal = rands.z < metalness;
+  const bool lobeCoat = !lobeMetal && rands.w < prob_specular;
+  const bool lobeDiffuse = !lobeMetal && !lobeCoat;
+  const bool coatedDiffuse = lobeDiffuse && coatValue > 0.0f && fresnelIOR > 0.0f;
+
+  V3 ggxDir = v3(0, 0, 0); float ggxPdf = 0.0f, ggxVal = 0.0f;
+  if (!CHOOSE_FIRST || !lobeDiffuse) {
+    if (roughness == 0.0f) {
+      const V3 pefReflDir = reflect((-1.0f) * v, n);
+      const float cosThetaOut = dot(pefReflDir, n);
+      ggxDir = pefReflDir;
+      ggxVal = (cosThetaOut <= 1e-6f) ? 0.0f : (1.0f / smax(cosThetaOut, 1e-6f));
+      ggxPdf = 1.0f;
+    } else {
+      ggxDir = ggxSample(v2(rands.x, rands.y), v, n, roughness);
+      ggxPdf = ggxEvalPDF(ggxDir, v, n, roughness);
+      ggxVal = ggxEvalBSDF(ggxDir, v, n, roughness);
+    }
   }
-  const V3 lambertDir = mapSampleToCosineDistribution(rands.x, rands.y, n, n, 1.0f);
-  const float lambertPdf = absf(dot(lambertDir, n)) * HPT_INV_PI;
+  V3 lambertDir = v3(0, 0, 0); float lambertPdf = 0.0f;
+  if (!CHOOSE_FIRST || lobeDiffuse) {
+    lambertDir = mapSampleToCosineDistribution(rands.x, rands.y, n, n, 1.0f);
+    lambertPdf = absf(dot(lambertDir, n)) * HPT_INV_PI;
+  }
   const float lambertVal = HPT_INV_PI;
+  float f_i = 0.0f;
+  if (CHOOSE_FIRST ? (lobeCoat || coatedDiffuse) : !lobeMetal) f_i = frDielectricPBRT(absf(dot(v, n)), 1.0f, fresnelIOR);
 
   float pdfSelect = 1.0f;
-  if (rands.z < metalness) {
+  if (lobeMetal) {
     pdfSelect *= metalness;
     const float VdotH = dot(v, normalize(v + ggxDir));
     r.dir = ggxDir;
@@ -532,10 +555,7 @@ HPT_DEV void gltfSampleAndEvalC(const MaterialRec& m, const V3 Mcol, const V3 co
     r.flags = (roughness == 0.0f) ? RAY_EVENT_S : RAY_FLAG_HAS_NON_SPEC;
   } else {
     pdfSelect *= 1.0f - metalness;
-    const float f_i = frDielectricPBRT(absf(dot(v, n)), 1.0f, fresnelIOR);
-    const float prob_specular = 0.5f * coatValue;
-    const float prob_diffuse = 1.0f - prob_specular;
-    if (rands.w < prob_specular) {
+    if (lobeCoat) {
       pdfSelect *= prob_specular;
       r.dir = ggxDir;
       r.val = ggxVal * coatCol * (1.0f - metalness) * f_i * coatValue;
@@ -549,7 +569,7 @@ HPT_DEV void gltfSampleAndEvalC(const MaterialRec& m, const V3 Mcol, const V3 co
       r.dval = v3s(lambertVal * (1.0f - metalness));
       r.pdf = lambertPdf;
       r.flags = RAY_FLAG_HAS_NON_SPEC;
-      if (coatValue > 0.0f && fresnelIOR > 0.0f) {
+      if (coatedDiffuse) {
         const float m_fdr_int = m.data[GLTF_FLOAT_MI_FDR_INT];
         const float f_o = frDielectricPBRT(absf(dot(lambertDir, n)), 1.0f, fresnelIOR);
         const float k = lerpf(1.0f, (1.0f - f_i) * (1.0f - f_o) / (fresnelIOR * fresnelIOR * (1.0f - m_fdr_int)), coatValue);
@@ -560,8 +580,9 @@ HPT_DEV void gltfSampleAndEvalC(const MaterialRec& m, const V3 Mcol, const V3 co
   }
   r.pdf *= pdfSelect;
 }
+template <bool CHOOSE_FIRST = false>
 HPT_DEV void gltfSampleAndEval(const MaterialRec& m, V4 rands, V3 v, V3 n, V3 baseColor, V3 fourParams, BsdfS& r)
-{ gltfSampleAndEvalC(m, ld3(m.colors[GLTF_COLOR_METAL]), ld3(m.colors[GLTF_COLOR_COAT]), rands, v, n, baseColor, fourParams, r); }
+{ gltfSampleAndEvalC<CHOOSE_FIRST>(m, ld3(m.colors[GLTF_COLOR_METAL]), ld3(m.colors[GLTF_COLOR_COAT]), rands, v, n, baseColor, fourParams, r); }
 
 // include/cmat_gltf.h:93-147
 HPT_DEV void gltfEvalC(const MaterialRec& m, const V3 Mcol, const V3 coatCol, V3 l, V3 v, V3 n, V3 baseColor, V3 fourParams, BsdfE& res)

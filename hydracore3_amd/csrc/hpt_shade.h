@@ -258,6 +258,8 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
                          bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V3& contrib,
                          V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f, const RANDS rands_ = RANDS())
 {
+  // the lean forward kernels (Lambert-heavy benchmark scenes: waves of one lobe) evaluate only what a vertex uses; see gltfSampleAndEvalC
+  constexpr bool LEAN_FWD = LEAN && !DR;
   bool didBounce = false;
   if (hit.inst == 0xFFFFFFFFu) {
     flags |= (bounce == 0) ? (RAY_FLAG_PRIME_RAY_MISS | RAY_FLAG_IS_DEAD | RAY_FLAG_OUT_OF_SCENE) : (RAY_FLAG_IS_DEAD | RAY_FLAG_OUT_OF_SCENE);
@@ -379,10 +381,13 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
 
     // -- kernel_NextBounce (integrator_pt.cpp:426-548) --
     if (mtype == MAT_TYPE_LIGHT_SOURCE) {
-      const V4 tc = texSample(S.textures, m.texid[0], mulRows2x4(m.row0[0], m.row1[0], uv));
       const uint lightId = (uint)S.remapInst[2 * instId + 1];
-      V3 lightInt = ld3(m.colors[0]) * v3(tc.x, tc.y, tc.z);
+      V3 lightInt = v3(0, 0, 0);
       float misWeight = 1.0f;
+      if (!LEAN_FWD || lightId == 0xFFFFFFFFu) {                       // (a mesh bound to a light discards this value: the lean forward kernels do not fetch it then)
+        const V4 tc = texSample(S.textures, m.texid[0], mulRows2x4(m.row0[0], m.row1[0], uv));
+        lightInt = ld3(m.colors[0]) * v3(tc.x, tc.y, tc.z);
+      }
       if (lightId != 0xFFFFFFFFu) {
         const LightRec& L = S.lights[lightId];
         const float lightCos = dot(rdir, ld3(L.norm));
@@ -428,7 +433,7 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
       V3 sNorm = hitNorm;
       if (leafBump) sNorm = bumpNormal(S, ml, hitNorm, hitTang, uv);
       const V4 rands = rands_.mats(gen, bounce);                       // GetRandomNumbersMats: drawn for every material type (integrator_pt_mat.cpp:147)
-      if (lt == MAT_TYPE_GLTF) gltfSampleAndEval(ml, rands, vdir, sNorm, ld3(ml.colors[GLTF_COLOR_BASE]) * ltex3, lfour, ms);
+      if (lt == MAT_TYPE_GLTF) gltfSampleAndEval<LEAN_FWD>(ml, rands, vdir, sNorm, ld3(ml.colors[GLTF_COLOR_BASE]) * ltex3, lfour, ms);
       else if (!(DR || LEAN) && lt == MAT_TYPE_CONDUCTOR) {
         if (smax(ml.data[1], ml.data[0]) < 1e-3f) conductorSmoothSampleAndEval(ml, ml.data[2], ml.data[3], vdir, sNorm, ms);
         else                                      conductorRoughSampleAndEval(ml, ml.data[2], ml.data[3], rands, vdir, sNorm, ltex3, ms);

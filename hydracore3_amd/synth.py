@@ -235,6 +235,57 @@ def material_zoo(width=96, height=64) -> S.SceneData:
     return sc
 
 
+def gltf_branch_scene(width=64, height=64, spectral=False) -> S.SceneData:
+    """Every branch of gltfSampleAndEvalC and both emissive cases in one frame: a Lambert floor and ceiling; seven panels on the back wall -
+    a metal (metalness 1), a half-metal mirror (metalness 0.5, roughness 0), a rough half-metal (metalness 0.5, roughness 0.4), a coat with
+    IOR 1.5, a coat with IOR 0, a rough full metal without Fresnel term (IOR 0) and a half coat; a textured emissive quad bound to the rect light
+    under the ceiling and a textured emissive quad without a light on the left wall. gltf and emissive materials only: the lean kernels render it.
+    `spectral`: the same scene under m_spectral_mode = 1."""
+    sc = S.SceneData()
+    sc.width, sc.height = width, height
+    sc.cam_pos, sc.cam_look_at, sc.cam_up = (0.3, 1.4, 5.5), (0.0, 1.1, 0.0), (0.0, 1.0, 0.0)
+    sc.fov, sc.trace_depth = 50.0, 5
+    if spectral:                                                       # m_spectral_mode = 1: colours carried as four samples, one uniform spectrum
+        sc.spectral_mode = 1
+        sc.spec_offset_sz, sc.spec_values = [(0, 471)], np.ones(471, np.float32)
+    chk = np.zeros((4, 4, 4), np.float32)
+    yy, xx = np.mgrid[0:4, 0:4]
+    chk[..., 0] = 0.3 + 0.6 * ((xx + yy) % 2)
+    chk[..., 1] = 0.9 - 0.5 * ((xx + yy) % 2)
+    chk[..., 2] = 0.5
+    chk[..., 3] = 1.0
+    tex = sc.add_texture(S.Texture(chk, S.TEX_RGBA32F, False, S.ADDR_WRAP, S.ADDR_WRAP, S.FILTER_LINEAR))
+    M = sc.materials
+    M.append(S.material_lambert((0.7, 0.65, 0.6)))                                        # 0 pure Lambert
+    M.append(S.material_gltf((0.9, 0.6, 0.2, 1.0), 1.0, 0.6, 0.0, 1.5))                   # 1 metal, metalness 1
+    M.append(S.material_gltf((0.8, 0.8, 0.9, 1.0), 0.5, 1.0, 0.0, 1.5))                   # 2 metalness 0.5, roughness 0
+    M.append(S.material_gltf((0.3, 0.7, 0.4, 1.0), 0.5, 0.6, 0.0, 1.5))                   # 3 metalness 0.5, roughness 0.4
+    M.append(S.material_gltf((0.2, 0.4, 0.8, 1.0), 0.0, 0.7, 1.0, 1.5, tex))              # 4 coat, IOR 1.5 (textured base)
+    c0 = S.material_gltf((0.8, 0.3, 0.3, 1.0), 0.0, 0.8, 1.0, 1.5)                        # 5 coat, IOR 0
+    c0["data"][S.GLTF_FLOAT_IOR] = 0.0
+    M.append(c0)
+    m0 = S.material_gltf((0.7, 0.7, 0.3, 1.0), 1.0, 0.5, 0.0, 1.5)                        # 6 metal, IOR 0: hydraFresnelCond without the Schlick term
+    m0["data"][S.GLTF_FLOAT_IOR] = 0.0
+    M.append(m0)
+    M.append(S.material_gltf((0.5, 0.5, 0.5, 1.0), 0.3, 1.0, 0.5, 1.33))                  # 7 all three lobes in one material: mirror metal / mirror coat / diffuse
+    lit, unlit = len(M), len(M) + 1
+    lm = S.translate(0.0, 2.99, 0.5)
+    sc.lights.append(S.light_rect(lm, 0.8, 0.8, (1.0, 0.95, 0.9), 14.0))
+    M.append(S.material_emissive((1.0, 0.95, 0.9), 14.0, 0, tex))                         # 8 textured emissive, bound to light 0
+    sc.lights[0]["matId"] = lit
+    M.append(S.material_emissive((0.4, 0.9, 0.6), 3.0, S.UINT_MAX, tex))                  # 9 textured emissive, no light
+    pw = 6.4 / 7.0
+    parts = [(*_quad((-3.2, 0, 3), (6.4, 0, 0), (0, 0, -4.5), 2, 2), 0),                  # floor (+y)
+             (*_quad((-3.2, 3, -1.5), (6.4, 0, 0), (0, 0, 4.5)), 0),                      # ceiling (-y)
+             (*_quad((3.2, 0, 3), (0, 0, -4.5), (0, 3, 0)), 7)]                           # right wall (-x)
+    parts += [(*_quad((-3.2 + pw * i, 0, -1.5), (pw, 0, 0), (0, 3, 0), 1, 1, 2.0), 1 + i) for i in range(7)]   # back wall (+z): materials 1..7
+    parts.append((*_quad((-3.2, 0.6, 2.0), (0, 0, -2.5), (0, 1.6, 0), 1, 1, 2.0), unlit))  # left wall (+x): the emitter without a light
+    sc.add_instance(sc.add_mesh(*_merge(parts)), np.eye(4))
+    lp, ln, lt, luv, lidx = _quad((-0.8, 0, -0.8), (1.6, 0, 0), (0, 0, 1.6), 1, 1, 2.0)   # (-y)
+    sc.add_instance(sc.add_mesh(lp, ln, lt, luv, lidx, [lit]), lm, -1, 0)
+    return sc
+
+
 def dr_scene(xml_path, width=512, height=512, tex_size=256, target=False) -> S.SceneData:
     """SURVEY.md 8d 'S3 dr-228': scenes/test_228 (two 4096-triangle spheres in a box, point light) with matGray bound to a
     tex_size^2 x 4 differentiable albedo texture (drmain.cpp:185's PutDiffTex2D(1, 256, 256, 4) shape; the scene as shipped has
