@@ -87,6 +87,7 @@ ABI = {
     "hpt_allreduce_grad": (_i, [_vp, _vp, _sz, _vp]),
     "hpt_get_schedule": (_i, [_vp, C.POINTER(_i), C.POINTER(_u32)]),
     "hpt_get_last_launch": (_i, [_vp, C.POINTER(_u32)]),
+    "hpt_get_stack_witness": (_i, [_vp, C.POINTER(_u64)]),
     "hpt_get_accel_info": (_i, [_vp, C.POINTER(_f)]),
     "hpt_set_option": (_i, [_vp, C.c_char_p, _i]),
     "hpt_get_commit_time": (_i, [_vp, C.POINTER(_f)]),
@@ -738,6 +739,12 @@ class HipIntegrator:
         out = (C.c_uint32 * 4)()
         self._chk(self.L.hpt_get_last_launch(self.h, out))
         return {"schedule": int(out[0]), "wide_nodes": bool(out[1]), "shade_records": bool(out[2]), "deep_stack": bool(out[3])}
+
+    def stack_witness(self):
+        """With set_option("dbg_stack_witness", 1): (words of the stacks' HBM part the last launch wrote, words filled before it). hpt_get_stack_witness."""
+        out = (C.c_uint64 * 2)()
+        self._chk(self.L.hpt_get_stack_witness(self.h, out))
+        return int(out[0]), int(out[1])
 
     def last_schedule(self):
         s, it = C.c_int(0), C.c_uint32(0)

@@ -29,6 +29,7 @@ template <bool DR, bool LEAN, bool DEEP, bool FLAT, bool WIDE, bool VJP>
 __global__ void __launch_bounds__(256, HPT_BW_WAVES(DR, LEAN)) pathTraceBlockKernel(const DevScene S, const Job job, uint refillBelow, uint nodeMin)
 {
   __shared__ uint stackMem[LDS_STACK * 256];
+  static_assert(!DR || LDS_STACK >= 15, "PathTraceDR stages its gradient scatter in rows 0..14 of the stack array (drReverseSweep): HPT_LDS_STACK >= 15");
   __shared__ uint pool[8 * BW_POOL];                   // ray entries, field-major: o.xyz, tfar | d.xyz, owner lane | kind << 31; reused for the ray's result
   __shared__ float coldPix[3 * 256];
   __shared__ uint  coldU[3 * 256];

@@ -200,6 +200,7 @@ struct hpt_ctx
   int deviceBuild = -1; void* lbvh = nullptr; unsigned long long geomVersion = 1, lbvhGeomVersion = 0; std::vector<size_t> lbvhPosOff, lbvhIdxOff;
   uint lastSchedule = 1, lastWfIters = 0;
   uint lastWide = 0, lastShadeRecords = 0, lastDeep = 0;          // what the last launch walked: 4-wide compressed tree, 64-byte shading records, HBM part of the stacks
+  bool stackWitness = false; size_t witnessWords = 0;             // "dbg_stack_witness": dStackOvf is filled with STACK_SENTINEL before a launch; words the last launch's fill covered
 
   DevScene S;
   bool sceneUploaded = false, paramsSet = false;
@@ -963,6 +964,20 @@ static hipError_t ensureStackOverflow(hpt_ctx* c, size_t lanes)
   return c->dStackOvf.alloc(extra * lanes);
 }
 
+// Diagnostic ("dbg_stack_witness"): the HBM part of the stacks is filled with a word no traversal pushes before a launch, so that the words a
+// launch wrote can be counted afterwards (hpt_get_stack_witness). REF_NONE is that word: a push stores a child reference whose box the ray hit -
+// a node index, a leaf (both builders give every inner node two real children; the empty slots of a 4-wide node carry REF_NONE but their valid
+// bit is clear, and wideNodeStep pushes valid children only) - or REF_RESTORE; a popped REF_NONE would end the walk with the rest of its stack unread.
+// REF_RESTORE (all ones) IS pushed, hence the 32-bit fill. Off: no call, no fill.
+static const uint STACK_SENTINEL = REF_NONE;
+static hipError_t stackWitnessFill(hpt_ctx* c, hipStream_t st)
+{
+  c->witnessWords = 0;
+  if (!c->stackWitness || !c->dStackOvf.p || c->dStackOvf.n == 0) return hipSuccess;
+  c->witnessWords = c->dStackOvf.n;
+  return hipMemsetD32Async((hipDeviceptr_t)c->dStackOvf.p, (int)STACK_SENTINEL, c->dStackOvf.n, st);
+}
+
 // The traversal variant of the committed layout for the kernels that are built for five of them (rayQueryKernel, gbufferKernel, castSingleRayKernel,
 // rayTraceKernel): sweep; single-level with motion; single-level; two-level with motion; two-level. f gets (FLAT, MOTION, SWEEP) as
 // std::bool_constant objects, i.e. as compile-time constants. (The path-tracing ladders also switch on the stack depth and are their own.)
@@ -983,6 +998,7 @@ template <bool EVENTS = true, class Launch>
 static int launchFrame(hpt_ctx* c, size_t lanes, hipStream_t st, Launch launch)
 {
   HIPCHK(c, ensureStackOverflow(c, lanes));
+  if (c->stackWitness) HIPCHK(c, stackWitnessFill(c, st));
   if (EVENTS) HIPCHK(c, hipEventRecord(c->ev0, st));
   launch();
   HIPCHK(c, hipGetLastError());
@@ -1725,6 +1741,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   const int traceBlocks = c->numCUs * bpc;
   // HBM part of the traversal stacks: one slice per group (their trace kernels run concurrently)
   HIPCHK(c, ensureStackOverflow(c, (size_t)traceBlocks * 256 * nGroups));
+  if (c->stackWitness) HIPCHK(c, stackWitnessFill(c, st));          // (before wfFork is recorded on st: every group's stream waits for it)
   const size_t ovfPerGroup = c->dStackOvf.n / nGroups;
   const bool deep = c->stackNeeded > (uint)LDS_STACK;
   const bool stats = c->instrument;
@@ -3306,6 +3323,7 @@ try {
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
+  else if (k == "dbg_stack_witness") { c->stackWitness = value != 0; c->witnessWords = 0; }   // diagnostic: sentinel fill of the stacks' HBM part before every launch (hpt_get_stack_witness)
   else return c->fail(HPT_ERR_ARG, "hpt_set_option: unknown option " + k);
   return HPT_OK;
 }
@@ -3339,6 +3357,21 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_last_launch"); }
+extern "C" int hpt_get_stack_witness(hpt_ctx* c, uint64_t out[2])
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  out[0] = 0; out[1] = c->witnessWords;
+  if (c->witnessWords == 0 || !c->dStackOvf.p) return HPT_OK;
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipDeviceSynchronize());
+  std::vector<uint> h(std::min(c->witnessWords, c->dStackOvf.n));
+  HIPCHK(c, hipMemcpy(h.data(), c->dStackOvf.p, h.size() * sizeof(uint), hipMemcpyDeviceToHost));
+  uint64_t written = 0;
+  for (const uint w : h) written += w != STACK_SENTINEL ? 1u : 0u;
+  out[0] = written;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_get_stack_witness"); }
 extern "C" int hpt_set_accel_layout(hpt_ctx* c, int layout)
 try {
   if (!c || layout < 0 || layout > 3) return HPT_ERR_ARG;

@@ -557,7 +557,11 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *   "stats_wide"            1: the instrumented probe (hpt_set_instrumentation) counts the walk over the 4-wide tree
  *   "force_full_materials"  1: never pick the kernels specialised for gltf + emissive scenes (kernel studies)
  *   "dbg_no_normal_lerp"    1: moving instances without the reference's normal interpolation (integrator_pt.cpp:285-292); the checker has the
- *                           same switch (ORC_DBG_NO_NORMAL_LERP) - used to show where the rare path divergences under motion blur come from */
+ *                           same switch (ORC_DBG_NO_NORMAL_LERP) - used to show where the rare path divergences under motion blur come from
+ *   "dbg_stack_witness"     1: before every launch that walks a tree (path tracing under any schedule, ray queries, the G-buffer, primary-ray,
+ *                           Whitted, RayTraceDR, QMC, primary-sample-space and KMLT passes) the HBM part of the traversal stacks is filled, on the
+ *                           launch's stream, with a word no traversal pushes; hpt_get_stack_witness then counts the words the launch wrote. The
+ *                           kernels and their results are the same; 0 (default): no fill, nothing else either. For tests of the deep stacks */
 int  hpt_set_option(hpt_ctx* ctx, const char* name, int value);
 /* ---- multi-GPU: one context = one GPU = one rank -----------------------------------------------------
  * The path shards without a data-path exchange; these three calls are the only traffic over xGMI. RCCL is loaded on first use.
@@ -570,7 +574,6 @@ int  hpt_comm_init(hpt_ctx* ctx, int nranks, int rank, const void* id128);
 int  hpt_comm_destroy(hpt_ctx* ctx);
 int  hpt_reduce_framebuffer(hpt_ctx* ctx, float* frameDev, size_t count, int root, void* stream);
 int  hpt_allreduce_grad(hpt_ctx* ctx, float* gradDev, size_t count, void* stream);
-/* Schedule the last hpt_path_trace_block(_dev) call used (1 / 2) and, for the wavefront one, its number of shade+trace rounds. */
 /* What CommitScene built: out[0] = expected inner-node visits per ray (surface-area estimate over the committed BVH; the quantity the automatic
  * schedule / layout choice is measured against), out[1] = instanced triangles, out[2] = instances, out[3] = layout (0 two-level, 1 single-level, 2 triangle sweep). */
 int  hpt_get_accel_info(hpt_ctx* ctx, float out[4]);
@@ -579,11 +582,19 @@ int  hpt_get_accel_info(hpt_ctx* ctx, float out[4]);
  * with unchanged topology: boxes recomputed bottom-up by two small kernels, CrossRT.h:85-86, 134), 2 when it was BUILT on the device (out[2] = the
  * build's milliseconds) and 0 when it was built on the host. hpt_set_option("refit", 0) forces the build. */
 int  hpt_get_commit_time(hpt_ctx* ctx, float out[4]);
+/* Schedule the last hpt_path_trace_block(_dev) call used (1 .. 4, as hpt_set_schedule numbers them) and, for the wavefront one, its number of
+ * shade+trace rounds. */
 int  hpt_get_schedule(hpt_ctx* ctx, int* lastSchedule, uint32_t* lastIterations);
 /* What the last hpt_path_trace_* call walked (no counterpart in the reference: lets a test assert WHICH kernels produced a frame):
- * out[0] = schedule (1 / 2), out[1] = 1 when rays walked the 4-wide compressed tree, out[2] = 1 when surface data came from the 64-byte
+ * out[0] = schedule (1 .. 4), out[1] = 1 when rays walked the 4-wide compressed tree, out[2] = 1 when surface data came from the 64-byte
  * shading records, out[3] = 1 when the traversal stacks had an HBM part. */
 int  hpt_get_last_launch(hpt_ctx* ctx, uint32_t out[4]);
+/* With hpt_set_option("dbg_stack_witness", 1): out[0] = words of the traversal stacks' HBM part that no longer hold the fill word after the last
+ * launch, i.e. that a lane pushed (the stack entries beyond the ones kept in LDS), out[1] = words that were filled before it. Waits for the device,
+ * copies the buffer and counts on the host; it does not interpret the buffer's layout (the wavefront schedule's per-group slices count alike).
+ * Without the option both are 0. 'Last launch' is literal: a launch that walks no tree refills the buffer too (hpt_path_trace_kmlt_block_dev with
+ * normalize = 2, the normalisation alone), and after it out[0] is 0. */
+int  hpt_get_stack_witness(hpt_ctx* ctx, uint64_t out[2]);
 /* Duration of the last path-tracing or G-buffer kernel, measured with HIP events on the stream it ran on (ms). */
 int  hpt_last_kernel_ms(hpt_ctx* ctx, float* ms);
 

@@ -9,7 +9,7 @@ import pytest
 from conftest import assert_pixel_parity
 from hydracore3_amd import scene as S
 from hydracore3_amd.scene import INTEGRATOR_MIS_PT, INTEGRATOR_SHADOW_PT
-from traversal_scenes import (FAMILIES, FLT_MAX, NO_HIT, forced_sweep_scene, make_rays, reference_hits, sweep_scene, with_tfar,
+from traversal_scenes import (FAMILIES, FLT_MAX, NO_HIT, assert_hits_equal, forced_sweep_scene, make_rays, reference_hits, sweep_scene, with_tfar,
                               world_triangles)
 
 AUTO_SEEDS = (11, 12, 13)
@@ -31,16 +31,6 @@ def _rays(sc, cpu, n, seed):
     # oracle's BVH can return another triangle than its brute force at origins ~7e4 away.
     open_t = np.where((h["instId"] != NO_HIT) & (fam != FAMILIES.index("far")), h["t"], np.inf)
     return pos, with_tfar(pos, dr, open_t, seed + 1), fam
-
-
-def _assert_hits_equal(h, ref, what):
-    for f in ("primId", "instId", "geomId"):
-        bad = np.flatnonzero(h[f] != ref[f])
-        assert bad.size == 0, f"{what}: {f} differs on {bad.size} rays, first {bad[:8]}: {h[f][bad[:4]]} vs {ref[f][bad[:4]]}"
-    bad = np.flatnonzero(h["t"].view(np.uint32) != ref["t"].view(np.uint32))
-    assert bad.size == 0, f"{what}: t differs on {bad.size} rays, first {bad[:8]}: {h['t'][bad[:4]]} vs {ref['t'][bad[:4]]}"
-    hit = ref["geomId"] != NO_HIT
-    assert np.array_equal(h["coords"][hit][:, :3].view(np.uint32), ref["coords"][hit][:, :3].view(np.uint32)), f"{what}: coords"
 
 
 # ---- CPU: the oracle's BVH, its brute force and the float64 reference -------------------------------------------------------------------------
@@ -66,7 +56,7 @@ def test_oracle_bvh_and_brute_force_agree_with_float64(kind, seed):
     lost = np.flatnonzero((hn["t"].view(np.uint32) != hb["t"].view(np.uint32)) | (hn["primId"] != hb["primId"]) | (hn["instId"] != hb["instId"]))
     print(f"{kind} {seed}: oracle BVH != brute force on rays {lost} (tnear {pos[lost, 3]})")
     assert lost.size <= 1
-    _assert_hits_equal(hn[keep], hb[keep], "oracle BVH vs brute force")
+    assert_hits_equal(hn[keep], hb[keep], "oracle BVH vs brute force")
     assert np.array_equal(an[keep], ab[keep]) and np.sum(an != ab) <= 1
     behind = robust & hit & (t < 0.0)
     print(f"{kind} {seed}: {robust.mean():.1%} robust, {int((robust & hit).sum())} robust hits ({int(behind.sum())} behind the origin), "
@@ -117,7 +107,7 @@ def test_every_layout_returns_the_brute_force_hits(kind, seed):
     hb, ab = cpu.ray_nearest(pos, dr, brute=True), cpu.ray_any(pos, dr, brute=True)
     assert (hb["instId"] != NO_HIT).mean() > 0.2 and ((hb["instId"] != NO_HIT) & (hb["t"] < 0)).sum() > 300
     for name, g in _variants(sc, "sweep" if kind == "auto" else "flat"):
-        _assert_hits_equal(g.RayQuery_NearestHit(pos, dr), hb, f"{kind} {seed}, {name}")
+        assert_hits_equal(g.RayQuery_NearestHit(pos, dr), hb, f"{kind} {seed}, {name}")
         a = g.RayQuery_AnyHit(pos, dr)
         bad = np.flatnonzero(a != ab)
         assert bad.size == 0, f"{kind} {seed}, {name}: any-hit differs on {bad.size} rays, first {bad[:8]}"
@@ -149,7 +139,7 @@ def test_wide_and_device_built_trees_keep_hits_behind_the_origin():
         assert g.commit_time()["device_built"]
         variants.append((f"device build, wide_nodes {w}", g))
     for name, g in variants:
-        _assert_hits_equal(g.RayQuery_NearestHit(pos, dr), hb, f"interior, {name}")
+        assert_hits_equal(g.RayQuery_NearestHit(pos, dr), hb, f"interior, {name}")
         assert np.array_equal(g.RayQuery_AnyHit(pos, dr), ab), name
 
 
@@ -168,7 +158,7 @@ def test_moving_instances_keep_hits_behind_the_origin():
     behind = 0
     for time in (0.0, 0.4, 1.0):
         hb = cpu.ray_nearest_motion(pos, dr, time, brute=True)
-        _assert_hits_equal(gpu.RayQuery_NearestHitMotion(pos, dr, time), hb, f"motion, time {time}")
+        assert_hits_equal(gpu.RayQuery_NearestHitMotion(pos, dr, time), hb, f"motion, time {time}")
         assert np.array_equal(gpu.RayQuery_AnyHitMotion(pos, dr, time), cpu.ray_any_motion(pos, dr, time, brute=True))
         behind += int(((hb["instId"] != NO_HIT) & (hb["t"] < -1.0)).sum())
     assert behind > 300

@@ -238,6 +238,17 @@ def reference_hits(tris, ids, inst_matrices, pos, dr, chunk=2048):
     return out_hit, out_t, out_inst, out_prim, robust
 
 
+def assert_hits_equal(h, ref, what):
+    """Two hit arrays (RayQuery_NearestHit / ray_nearest records) equal bit for bit: ids, t, and the coordinates of the rays that hit."""
+    for f in ("primId", "instId", "geomId"):
+        bad = np.flatnonzero(h[f] != ref[f])
+        assert bad.size == 0, f"{what}: {f} differs on {bad.size} rays, first {bad[:8]}: {h[f][bad[:4]]} vs {ref[f][bad[:4]]}"
+    bad = np.flatnonzero(h["t"].view(np.uint32) != ref["t"].view(np.uint32))
+    assert bad.size == 0, f"{what}: t differs on {bad.size} rays, first {bad[:8]}: {h['t'][bad[:4]]} vs {ref['t'][bad[:4]]}"
+    hit = ref["geomId"] != NO_HIT
+    assert np.array_equal(h["coords"][hit][:, :3].view(np.uint32), ref["coords"][hit][:, :3].view(np.uint32)), f"{what}: coords"
+
+
 # ---- rays ---------------------------------------------------------------------------------------------------------------------------------------
 FAMILIES = ("random", "aimed", "grazing", "offset", "axis", "far")
 TNEARS = (0.0, None, -1.0, -1e2, -1e4, -float(FLT_MAX))                   # None: a random tnear > 0
@@ -322,3 +333,114 @@ def with_tfar(pos, dr, open_t, seed):
     out = dr.copy()
     out[:, 3] = np.select([k == 0, k == 1, k == 2], [np.full(n, FLT_MAX), rnd, exact], below).astype(np.float32)
     return out
+
+
+# ---- nested sheets: trees deeper than the LDS part of the traversal stacks ------------------------------------------------------------------------
+NESTED_TRI_CAP = 32768                     # instanced triangles
+
+
+def nested_sheets(n=8000, ratio=1.0015, a0=0.03, dz=3e-4, instances=1, width=96, height=64, spectral=False, emissive=False):
+    """n right triangles in the planes z = i dz, triangle i larger than triangle i - 1 by `ratio` (legs 2 a0 ratio^i), every hypotenuse on the line
+    x + y = 0 through the z axis and the boxes' centres (a_i / 2, -a_i / 2) moving away from it with the size: a ray along z at a distance
+    below a0 / 2 from the axis lies in every triangle's box - hence in every node's - and meets every triangle (x + y < 0) or none (x + y > 0).
+    The binned SAH build peels the few largest sheets off at every level, so the tree is far deeper than log2(n / 4): 8000 sheets at 1.0015 give
+    a BVH2 of depth 18 and a 4-wide tree of depth 16 (stack bounds 19 and 49; the LDS part holds 16). instances > 1: the same mesh that many
+    times, instance k scaled by 1.5^k in x and y and its stack of sheets put behind the one before. All materials gltf (the second one
+    textured: texture 1, 8 x 8) or emissive; one large emissive sheet behind the camera lights the scene; the camera sits on the small end and
+    looks along +z. emissive: every sheet an emitter of one of three colours instead, no light, trace depth 1 - a sample's colour is then the
+    emission its primary ray meets (what the QMC pass can be held to the oracle on). Other sizes used by the tests (host build, BVH2 / 4-wide
+    depth): 20 000 sheets at 1.0006: 19 / 17; 4 000 at 1.003 x 8 instances: 24 / 20. The parameters are returned in sc.nested."""
+    assert n * instances + 2 <= NESTED_TRI_CAP
+    sc = S.SceneData()
+    sc.width, sc.height = width, height
+    if spectral:
+        sc.spectral_mode = 1
+        sc.spec_offset_sz, sc.spec_values = [(0, 471)], np.ones(471, np.float32)
+    sc.cam_pos, sc.cam_look_at, sc.cam_up = (0.0, 0.0, -0.3), (0.0, 0.0, 1.0), (0.0, 1.0, 0.0)
+    sc.fov, sc.trace_depth = 20.0, 4
+    sc.env_color = (0.05, 0.06, 0.08, 0.0)
+    rng = np.random.default_rng(n)
+    img = rng.integers(0, 2 ** 32, (8, 8), dtype=np.uint64).astype(np.uint32) | np.uint32(0xFF000000)
+    tex = sc.add_texture(S.Texture(img, S.TEX_RGBA8, True))
+    M = sc.materials
+    M.append(S.material_gltf((0.7, 0.65, 0.6, 1.0), 0.0, 0.3))
+    M.append(S.material_gltf((0.8, 0.8, 0.8, 1.0), 0.0, 0.5, 1.0, 1.5, tex))
+    M.append(S.material_gltf((0.9, 0.9, 0.9, 1.0), 1.0, 0.9))
+    emis = len(M)
+    a = a0 * ratio ** np.arange(n)
+    z = dz * np.arange(n)
+    p = np.empty((n, 3, 3))
+    p[:, 0] = np.stack([-a / 2, -3 * a / 2, z], 1)
+    p[:, 1] = np.stack([3 * a / 2, -3 * a / 2, z], 1)
+    p[:, 2] = np.stack([-a / 2, a / 2, z], 1)
+    pos4 = np.concatenate([p.reshape(-1, 3), np.ones((3 * n, 1))], 1).astype(np.float32)
+    nrm = np.tile([0.0, 0.0, -1.0, 0.0], (3 * n, 1)).astype(np.float32)
+    tng = np.tile([1.0, 0.0, 0.0, 0.0], (3 * n, 1)).astype(np.float32)
+    uv = np.tile([[0.0, 0.0], [1.0, 0.0], [0.0, 1.0]], (n, 1)).astype(np.float32)
+    g = sc.add_mesh(pos4, nrm, tng, uv, np.arange(3 * n, dtype=np.uint32), (np.arange(n) % 3).astype(np.uint32))
+    depth = n * dz
+    for k in range(instances):
+        sc.add_instance(g, S.translate(0.0, 0.0, k * depth) @ S.scale(1.5 ** k, 1.5 ** k, 1.0))
+    sc.nested = {"n": n, "ratio": ratio, "a0": a0, "dz": dz, "instances": instances, "z_end": instances * depth, "a_max": float(a[-1]) * 1.5 ** (instances - 1)}
+    if emissive:
+        sc.materials = [S.material_emissive(c, mult=m) for c, m in (((0.9, 0.2, 0.1), 1.0), ((0.1, 0.8, 0.3), 1.25), ((0.3, 0.4, 1.2), 1.5))]
+        sc.trace_depth = 1
+        sc.env_color = (0.125, 0.25, 0.5, 0.0)
+        return sc
+    lm = S.translate(0.0, 0.0, -2.0) @ S.rotate_x(-90.0)
+    sc.lights.append(S.light_rect(lm, 3.0, 3.0, (1.0, 0.95, 0.9), 6.0))
+    M.append(S.material_emissive((1.0, 0.95, 0.9), 6.0, 0))
+    sc.lights[0]["matId"] = emis
+    _add_emitter(sc, lm, emis)
+    return sc
+
+
+def _add_emitter(sc, lm, mat):
+    p = np.array([[-3, 0, -3], [3, 0, -3], [3, 0, 3], [-3, 0, 3]], float)
+    pos4 = np.concatenate([p, np.ones((4, 1))], 1).astype(np.float32)
+    nrm = np.tile([0.0, -1.0, 0.0, 0.0], (4, 1)).astype(np.float32)
+    tng = np.tile([1.0, 0.0, 0.0, 0.0], (4, 1)).astype(np.float32)
+    uv = np.array([[0, 0], [1, 0], [1, 1], [0, 1]], np.float32)
+    g = sc.add_mesh(pos4, nrm, tng, uv, np.array([0, 1, 2, 0, 2, 3], np.uint32), np.full(2, mat, np.uint32))
+    sc.add_instance(g, lm, -1, 0)
+
+
+NESTED_FAMILIES = ("covered", "empty", "covered tilted", "empty tilted", "outer covered", "outer empty")
+
+
+def nested_rays(sc, n, seed, near=0.5):
+    """Rays for nested_sheets, float32 pos (n, 4), dir (n, 4) and the family of each. Near the axis (distance a0 10^-2.5 .. a0 / 10: inside
+    every box), through the covered half (x + y < 0: every sheet is hit, the closest-hit order matters) or the empty half of the boxes
+    (x + y > 0: every node is visited, nothing is hit), along +z (most) or -z or tilted by 1e-4 .. 3e-2 rad about the point where they cross the
+    middle of the stack; and, for the float64 reference, which cannot call a ray robust that passes a_max / 10^5 from an edge of the largest
+    sheets, the same two kinds further out (a_max / 300 .. a_max / 4, along the axis only; the share 1 - near of all rays). Origins in front of the stack, behind it, or (a quarter to a sixth)
+    inside it, where the negative tnear of TNEARS finds sheets behind the origin. tfar = FLT_MAX (with_tfar sets others)."""
+    q = sc.nested
+    rng = np.random.default_rng(seed)
+    fam = rng.choice(len(NESTED_FAMILIES), n, p=[near / 4] * 4 + [(1.0 - near) / 2] * 2)
+    outer = fam >= 4
+    empty = (fam % 2) == 1
+    r = np.where(outer, q["a_max"] * 10.0 ** rng.uniform(-2.5, -0.6, n), q["a0"] * 10.0 ** rng.uniform(-2.5, -1.0, n))
+    # covered: a direction between -x and -y, where the triangle's own box ends furthest out; empty: between +x and the hypotenuse (y <= a / 2 there)
+    phi = np.where(empty, rng.uniform(-0.6, 0.6, n), np.pi + np.pi / 4 + rng.uniform(-0.5, 0.5, n))
+    x, y = r * np.cos(phi), r * np.sin(phi) * np.where(empty, 0.3, 1.0)
+    sgn = np.where(rng.uniform(size=n) < np.where(outer, 0.5, 0.85), 1.0, -1.0)   # (from the small end the walk descends the whole unbalanced tree before its first leaf: the deepest stacks)
+    d = np.zeros((n, 3)); d[:, 2] = sgn
+    tilt = ((fam == 2) | (fam == 3))
+    ang = 10.0 ** rng.uniform(-4.0, -1.5, n) * tilt
+    psi = rng.uniform(0.0, 2.0 * np.pi, n)
+    d[:, 0], d[:, 1] = np.tan(ang) * np.cos(psi), np.tan(ang) * np.sin(psi)
+    d = _unit(d)
+    zmid = 0.5 * q["z_end"]
+    inside = rng.uniform(size=n) < np.where(outer, 0.25, 0.15)
+    oz = np.where(inside, rng.uniform(0.0, q["z_end"], n), np.where(sgn > 0, -0.25, q["z_end"] + 0.25))
+    s = (oz - zmid) / d[:, 2]                                             # the ray passes (x, y, zmid)
+    org = np.stack([x + d[:, 0] * s, y + d[:, 1] * s, oz], 1)
+    pos, dr = np.zeros((n, 4), np.float32), np.zeros((n, 4), np.float32)
+    pos[:, :3], dr[:, :3] = org, d
+    tk = rng.integers(0, len(TNEARS), n)
+    tn = np.array([0.0 if TNEARS[j] is None else TNEARS[j] for j in tk])
+    tn[tk == 1] = rng.uniform(0.0, 1.0, (tk == 1).sum()) * (q["z_end"] + 0.25)
+    pos[:, 3] = tn.astype(np.float32)
+    dr[:, 3] = FLT_MAX
+    return pos, dr, fam
