@@ -91,6 +91,8 @@ ABI = {
     "hpt_get_accel_info": (_i, [_vp, C.POINTER(_f)]),
     "hpt_set_option": (_i, [_vp, C.c_char_p, _i]),
     "hpt_get_commit_time": (_i, [_vp, C.POINTER(_f)]),
+    "hpt_get_refit_info": (_i, [_vp, C.POINTER(_f)]),
+    "hpt_read_accel": (_i, [_vp, _i, _vp, _u64, C.POINTER(_u64), C.POINTER(_u32)]),
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
     "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
@@ -129,6 +131,11 @@ GBUFFER_SAMPLES = 16
 GBUFFER_DTYPE = np.dtype([("depth", np.float32), ("norm", np.float32, (3,)), ("texc", np.float32, (2,)), ("rgba", np.float32, (4,)),
                           ("shadow", np.float32), ("coverage", np.float32), ("matId", np.int32), ("objId", np.int32), ("instId", np.int32)])
 assert GBUFFER_DTYPE.itemsize == 60
+
+# the single-level tree as hpt_read_accel returns it (hpt_types.h: BvhNode, BvhTri)
+BVH_NODE_DTYPE = np.dtype([("q", np.float32, (12,)), ("ref0", np.uint32), ("ref1", np.uint32), ("pad0", np.uint32), ("pad1", np.uint32)])
+BVH_TRI_DTYPE = np.dtype([("v0", np.float32, (3,)), ("primId", np.uint32), ("e1", np.float32, (3,)), ("instId", np.uint32), ("e2", np.float32, (3,)), ("pad1", np.uint32)])
+assert BVH_NODE_DTYPE.itemsize == 64 and BVH_TRI_DTYPE.itemsize == 48
 
 
 
@@ -722,6 +729,35 @@ class HipIntegrator:
         out = (C.c_float * 4)()
         self._chk(self.L.hpt_get_commit_time(self.h, out))
         return {"host_ms": out[0], "upload_ms": out[1], "refit_ms": out[2], "device_ms": out[2], "refitted": int(out[3]) == 1, "device_built": int(out[3]) == 2}
+
+    def refit_info(self):
+        """hpt_get_refit_info: the surface-area estimate at build time and after the last refit (equal when the last commit was a build), the levels
+        a refit launches (0: the tree cannot be refitted) and whether "refit_max_sah_pct" rejected the last commit's refit."""
+        out = (C.c_float * 4)()
+        self._chk(self.L.hpt_get_refit_info(self.h, out))
+        return {"build": out[0], "after": out[1], "levels": int(out[2]), "rejected": int(out[3]) == 1}
+
+    def read_accel(self):
+        """hpt_read_accel: the committed single-level tree as it lies in device memory: (nodes [BVH_NODE_DTYPE], tris [BVH_TRI_DTYPE], rootRef).
+        A device-built tree's node array has unused entries: only what rootRef reaches is a node."""
+        out = []
+        root = C.c_uint32(0)
+        for what, dt in ((0, BVH_NODE_DTYPE), (1, BVH_TRI_DTYPE)):
+            nbytes = C.c_uint64(0)
+            self._chk(self.L.hpt_read_accel(self.h, what, None, 0, C.byref(nbytes), C.byref(root)))
+            a = np.zeros(nbytes.value // dt.itemsize, dt)
+            if a.size:
+                self._chk(self.L.hpt_read_accel(self.h, what, a.ctypes.data, a.nbytes, C.byref(nbytes), C.byref(root)))
+            out.append(a)
+        return out[0], out[1], int(root.value)
+
+    def UpdateGeom_Triangles3f(self, geom_id, vpos, indices):
+        """ISceneObject::UpdateGeom_Triangles3f (CrossRT.h:85-86): new positions (float32 [n, 3] or [n, 4]) and indices for a mesh; takes effect at the
+        next CommitScene. Unchanged indices keep a committed single-level tree refittable."""
+        vpos = np.ascontiguousarray(vpos, np.float32)
+        assert vpos.ndim == 2 and vpos.shape[1] in (3, 4)
+        indices = np.ascontiguousarray(indices, np.uint32).reshape(-1)
+        self._chk(self.L.hpt_update_geom_triangles3f(self.h, geom_id, vpos.ctypes.data, vpos.shape[0], indices.ctypes.data, indices.size, 0, 4 * vpos.shape[1]))
 
     def UpdateInstance(self, inst_id, matrix_rowmajor):
         """ISceneObject::UpdateInstance (CrossRT.h:134); takes effect at the next CommitScene."""

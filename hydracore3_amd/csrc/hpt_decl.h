@@ -321,6 +321,7 @@ __global__ void adamStepKernel(float* state, const float* grad, float* momentum,
 __global__ void refitTriBoxesKernel(const BvhTri* tris, const float* instMat, uint n, float* triBox);
 __global__ void refitLevelKernel(BvhNode* nodes, const uint* ids, uint count, const float* triBox, float* bounds);
 __global__ void refitNodes4Kernel(BvhNode4* nodes4, const uint* src, const BvhNode* nodes2, uint count);
+__global__ void __launch_bounds__(256) refitSahKernel(const BvhNode* nodes, const uint* ids, uint count, uint rootId, double* out);   // out[0] += the inner children's half-areas, out[1] = the root's
 __global__ void buildShadeTrisKernel(const DevScene S, uint n, float4* out);
 
 } // namespace hpt

@@ -212,5 +212,31 @@ __global__ void refitLevelKernel(BvhNode* nodes, const uint* ids, uint count, co
   for (int a = 0; a < 3; a++) { o[2 * a] = nlo[a]; o[2 * a + 1] = nhi[a]; }
   nodes[id] = nd;
 }
+// The refitted tree's cost (hpt_get_refit_info): the numerator of the surface-area estimate sah_node_visits computes at build time. One lane per
+// node of the level lists; every inner child adds the half-area of its padded box, a float expression, to a DOUBLE sum: reduced over the wave
+// by shuffles, one atomicAdd(double) per wave. The lane that meets the root leaves the half-area of the root's box - the union of its two
+// padded child boxes - in out[1]. The host divides and adds the root's own visit.
+__global__ void __launch_bounds__(256) refitSahKernel(const BvhNode* nodes, const uint* ids, uint count, uint rootId, double* out)
+{
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  double sum = 0.0;
+  if (i < count) {
+    const uint id = ids[i];
+    const BvhNode nd = nodes[id];
+    float ulo[3] = { HPT_FLT_MAX, HPT_FLT_MAX, HPT_FLT_MAX }, uhi[3] = { -HPT_FLT_MAX, -HPT_FLT_MAX, -HPT_FLT_MAX };
+    for (int c = 0; c < 2; c++) {
+      const uint ref = c ? nd.ref1 : nd.ref0;
+      if (ref == REF_NONE) continue;
+      const float* q = nd.q + 6 * c;
+      for (int a = 0; a < 3; a++) { ulo[a] = fminf(ulo[a], q[2 * a]); uhi[a] = fmaxf(uhi[a], q[2 * a + 1]); }
+      if (ref & REF_LEAF) continue;
+      const float dx = q[1] - q[0], dy = q[3] - q[2], dz = q[5] - q[4];
+      if (dx >= 0.0f) sum += (double)(dx * dy + dy * dz + dz * dx);
+    }
+    if (id == rootId) { const float dx = uhi[0] - ulo[0], dy = uhi[1] - ulo[1], dz = uhi[2] - ulo[2]; out[1] = (double)(dx * dy + dy * dz + dz * dx); }
+  }
+  for (int o = 32; o > 0; o >>= 1) sum += __shfl_down(sum, o);
+  if ((threadIdx.x & 63u) == 0u && sum != 0.0) atomicAdd(&out[0], sum);
+}
 
 } // namespace hpt

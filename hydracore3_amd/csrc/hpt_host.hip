@@ -142,6 +142,12 @@ struct hpt_ctx
   bool flatRefittable = false;                           // a single-level tree is committed and nothing but instance matrices / vertex positions changed since
   std::vector<uint> dirtyGeoms;                          // meshes whose vertices changed since the last commit (UpdateGeom_Triangles3f)
   bool refitEnabled = true;                              // hpt_set_option("refit", 0): always rebuild
+  bool deviceRefit = false;                              // hpt_set_option("device_refit", 1): a device build leaves its level lists behind and an update of its tree is a refit
+  bool flatOnDevice = false;                             // the committed single-level tree was built by hpt_lbvh.hip: no host copy of its records (flatTris), dNodes indexed by Karras node
+  size_t flatNodes = 0;                                  // entries of dNodes that belong to the committed single-level tree (hpt_read_accel)
+  int  refitMaxSahPct = 0;                               // hpt_set_option("refit_max_sah_pct", p): a refit whose estimate exceeds p % of the build's is followed by a build (0: never)
+  float sahRefit = 0.0f; bool refitRejected = false;     // hpt_get_refit_info: the estimate after the last refit; the last commit's refit was rejected by the guard
+  DevBuf<double> dRefitSah;                              // refitSahKernel's two results
   float tCommit[4] = {0, 0, 0, 0};                       // last CommitScene: host build ms, upload ms, device refit ms, 1 = refit / 0 = build
   float sahVisits = 0.0f;                                // expected inner-node visits per ray of the committed structure (sah_node_visits)
   bool anyMotion = false;                                // some instance moves: the MOTION kernel variants (either BVH layout, either schedule; no sweep, no refit)
@@ -565,6 +571,14 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   const bool wantWide = true;
   HIPCHK(c, c->dNodes4.alloc(std::max<size_t>(n, 1)));
   HIPCHK(c, c->dInsts.upload(dinst.data(), dinst.size()));
+  LbvhRefitOut refit;                                        // "device_refit": the build groups its nodes by level and remembers where the 4-wide boxes come from
+  if (c->deviceRefit) {
+    HIPCHK(c, c->dLevelNodes.alloc(std::max<size_t>(n, 1)));
+    HIPCHK(c, c->dNodes4Src.alloc(4 * c->dNodes4.n));
+    HIPCHK(c, c->dTriBox.alloc(6 * std::max<size_t>(n, 1)));
+    HIPCHK(c, c->dNodeBounds.alloc(6 * std::max<size_t>(n, 1)));
+    refit.levelIds = c->dLevelNodes.p; refit.src4 = c->dNodes4Src.p;
+  }
   {                                                          // (both layouts' kernels read the motion rows' pointer; none of these instances moves)
     std::vector<float> mo(24 * std::max<size_t>(ni, 1), 0.0f);
     for (size_t i = 0; i < ni; i++) for (int key = 0; key < 2; key++) for (int k = 0; k < 12; k++) mo[24 * i + 12 * (size_t)key + k] = li[i].objectToWorld[k];
@@ -573,7 +587,7 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   }
   const double tDev0 = now_ms();
   LbvhResult r;
-  if (!lbvhBuild(c->lbvh, li.data(), (uint)ni, n, c->dNodes.p, c->dTris.p, c->dNodes4.p, (uint)c->dNodes4.n, wantWide, r, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build): " + err);
+  if (!lbvhBuild(c->lbvh, li.data(), (uint)ni, n, c->dNodes.p, c->dTris.p, c->dNodes4.p, (uint)c->dNodes4.n, wantWide, refit, r, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build): " + err);
   const double tDev1 = now_ms();
   if (r.depth + 1u > MAX_STACK) return HPT_ERR_STATE;         // a degenerate input (the Morton curve cannot separate it): the host's depth-capped build takes over
   c->instTris = instTris; c->anyMotion = false;
@@ -584,7 +598,11 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
     c->S.nodes4 = c->dNodes4.p; c->S.root4 = 0u;
     c->S.megaWide = (c->wideEnabled && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u;
   }
-  c->flatTris.clear(); c->flatRefittable = false;             // (an update is answered by another device build, not by a refit)
+  // an update is answered by another device build unless "device_refit" had the build leave its level lists: then by refit_flat, like a host-built tree's
+  c->flatTris.clear(); c->flatOnDevice = true; c->flatNodes = r.numNodes;
+  c->levelOffsets.assign(1, 0u);
+  for (uint l = 0; l < r.numLevels; l++) c->levelOffsets.push_back(c->levelOffsets.back() + r.levelCount[l]);
+  c->flatRefittable = r.numLevels != 0u && (r.rootRef & REF_LEAF) == 0u && c->levelOffsets.back() <= c->dLevelNodes.n;
   c->S.nodes = c->dNodes.p; c->S.tris = c->dTris.p; c->S.insts = c->dInsts.p;
   c->S.rootRef = r.rootRef; c->S.numInsts = (uint)ni; c->S.flatMode = 1; c->S.sweep = 0; c->S.sweepInsts = nullptr; c->S.sweepTris = nullptr;
   c->S.nodeMin = c->nodeMinOverride >= 0 ? (uint)c->nodeMinOverride : (c->sahVisits >= HEAVY_SAH_VISITS ? 16u : 0u);
@@ -597,6 +615,11 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   return HPT_OK;
 }
 
+static const int HPT_REFIT_REJECTED = -1;                     // refit_flat: the refitted tree's estimate is over "refit_max_sah_pct"; hpt_commit_scene builds instead
+
+// One body for both trees. They differ in where the moved vertices' records are rewritten: a host-built tree has a host copy of its records
+// (flatTris) that is patched and uploaded whole, a device-built tree has none - its meshes' positions are copied to the builder's device copy
+// (the changed meshes only) and a kernel rewrites the records in place (lbvhUpdatePositions).
 static int refit_flat(hpt_ctx* c)
 {
   const double t0 = now_ms();
@@ -607,9 +630,9 @@ static int refit_flat(hpt_ctx* c)
     dinst[i].root = REF_NONE; dinst[i].geomId = c->insts[i].geomId; dinst[i].pad0 = dinst[i].pad1 = 0;
   }
   std::vector<float> o2w; inst_o2w_rows(c->insts, o2w);
-  if (!c->dirtyGeoms.empty()) {                                 // moved vertices: the object-space records (v0, e1, e2) of those meshes' triangles
-    std::vector<char> dirty(c->geoms.size(), 0);
-    for (uint g : c->dirtyGeoms) if (g < dirty.size()) dirty[g] = 1;
+  std::vector<char> dirty(c->geoms.size(), 0);
+  for (uint g : c->dirtyGeoms) if (g < dirty.size()) dirty[g] = 1;
+  if (!c->dirtyGeoms.empty() && !c->flatOnDevice) {             // moved vertices: the object-space records (v0, e1, e2) of those meshes' triangles
     for (BvhTri& t : c->flatTris) {
       const uint gi = c->insts[t.instId].geomId;
       if (!dirty[gi]) continue;
@@ -617,12 +640,20 @@ static int refit_flat(hpt_ctx* c)
       const float* A = &g.pos[3 * g.idx[3 * t.primId + 0]]; const float* B = &g.pos[3 * g.idx[3 * t.primId + 1]]; const float* C = &g.pos[3 * g.idx[3 * t.primId + 2]];
       for (int a = 0; a < 3; a++) { t.v0[a] = A[a]; t.e1[a] = B[a] - A[a]; t.e2[a] = C[a] - A[a]; }
     }
-    for (uint g : c->dirtyGeoms) if (g < c->geoms.size()) c->geoms[g].dirty = true;   // a later two-level build must redo these BLAS
   }
+  for (uint g : c->dirtyGeoms) if (g < c->geoms.size()) c->geoms[g].dirty = true;   // a later two-level build must redo these BLAS
   const double t1 = now_ms();
   HIPCHK(c, c->dInsts.upload(dinst.data(), dinst.size()));
   HIPCHK(c, c->dInstO2W.upload(o2w.data(), o2w.size()));
-  if (!c->dirtyGeoms.empty()) HIPCHK(c, c->dTris.upload(c->flatTris.data(), c->flatTris.size()));
+  if (!c->dirtyGeoms.empty() && !c->flatOnDevice) HIPCHK(c, c->dTris.upload(c->flatTris.data(), c->flatTris.size()));
+  if (!c->dirtyGeoms.empty() && c->flatOnDevice) {
+    std::vector<uint> moved; std::vector<const float*> pos; std::vector<size_t> posN; std::vector<unsigned char> instDirty(std::max<size_t>(ni, 1), 0);
+    for (size_t g = 0; g < c->geoms.size(); g++) { pos.push_back(c->geoms[g].pos.data()); posN.push_back(c->geoms[g].pos.size()); if (dirty[g]) moved.push_back((uint)g); }
+    for (size_t i = 0; i < ni; i++) instDirty[i] = dirty[c->insts[i].geomId] ? 1 : 0;
+    std::string err;
+    if (!lbvhUpdatePositions(c->lbvh, moved, pos, posN, c->lbvhPosOff, instDirty.data(), (uint)ni, (uint)c->instTris, c->dTris.p, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device refit): " + err);
+    c->lbvhGeomVersion = c->geomVersion;                        // (a refittable tree: nothing but these positions changed since the geometry was uploaded)
+  }
   c->dirtyGeoms.clear();
   const double t2 = now_ms();
   const uint nt = (uint)c->instTris;
@@ -632,9 +663,18 @@ static int refit_flat(hpt_ctx* c)
     if (cnt) refitLevelKernel<<<dim3((cnt + 255u) / 256u), dim3(256), 0, 0>>>(c->dNodes.p, c->dLevelNodes.p + c->levelOffsets[l], cnt, c->dTriBox.p, c->dNodeBounds.p);
   }
   if (c->nodes4Count) refitNodes4Kernel<<<dim3((c->nodes4Count + 255u) / 256u), dim3(256), 0, 0>>>(c->dNodes4.p, c->dNodes4Src.p, c->dNodes.p, c->nodes4Count);
+  // the refitted tree's cost (hpt_get_refit_info): reported and, under "refit_max_sah_pct", compared; the schedule keeps following the build's estimate
+  const uint nn = c->levelOffsets.back();
+  HIPCHK(c, c->dRefitSah.alloc(2));
+  HIPCHK(c, hipMemsetAsync(c->dRefitSah.p, 0, 2 * sizeof(double), 0));
+  if (nn) refitSahKernel<<<dim3((nn + 255u) / 256u), dim3(256), 0, 0>>>(c->dNodes.p, c->dLevelNodes.p, nn, c->S.rootRef, c->dRefitSah.p);
   HIPCHK(c, hipGetLastError());
+  double sah[2] = { 0.0, 0.0 };
+  HIPCHK(c, hipMemcpy(sah, c->dRefitSah.p, sizeof(sah), hipMemcpyDeviceToHost));
   HIPCHK(c, hipDeviceSynchronize());
   c->S.insts = c->dInsts.p;
+  c->sahRefit = sah[1] > 0.0 ? (float)(1.0 + sah[0] / sah[1]) : 0.0f;
+  if (c->refitMaxSahPct > 0 && (double)c->sahRefit * 100.0 > (double)c->refitMaxSahPct * (double)c->sahVisits) { c->refitRejected = true; return HPT_REFIT_REJECTED; }
   c->tCommit[0] = float(t1 - t0); c->tCommit[1] = float(t2 - t1); c->tCommit[2] = float(now_ms() - t2); c->tCommit[3] = 1.0f;
   c->accelCommitted = true; c->shadeTrisDirty = true;
   return HPT_OK;
@@ -644,7 +684,13 @@ extern "C" int hpt_commit_scene(hpt_ctx* c, uint32_t options)
 try {
   if (!c) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
-  if (c->flatRefittable && c->refitEnabled && c->S.flatMode == 1u) return refit_flat(c);
+  c->refitRejected = false;
+  int onDevice = -1;                                         // 1 / 0: a rejected refit is followed by a build of the kind the tree came from
+  if (c->flatRefittable && c->refitEnabled && c->S.flatMode == 1u && (!c->flatOnDevice || c->deviceRefit)) {
+    const int rc = refit_flat(c);
+    if (rc != HPT_REFIT_REJECTED) return rc;
+    onDevice = c->flatOnDevice ? 1 : 0;
+  }
   const double tBuild0 = now_ms();
   c->dirtyGeoms.clear();
   {
@@ -655,7 +701,7 @@ try {
     const bool wantFlat = nTris <= FLAT_TRI_BUDGET && nTris < (size_t(1) << 28) && !moving &&
                           (c->accelLayout == 2 || (c->accelLayout == 0 && (nTris >= FLAT_AUTO_TRIS || c->insts.size() >= MANY_INSTANCES)));
     const bool fast = (options & 3u) != 0u && (options & 4u) == 0u;
-    if (wantFlat && nTris > 0 && (c->deviceBuild == 1 || (c->deviceBuild < 0 && fast))) {
+    if (wantFlat && nTris > 0 && (onDevice == 1 || (onDevice < 0 && (c->deviceBuild == 1 || (c->deviceBuild < 0 && fast))))) {
       const int rc = commit_flat_on_device(c, nTris, tBuild0);
       if (rc != HPT_ERR_STATE) return rc;                    // (HPT_ERR_STATE: the tree came out deeper than the traversal stack - the host's depth-capped build takes over)
     }
@@ -817,7 +863,7 @@ try {
       HIPCHK(c, c->dLevelNodes.upload(ids.data(), ids.size()));
       HIPCHK(c, c->dTriBox.alloc(6 * std::max<size_t>(instTris, 1)));
       HIPCHK(c, c->dNodeBounds.alloc(6 * std::max<size_t>(tree.nodes.size(), 1)));
-      c->flatTris.swap(tris);
+      c->flatTris.swap(tris); c->flatOnDevice = false; c->flatNodes = tree.nodes.size();
       c->flatRefittable = tree.rootRef != REF_NONE && !(tree.rootRef & REF_LEAF) && instTris > 0 && !c->anyMotion;   // (the refit kernels know one key only)
     }
     c->tCommit[0] = float(tUp0 - tBuild0 + collapseMs); c->tCommit[1] = float(now_ms() - tUp0 - collapseMs); c->tCommit[2] = 0.0f; c->tCommit[3] = 0.0f;   // the collapse is host build time
@@ -944,7 +990,7 @@ try {
   c->S.nodes = c->dNodes.p; c->S.tris = c->dTris.p; c->S.insts = c->dInsts.p;
   c->S.rootRef = rootRef; c->S.numInsts = (uint)ni; c->S.flatMode = 0;
   c->nodes4Count = 0; c->stackNeeded4 = 0; c->S.nodes4 = nullptr; c->S.root4 = REF_NONE; c->S.statsWide = 0; c->S.megaWide = 0; c->S.nodeMin4 = 0;
-  c->flatRefittable = false;
+  c->flatRefittable = false; c->flatOnDevice = false; c->flatNodes = 0; c->levelOffsets.assign(1, 0u);
   c->tCommit[0] = float(now_ms() - tBuild0); c->tCommit[1] = 0.0f; c->tCommit[2] = 0.0f; c->tCommit[3] = 0.0f;
   c->stackNeeded = tlas.depth + 1u + maxBlasDepth + 1u;
   if (std::getenv("HPT_DEBUG_ACCEL")) std::fprintf(stderr, "[hydra_hip] two-level BVH: %zu instances, TLAS depth %u, deepest BLAS %u, stack %u (LDS part %d)\n", ni, tlas.depth, maxBlasDepth, c->stackNeeded, LDS_STACK);
@@ -3307,6 +3353,8 @@ try {
   if (k == "wf_grace") c->wfGrace = (uint)value;                                      // trips after the queue ran dry before a trace wave suspends its rays (0: never)
   else if (k == "node_min") { c->nodeMinOverride = value & 63; c->accelCommitted = false; c->flatRefittable = false; }
   else if (k == "refit") c->refitEnabled = value != 0;                                  // 0: UpdateInstance / UpdateGeom + CommitScene always rebuild the tree on the host   // voted exit of the inner-node loop; takes effect at the next CommitScene
+  else if (k == "device_refit") { if (value > 1) return c->fail(HPT_ERR_ARG, "device_refit: 0 an update of a device-built tree is another device build, 1 it is a refit"); c->deviceRefit = value != 0; }
+  else if (k == "refit_max_sah_pct") { if (value != 0 && value < 100) return c->fail(HPT_ERR_ARG, "refit_max_sah_pct: 0 never, else >= 100 (per cent of the estimate at build time)"); c->refitMaxSahPct = value; }
   else if (k == "dbg_no_normal_lerp") { if (c->S.motion) c->S.motion = value ? 3u : 1u; }   // diagnostic: moving instances without the reference's normal interpolation (bit 1 of DevScene::motion)
   else if (k == "dbg_wf_iter_cap") c->wfIterCap = (uint)value;                         // diagnostic: make the wavefront loop's safety net reachable in a test
   else if (k == "dr_grad_mode") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_grad_mode: 0 forward only, 1 with the gradient"); c->drGradMode = value != 0; }   // IntegratorDR's a_gradMode: RayTraceDR only
@@ -3342,6 +3390,31 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_commit_time"); }
+extern "C" int hpt_get_refit_info(hpt_ctx* c, float out[4])
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  out[0] = c->sahVisits; out[1] = c->tCommit[3] == 1.0f ? c->sahRefit : c->sahVisits;
+  out[2] = (c->S.flatMode == 1u && !c->S.sweep && c->flatRefittable) ? (float)(c->levelOffsets.size() - 1) : 0.0f;
+  out[3] = c->refitRejected ? 1.0f : 0.0f;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_get_refit_info"); }
+extern "C" int hpt_read_accel(hpt_ctx* c, int what, void* dst, uint64_t capacityBytes, uint64_t* outBytes, uint32_t* outRootRef)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (what < 0 || what > 1) return c->fail(HPT_ERR_ARG, "hpt_read_accel: what = 0 (BvhNode array) or 1 (BvhTri array)");
+  if (!c->accelCommitted || c->S.flatMode != 1u || c->S.sweep) return c->fail(HPT_ERR_STATE, "hpt_read_accel: no single-level tree is committed");
+  const uint64_t bytes = what == 0 ? (uint64_t)std::min(c->flatNodes, c->dNodes.n) * sizeof(BvhNode) : (uint64_t)std::min(c->instTris, c->dTris.n) * sizeof(BvhTri);
+  if (outBytes) *outBytes = bytes;
+  if (outRootRef) *outRootRef = c->S.rootRef;
+  if (!dst) return HPT_OK;
+  if (capacityBytes < bytes) return c->fail(HPT_ERR_ARG, "hpt_read_accel: the destination is too small");
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipDeviceSynchronize());
+  if (bytes) HIPCHK(c, hipMemcpy(dst, what == 0 ? (const void*)c->dNodes.p : (const void*)c->dTris.p, bytes, hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_read_accel"); }
 extern "C" int hpt_get_schedule(hpt_ctx* c, int* lastSchedule, uint32_t* lastIterations)
 try {
   if (!c) return HPT_ERR_ARG;

@@ -30,23 +30,30 @@ struct Scratch
   void* sortTemp = nullptr; size_t sortTempBytes = 0;
   // hierarchy: inner node i in [0, n - 1)
   uint *childL = nullptr, *childR = nullptr, *parent = nullptr, *leafParent = nullptr, *first = nullptr, *last = nullptr, *flags = nullptr, *depth = nullptr;
+  uint* height = nullptr;                 // per inner node: its height in the EMITTED tree (0 = both children are leaves), see lbvhFitKernel
   float* nodeBox = nullptr;               // [6][n - 1]
   uint2 *frontA = nullptr, *frontB = nullptr;
   uint* counters = nullptr;               // see LbvhCounters
   // inputs mirrored on the device
   float* geomPos = nullptr; uint* geomIdx = nullptr; size_t geomPosCap = 0, geomIdxCap = 0;
   float* instMat = nullptr; uint4* instInfo = nullptr; size_t instCap = 0;
+  unsigned char* instDirty = nullptr; size_t instDirtyCap = 0;   // lbvhUpdatePositions: 1 = the instance's mesh moved
+  uint ni = 0, n = 0;                     // what the last build was over (valsOut, instInfo and the geometry stay as it left them)
   size_t cap = 0;
   void freeAll()
   {
-    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo };
+    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, height, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo, instDirty };
     for (void* p : ps) if (p) (void)hipFree(p);
     *this = Scratch();
   }
 };
 
 // device-side result words
-struct LbvhCounters { uint sceneLo[3], sceneHi[3]; uint count4; uint frontCount[2]; uint depth4; float sahSum; uint pad; };
+struct LbvhCounters
+{
+  uint sceneLo[3], sceneHi[3]; uint count4; uint frontCount[2]; uint depth4; float sahSum; uint pad;
+  uint levelCount[LBVH_MAX_LEVELS], levelFill[LBVH_MAX_LEVELS];       // emitted nodes per height; where the next node of that height goes in the level lists
+};
 
 HPT_HD uint floatKey(float f) { const uint b = hptFloatToBits(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }       // monotonic float -> uint
 HPT_HD float keyFloat(uint k) { return hptBitsToFloat((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
@@ -159,7 +166,8 @@ __global__ void __launch_bounds__(256) lbvhHierarchyKernel(const unsigned long l
 
 // ---- 4. boxes bottom-up: the second thread to arrive at a node fits it ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ triBox, const uint* __restrict__ vals, uint n, const uint* __restrict__ childL, const uint* __restrict__ childR,
-                                                     const uint* __restrict__ parent, const uint* __restrict__ leafParent, uint* flags, float* nodeBox, uint* depth)
+                                                     const uint* __restrict__ parent, const uint* __restrict__ leafParent, const uint* __restrict__ first, const uint* __restrict__ last,
+                                                     uint* flags, float* nodeBox, uint* depth, uint* height)
 {
   const uint k = blockIdx.x * 256u + threadIdx.x;
   if (k >= n || n < 2u) return;
@@ -169,7 +177,7 @@ __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ t
     __threadfence();
     if (atomicAdd(&flags[node], 1u) == 0u) return;                       // the first arrival leaves; its sibling's subtree is not ready yet
     __threadfence();
-    float lo[3], hi[3]; uint dep = 0;
+    float lo[3], hi[3]; uint dep = 0, hgt = 0;                           // hgt: the height among the nodes lbvhEmitKernel emits (a child folded into a leaf counts as a leaf)
     const uint cs[2] = { childL[node], childR[node] };
     for (int a = 0; a < 3; a++) { lo[a] = 3.0e38f; hi[a] = -3.0e38f; }
     for (int c = 0; c < 2; c++) {
@@ -180,10 +188,12 @@ __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ t
       } else {
         for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __hip_atomic_load(&nodeBox[(size_t)a * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); hi[a] = fmaxf(hi[a], __hip_atomic_load(&nodeBox[(size_t)(3 + a) * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
         dep = max(dep, __hip_atomic_load(&depth[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        if (last[ch] - first[ch] + 1u > (uint)BVH_LEAF_MAX) hgt = max(hgt, __hip_atomic_load(&height[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u);
       }
     }
     for (int a = 0; a < 3; a++) { __hip_atomic_store(&nodeBox[(size_t)a * m + node], lo[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(&nodeBox[(size_t)(3 + a) * m + node], hi[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
     __hip_atomic_store(&depth[node], dep + 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&height[node], hgt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     node = parent[node];
   }
 }
@@ -240,7 +250,7 @@ __global__ void __launch_bounds__(256) lbvhGatherTrisKernel(const float* __restr
 }
 
 // ---- 6. collapse to 4-wide compressed nodes, one level per launch (collapseToWide of bvh_build.h as a frontier kernel) -------------------------------
-__global__ void __launch_bounds__(256) lbvhCollapseKernel(const BvhNode* __restrict__ nodes, const uint2* __restrict__ frontIn, uint2* frontOut, uint level, BvhNode4* nodes4, uint cap4, LbvhCounters* C)
+__global__ void __launch_bounds__(256) lbvhCollapseKernel(const BvhNode* __restrict__ nodes, const uint2* __restrict__ frontIn, uint2* frontOut, uint level, BvhNode4* nodes4, uint cap4, uint* src4, LbvhCounters* C)
 {
   const uint e = blockIdx.x * 256u + threadIdx.x;
   const uint cnt = C->frontCount[level & 1u];
@@ -282,9 +292,74 @@ __global__ void __launch_bounds__(256) lbvhCollapseKernel(const BvhNode* __restr
   nd.pad[0] = nd.pad[1] = 0u;
   quantizeNode4(lo, hi, valid, nd);
   for (int k = 0; k < 4; k++) nd.ref[k] = refs[k];
-  if (it.y < cap4) nodes4[it.y] = nd;
+  if (it.y < cap4) {
+    nodes4[it.y] = nd;
+    if (src4) for (int k = 0; k < 4; k++) src4[4u * (size_t)it.y + k] = k < nk ? kids[k] : 0u;     // where child k's box lives: what refitNodes4Kernel requantises from
+  }
 }
 __global__ void lbvhResetFrontKernel(LbvhCounters* C, uint level) { C->frontCount[level & 1u] = 0u; }
+
+// ---- 7. what a refit needs: the emitted nodes grouped by height (a node reads only children of smaller height) ------------------------------------
+// Histogram over the heights, a scan over its <= 64 bins, a scatter. Level l of the lists holds the nodes of height (root's height - l): level 0 is
+// the root alone and the refit walks the levels from the last to the first, as it does for a host-built tree. The order inside a level is whatever
+// the atomics make it. Heights are clamped to the bins: a tree that deep is given back to the host's builder (hpt_host.hip) and its lists are not used.
+__device__ inline bool emittedHeight(uint i, uint n, const uint* first, const uint* last, const uint* height, uint& h)
+{
+  if (i + 1u >= n || last[i] - first[i] + 1u <= (uint)BVH_LEAF_MAX) return false;
+  h = min(height[i], LBVH_MAX_LEVELS - 1u);
+  return true;
+}
+__global__ void __launch_bounds__(256) lbvhLevelHistKernel(uint n, const uint* __restrict__ first, const uint* __restrict__ last, const uint* __restrict__ height, LbvhCounters* C)
+{
+  __shared__ uint cnt[LBVH_MAX_LEVELS];
+  if (threadIdx.x < LBVH_MAX_LEVELS) cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  uint h;
+  if (emittedHeight(blockIdx.x * 256u + threadIdx.x, n, first, last, height, h)) atomicAdd(&cnt[h], 1u);
+  __syncthreads();
+  if (threadIdx.x < LBVH_MAX_LEVELS && cnt[threadIdx.x]) atomicAdd(&C->levelCount[threadIdx.x], cnt[threadIdx.x]);
+}
+__global__ void __launch_bounds__(64) lbvhLevelScanKernel(const uint* __restrict__ height, LbvhCounters* C)       // one wave: lane = height
+{
+  const uint h = threadIdx.x, top = min(height[0], LBVH_MAX_LEVELS - 1u);
+  uint before = 0u;                                                     // nodes of the levels in front of this height's: the greater heights
+  for (uint g = h + 1u; g <= top; g++) before += C->levelCount[g];
+  C->levelFill[h] = before;
+}
+__global__ void __launch_bounds__(256) lbvhLevelScatterKernel(uint n, const uint* __restrict__ first, const uint* __restrict__ last, const uint* __restrict__ height, LbvhCounters* C, uint* levelIds)
+{
+  __shared__ uint cnt[LBVH_MAX_LEVELS], base[LBVH_MAX_LEVELS];
+  if (threadIdx.x < LBVH_MAX_LEVELS) cnt[threadIdx.x] = 0u;
+  __syncthreads();
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  uint h = 0u, rank = 0u;
+  const bool emitted = emittedHeight(i, n, first, last, height, h);
+  if (emitted) rank = atomicAdd(&cnt[h], 1u);
+  __syncthreads();
+  if (threadIdx.x < LBVH_MAX_LEVELS && cnt[threadIdx.x]) base[threadIdx.x] = atomicAdd(&C->levelFill[threadIdx.x], cnt[threadIdx.x]);
+  __syncthreads();
+  if (emitted && base[h] + rank < n - 1u) levelIds[base[h] + rank] = i;  // (fewer than n - 1 nodes are emitted: the lists fit in n - 1 entries)
+}
+
+// ---- 8. moved vertices: the records of the flagged instances again, from the meshes' current positions ---------------------------------------------
+// One lane per record. The record names its instance and primitive, so the sorted order need not be consulted; the expressions are
+// lbvhGatherTrisKernel's, so the records equal a fresh build's bit for bit.
+__global__ void __launch_bounds__(256) lbvhRegatherTrisKernel(const float* __restrict__ geomPos, const uint* __restrict__ geomIdx, const uint4* __restrict__ instInfo, const unsigned char* __restrict__ instDirty,
+                                                              uint ni, uint n, BvhTri* tris)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const uint i = tris[k].instId, p = tris[k].primId;
+  if (i >= ni || !instDirty[i]) return;
+  const uint4 inf = instInfo[i];
+  if (p >= inf.y) return;
+  const uint* ix = geomIdx + inf.w + 3 * (size_t)p;
+  const float* A = geomPos + inf.z + 3 * (size_t)ix[0]; const float* B = geomPos + inf.z + 3 * (size_t)ix[1]; const float* Cc = geomPos + inf.z + 3 * (size_t)ix[2];
+  BvhTri t;
+  for (int a = 0; a < 3; a++) { t.v0[a] = A[a]; t.e1[a] = B[a] - A[a]; t.e2[a] = Cc[a] - A[a]; }
+  t.primId = p; t.instId = i; t.pad1 = 0u;
+  tris[k] = t;
+}
 
 template <class T> bool ensure(T*& p, size_t count) { if (p) (void)hipFree(p); p = nullptr; return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
 
@@ -311,15 +386,16 @@ bool lbvhUploadGeometry(void* scratch, const std::vector<const float*>& pos, con
   return true;
 }
 
-bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNode* nodes, BvhTri* tris, BvhNode4* nodes4, uint cap4, bool wantWide, LbvhResult& out, std::string& err)
+bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNode* nodes, BvhTri* tris, BvhNode4* nodes4, uint cap4, bool wantWide, const LbvhRefitOut& refit, LbvhResult& out, std::string& err)
 {
   Scratch& S = *(Scratch*)scratch;
   out = LbvhResult();
+  S.ni = 0; S.n = 0;
   if (n == 0u) { out.rootRef = REF_NONE; return true; }
   if (n > S.cap) {
     const size_t c = n;
     bool ok = ensure(S.triBox, 6 * c) && ensure(S.keysIn, c) && ensure(S.keysOut, c) && ensure(S.valsIn, c) && ensure(S.valsOut, c) && ensure(S.childL, c) && ensure(S.childR, c) &&
-              ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.nodeBox, 6 * c) &&
+              ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.height, c) && ensure(S.nodeBox, 6 * c) &&
               ensure(S.frontA, c) && ensure(S.frontB, c);
     if (!ok) { err = "hipMalloc (build scratch)"; S.cap = 0; return false; }
     S.cap = c;
@@ -354,6 +430,7 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   size_t bytes = S.sortTempBytes;
   LCHK(hipcub::DeviceRadixSort::SortPairs(S.sortTemp, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 63, nullptr));
   lbvhGatherTrisKernel<<<grdN, blk>>>(S.geomPos, S.geomIdx, S.instInfo, ni, n, S.valsOut, tris);
+  S.ni = ni; S.n = n;
   if (n <= (uint)BVH_LEAF_MAX) {                                      // the whole scene is one leaf
     LCHK(hipStreamSynchronize(nullptr));
     out.rootRef = REF_LEAF | (n << 28); out.numNodes = 0; out.depth = 0; out.sahVisits = 1.0f;
@@ -361,8 +438,9 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   }
   LCHK(hipMemsetAsync(S.flags, 0, (size_t)n * sizeof(uint), nullptr));
   LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
+  LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
   lbvhHierarchyKernel<<<grdN, blk>>>(S.keysOut, (int)n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last);
-  lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.flags, S.nodeBox, S.depth);
+  lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.flags, S.nodeBox, S.depth, S.height);
   lbvhEmitKernel<<<grdN, blk>>>(n, S.childL, S.childR, S.first, S.last, S.triBox, S.valsOut, S.nodeBox, nodes, C);
   const uint MAX_LEVELS = 64u;
   if (wantWide && nodes4 && cap4) {
@@ -370,13 +448,25 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
     LCHK(hipMemcpyAsync(S.frontA, &root, sizeof(root), hipMemcpyHostToDevice, nullptr));
     for (uint level = 0; level < MAX_LEVELS; level++) {
       lbvhResetFrontKernel<<<1, 1>>>(C, level + 1u);
-      lbvhCollapseKernel<<<grdN, blk>>>(nodes, (level & 1u) ? S.frontB : S.frontA, (level & 1u) ? S.frontA : S.frontB, level, nodes4, cap4, C);
+      lbvhCollapseKernel<<<grdN, blk>>>(nodes, (level & 1u) ? S.frontB : S.frontA, (level & 1u) ? S.frontA : S.frontB, level, nodes4, cap4, refit.src4, C);
     }
   }
+  if (refit.levelIds) {
+    lbvhLevelHistKernel<<<grdN, blk>>>(n, S.first, S.last, S.height, C);
+    lbvhLevelScanKernel<<<1, LBVH_MAX_LEVELS>>>(S.height, C);
+    lbvhLevelScatterKernel<<<grdN, blk>>>(n, S.first, S.last, S.height, C, refit.levelIds);
+  }
   LCHK(hipGetLastError());
-  LbvhCounters res; uint rootDepth = 0; float rootBox[6];
+  LbvhCounters res; uint rootDepth = 0, rootHeight = 0; float rootBox[6];
   LCHK(hipMemcpy(&res, S.counters, sizeof(res), hipMemcpyDeviceToHost));
   LCHK(hipMemcpy(&rootDepth, S.depth, sizeof(uint), hipMemcpyDeviceToHost));
+  if (refit.levelIds) {
+    LCHK(hipMemcpy(&rootHeight, S.height, sizeof(uint), hipMemcpyDeviceToHost));
+    if (rootHeight < LBVH_MAX_LEVELS) {                                  // (else: deeper than the traversal stack; the caller rebuilds on the host)
+      out.numLevels = rootHeight + 1u;
+      for (uint l = 0; l <= rootHeight; l++) out.levelCount[l] = res.levelCount[rootHeight - l];
+    }
+  }
   for (int a = 0; a < 6; a++) LCHK(hipMemcpy(&rootBox[a], S.nodeBox + (size_t)a * (n - 1), sizeof(float), hipMemcpyDeviceToHost));
   out.rootRef = 0u; out.numNodes = n - 1u; out.depth = rootDepth;
   float lo[3] = { rootBox[0], rootBox[1], rootBox[2] }, hi[3] = { rootBox[3], rootBox[4], rootBox[5] };
@@ -387,6 +477,23 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
     if (res.frontCount[MAX_LEVELS & 1u] != 0u || res.count4 > cap4) { out.nodes4Count = 0; out.depth4 = 0; }     // (deeper than the level loop / more nodes than room: no wide tree)
     else { out.nodes4Count = res.count4; out.depth4 = res.depth4; }
   }
+  return true;
+}
+
+bool lbvhUpdatePositions(void* scratch, const std::vector<uint>& geoms, const std::vector<const float*>& pos, const std::vector<size_t>& posFloats, const std::vector<size_t>& posOffset,
+                         const unsigned char* instDirty, uint ni, uint n, BvhTri* tris, std::string& err)
+{
+  Scratch& S = *(Scratch*)scratch;
+  if (ni != S.ni || n != S.n || !S.geomPos || !S.instInfo) { err = "the scene is not the one the tree was built over"; return false; }
+  for (uint g : geoms) {
+    if (g >= pos.size() || g >= posOffset.size() || posOffset[g] + posFloats[g] > S.geomPosCap) { err = "a mesh outside the uploaded geometry"; return false; }
+    if (posFloats[g]) LCHK(hipMemcpyAsync(S.geomPos + posOffset[g], pos[g], posFloats[g] * sizeof(float), hipMemcpyHostToDevice, nullptr));
+  }
+  if (ni > S.instDirtyCap) { if (!ensure(S.instDirty, (size_t)ni)) { err = "hipMalloc (instance flags)"; S.instDirtyCap = 0; return false; } S.instDirtyCap = ni; }
+  LCHK(hipMemcpyAsync(S.instDirty, instDirty, ni, hipMemcpyHostToDevice, nullptr));
+  lbvhRegatherTrisKernel<<<dim3((n + 255u) / 256u), dim3(256)>>>(S.geomPos, S.geomIdx, S.instInfo, S.instDirty, ni, n, tris);
+  LCHK(hipGetLastError());
+  LCHK(hipStreamSynchronize(nullptr));                                 // (the caller's staging leaves scope)
   return true;
 }
 

@@ -540,6 +540,12 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               state + stack to HBM) for the next round's trace pass, which resumes them first; 0 = run every ray to the end.
  *               Only applied in rounds with at least 2 rays per lane of the trace grid.
  *   "refit"     1 (default): CommitScene after UpdateInstance / UpdateGeom_Triangles3f refits the single-level tree on the device; 0: rebuild.
+ *   "device_refit"  0 (default): an update of a DEVICE-built single-level tree is answered by another device build; 1: the device build leaves
+ *               its level lists behind and such an update refits the tree (instance matrices and vertex positions; "refit", 0 still rebuilds).
+ *               Read when the tree is built and again when the update is committed.
+ *   "refit_max_sah_pct"  p: 0 (default) = never; p >= 100: a refit whose surface-area estimate (hpt_get_refit_info) exceeds p / 100 times the
+ *               estimate at build time is followed, in the same hpt_commit_scene, by a build (on the device for a device-built tree, on the host
+ *               for a host-built one). 1 .. 99 is an argument error.
  *   "node_min"  voted exit of the inner-node loop (0..63, applied at the next hpt_commit_scene; default chosen per scene).
  * A member of the reference that is set in its constructor:
  *   "dr_grad_mode"  IntegratorDR's a_gradMode (integrator_dr.h; default 1). 0: RayTraceDR renders and returns the loss through the ordinary
@@ -579,9 +585,24 @@ int  hpt_allreduce_grad(hpt_ctx* ctx, float* gradDev, size_t count, void* stream
 int  hpt_get_accel_info(hpt_ctx* ctx, float out[4]);
 /* The last hpt_commit_scene: out[0] = host milliseconds (BVH build, or for a refit the matrix inversions and record updates), out[1] = upload ms,
  * out[2] = device refit ms, out[3] = 1 when the committed single-level tree was REFITTED on the device (UpdateInstance / UpdateGeom_Triangles3f
- * with unchanged topology: boxes recomputed bottom-up by two small kernels, CrossRT.h:85-86, 134), 2 when it was BUILT on the device (out[2] = the
- * build's milliseconds) and 0 when it was built on the host. hpt_set_option("refit", 0) forces the build. */
+ * with unchanged topology: triangle boxes, then one small kernel per tree level from the leaves up, then the 4-wide nodes requantised and the
+ * tree's cost summed, CrossRT.h:85-86, 134; a host-built tree always, a device-built one under hpt_set_option("device_refit", 1)), 2 when it was
+ * BUILT on the device (out[2] = the build's milliseconds) and 0 when it was built on the host. hpt_set_option("refit", 0) forces the build. */
 int  hpt_get_commit_time(hpt_ctx* ctx, float out[4]);
+/* The committed single-level tree's surface-area estimate before and after refits (a refit keeps the topology, so the tree degrades as objects
+ * move; this is the number from which to decide on a rebuild): out[0] = the estimate at build time (hpt_get_accel_info's out[0]), out[1] = the
+ * estimate of the tree as the last refit left it, summed on the device over the refitted boxes (= out[0] when the last commit was a build),
+ * out[2] = number of levels a refit launches (0: the tree cannot be refitted), out[3] = 1 when the last hpt_commit_scene attempted a refit and
+ * "refit_max_sah_pct" rejected it. Schedule and kernel choices keep following out[0]. */
+int  hpt_get_refit_info(hpt_ctx* ctx, float out[4]);
+/* Host copy of the committed single-level tree as it lies in device memory (tests, checkpoints; the counterpart of hpt_cam_read_state):
+ * what = 0: the BvhNode array (64-byte records: q[12] = child 0 {lo.x hi.x lo.y hi.y lo.z hi.z}, child 1 {same}; ref0, ref1, two pad words),
+ * what = 1: the BvhTri array (48-byte records: v0[3], primId, e1[3], instId, e2[3], pad). A reference with bit 31 set is a leaf
+ * (bits 28..30 = triangle count, bits 0..27 = first record), 0xFFFFFFFE is "no child", anything else indexes the node array; *outRootRef
+ * receives the root's reference. A device-built tree's node array has unused entries (only what the root reaches is a node).
+ * dst == NULL: only *outBytes is set. HPT_ERR_ARG when capacityBytes is too small, HPT_ERR_STATE when no single-level tree is committed
+ * (the two-level and sweep layouts are not read back). */
+int  hpt_read_accel(hpt_ctx* ctx, int what, void* dst, uint64_t capacityBytes, uint64_t* outBytes, uint32_t* outRootRef);
 /* Schedule the last hpt_path_trace_block(_dev) call used (1 .. 4, as hpt_set_schedule numbers them) and, for the wavefront one, its number of
  * shade+trace rounds. */
 int  hpt_get_schedule(hpt_ctx* ctx, int* lastSchedule, uint32_t* lastIterations);
