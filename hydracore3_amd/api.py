@@ -771,10 +771,11 @@ class HipIntegrator:
         self._chk(self.L.hpt_commit_scene(self.h, options))
 
     def last_launch(self):
-        """What the last PathTrace* call walked: schedule, 4-wide compressed tree, 64-byte shading records, HBM part of the stacks."""
-        out = (C.c_uint32 * 4)()
+        """What the last PathTrace* call walked: schedule, 4-wide compressed tree, 64-byte shading records, HBM part of the stacks, passes per
+        work item of the megakernel (0: whole pixels)."""
+        out = (C.c_uint32 * 5)()
         self._chk(self.L.hpt_get_last_launch(self.h, out))
-        return {"schedule": int(out[0]), "wide_nodes": bool(out[1]), "shade_records": bool(out[2]), "deep_stack": bool(out[3])}
+        return {"schedule": int(out[0]), "wide_nodes": bool(out[1]), "shade_records": bool(out[2]), "deep_stack": bool(out[3]), "pass_slice": int(out[4])}
 
     def stack_witness(self):
         """With set_option("dbg_stack_witness", 1): (words of the stacks' HBM part the last launch wrote, words filled before it). hpt_get_stack_witness."""

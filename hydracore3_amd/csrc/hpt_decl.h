@@ -25,9 +25,16 @@ struct Job
   const float* refImg;            // a_refImg
   const float* data;              // a_data
   float* grad;                    // a_dataGrad (atomically accumulated)
-  float* lossAccum;               // sum over samples of loss / passNum
-  float* record;                  // per-lane, per-bounce adjoint records: [bounce][field][lane]
-  uint   recordLanes;             // total lanes of the grid (stride of the record buffer)
+  // Pass slices (SLICED instantiations of pathTraceKernel, forward calls; hpt_set_option("pass_slice")) share the storage of four fields that
+  // only PathTraceDR reads, so that Job - a by-value kernel argument of every kernel family - keeps its size and layout:
+  //   passSlice       s > 0: the queue holds tidCount * passSliceCount(passNum, s) items (hpt_types.h: passSliceItem) and a pixel is handed
+  //                   from slice to slice through HBM
+  //   sliceDone       [tid]: slices of the pixel that are finished and published (zeroed before the launch)
+  //   slicePollLimit  polls after which a lane waiting for its predecessor gives up (a protocol bug ends as an error, not as a hang)
+  //   sliceError      set to 1 by a lane that gave up (host-visible; the host reports HPT_ERR_STATE)
+  union { float* lossAccum; uint* sliceError; };      // lossAccum: sum over samples of loss / passNum
+  union { float* record; uint* sliceDone; };          // record: per-lane, per-bounce adjoint records: [bounce][field][lane]
+  union { uint recordLanes; uint passSlice; };        // recordLanes: total lanes of the grid (stride of the record buffer)
   uint   naive;                   // the spectral kernel only: NaivePathTrace (the RGB kernels have their own instantiations)
   uint   drSkipNonFinite;         // hpt_set_option("dr_skip_nonfinite"): samples whose radiance is not finite give neither loss, colour nor gradient
                                   // (0 = the reference's PixelLossPT, which adds them like any other)
@@ -37,7 +44,7 @@ struct Job
   // `channels` floats in out_color's row order (not flipped as a_refImg is). Null: the DR path is rendered and recorded, nothing is swept.
   // No loss is computed; refImg and lossAccum are not read.
   const float* adjImg;
-  uint   vjp;
+  union { uint vjp; uint slicePollLimit; };
   const float4* inRayPos;         // PathTraceFromInputRays: RayPosAndW[tid] / RayDirAndT[tid] in camera space (MODE 2)
   const float4* inRayDir;
 };
@@ -62,7 +69,8 @@ struct Job
 #define HPT_DR_WAVES HPT_MIN_WAVES   // the PathTraceDR megakernel
 #endif
 #define HPT_PT_BOUNDS(DR, MODE) __launch_bounds__(256, (DR) ? HPT_DR_WAVES : ((MODE) == 3 ? HPT_MIN_WAVES : ((MODE) == 7 ? HPT_FULL_WAVES + 1 : ((MODE) >= 4 ? HPT_FILM_WAVES : HPT_FULL_WAVES))))
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false>
+// SLICED: work items are runs of Job::passSlice passes of a pixel (instantiated for PathTrace from the camera: MODE 3, 0, 7 and moving instances)
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false, bool SLICED = false>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job);
 
 // spectral rendering (hpt_spectral.hip): one thread per pixel, four wavelengths per path

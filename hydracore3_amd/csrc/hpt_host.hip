@@ -26,6 +26,11 @@
 #include "bvh_build.h"
 #include "hpt_lbvh.h"
 
+// Pass slices of the forward megakernel when hpt_set_option("pass_slice") was never called: 256 passes per work item in calls with at least two
+// pixels per lane and at least two such slices per pixel, whole pixels otherwise. Every hand-over writes the XCD's L2 back, so short slices
+// lose steeply. profiles/r7_pass_slices.md has what was measured: 16 ... 512 passes per item at four pixels per lane, 16 ... 256 at half a pixel,
+// 256 at one pixel (loses) and at two (gains), and 1024^2 calls of 512 passes with 0 / 128 / 256. Nothing between one and two pixels per lane was measured.
+static const uint PASS_SLICE_AUTO = 256u;
 static const float BLOCK_SAH_VISITS = 8.0f;                     // automatic schedule: from this many expected inner-node visits per ray the megakernel repacks rays block-locally (hpt_block.hip)
 static const uint MAX_STACK = 64;                           // traversal stack entries per lane: LDS_STACK in LDS + the rest in an HBM overflow buffer
 // Static scenes with at most this many INSTANCED triangles get the single-level world-space BVH (48 B + ~32 B of nodes per triangle:
@@ -158,6 +163,11 @@ struct hpt_ctx
   DevBuf<Rng> dGens;
   uint gensCount = 0;                                    // m_randomGens.size() as the last InitRandomGens / hpt_set_random_gens left it (the buffer never shrinks)
   DevBuf<uint> dQueue, dStackOvf; DevBuf<Counters> dCounters;
+  // pass slices of the forward megakernel (hpt_kernels.hip): hpt_set_option("pass_slice", n), 0 = a work item is a whole pixel
+  int  passSlice = -1;                                   // -1: by the rule at PASS_SLICE_AUTO
+  uint lastPassSlice = 0;
+  DevBuf<uint> dSliceDone;                               // [tid]: finished slices of the pixel, zeroed before every sliced launch
+  uint* sliceError = nullptr;                            // pinned, device-visible: a lane gave up waiting for its predecessor (sliceErrorCheck)
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
@@ -227,6 +237,7 @@ struct hpt_ctx
     for (WfGroup* g : wfGroups) delete g;
     for (void* p : texData) if (p) (void)hipFree(p);
     for (hipEvent_t e : { ev0, ev1, wfFork }) if (e) (void)hipEventDestroy(e);
+    if (sliceError) (void)hipHostFree(sliceError);
   }
   int fail(int code, const std::string& m) { err = m; std::fprintf(stderr, "[hydra_hip] %s\n", m.c_str()); return code; }
   int hipFail(hipError_t e, const char* what) { return fail(HPT_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
@@ -270,6 +281,7 @@ try {
   (void)hipEventCreate(&c->ev0); (void)hipEventCreate(&c->ev1);
   if (const char* e = std::getenv("HPT_NODE_MIN")) c->nodeMinOverride = std::atoi(e) & 63;
   if (const char* e = std::getenv("HPT_WF_GRACE")) c->wfGrace = (uint)std::atoi(e);
+  if (const char* e = std::getenv("HPT_PASS_SLICE")) c->passSlice = std::max(0, std::atoi(e));   // diagnostic, like the ones above: the slice sweep of profiles/r7_pass_slices.sh goes through bench.py, which sets no options
   if (const char* e = std::getenv("HPT_SHADE_RECORDS")) c->shadeTrisEnabled = std::atoi(e) != 0;
   if (const char* e = std::getenv("HPT_WIDE_NODES")) c->wideEnabled = std::atoi(e) != 0;   // (read before any scene is committed: CommitScene derives DevScene::megaWide from it)
   std::memset(&c->S, 0, sizeof(DevScene));
@@ -1624,16 +1636,16 @@ static int gridBlocks(hpt_ctx* c, bool dr, bool fullMaterials = false)
 
 // DEEP: the scene's BVH can need more than LDS_STACK stack entries, so pushes / pops check for the HBM overflow part
 // FLAT: single-level world-space BVH (static scenes within FLAT_TRI_BUDGET) vs two-level TLAS/BLAS
-template <bool STATS, bool DR, int NAIVE>
+template <bool STATS, bool DR, int NAIVE, bool SLICED = false>
 static void launchPT(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
-  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   else if (S.flatMode) {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, false><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -1669,15 +1681,15 @@ static void launchSpectralBlock(const DevScene& S, const Job& job, int blocks, h
 }
 
 // the MOTION variants: moving instances (two-level layout only), every BSDF branch
-template <int MODE>
+template <int MODE, bool SLICED = false>
 static void launchPTMotion(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
   if (S.flatMode) {
-    if (deep) pathTraceKernel<false, false, MODE, true, true, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<false, false, MODE, false, true, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<false, false, MODE, true, true, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<false, false, MODE, false, true, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<false, false, MODE, true, false, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<false, false, MODE, false, false, true><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<false, false, MODE, true, false, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<false, false, MODE, false, false, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -1934,9 +1946,20 @@ static int launch_stream(hpt_ctx* c, const Job& job, hipStream_t st)
   return rc;
 }
 
+// Pass slices: a lane of an earlier sliced launch gave up waiting for the slice before its own (Job::slicePollLimit). Called where the host
+// has waited for that launch anyway, and before the next one; the word is sticky until it has been reported once.
+static int sliceErrorCheck(hpt_ctx* c)
+{
+  if (!c->sliceError || *(volatile uint*)c->sliceError == 0u) return HPT_OK;
+  *(volatile uint*)c->sliceError = 0u;
+  return c->fail(HPT_ERR_STATE, "PathTraceBlock with pass slices: a lane waited for the slice before its own beyond the poll limit; the frame of that call is incomplete");
+}
+
 static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st)
 {
   const bool inRays = job.inRayPos != nullptr;
+  c->lastPassSlice = 0u;
+  if (int rc = sliceErrorCheck(c)) return rc;
   if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before CommitDeviceData / UpdateMembersPlainData");
   if (!inRays && c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlock before PackXYBlock");
   job.tidStride = c->tidStride > 1 ? c->tidStride : 1u;
@@ -2016,22 +2039,50 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   const bool fullMaterials = film || motion || !dr && !(c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && !naive && !inRays && !(c->instrument && !dr));   // MODE 0 / 1 / 2 / STATS kernels
   // MODE 7: the kernel with every BSDF branch built for one more wave per SIMD, for scenes with few material types (hpt_decl.h)
   const bool mode7 = fullMaterials && c->fewMaterialTypes && !c->forceFull && !film && !motion && !dr && !inRays && !naive && !(c->instrument && !dr);
-  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, dr, fullMaterials && !mode7), ((size_t)job.tidCount + 255) / 256);
+  // Pass slices: the forward megakernel only (PathTraceDR's per-lane loss sum would change its summation order across items; input rays keep
+  // one item per ray), and not its instrumented probe nor the block-local schedule, which have their own loops. The slice doubles until the
+  // item count fits the queue's 32-bit head with room for every lane's last draw.
+  const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
+  const bool streamCall = c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u;
+  const bool waveCall = !streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount);
+  // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
+  // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
+  // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
+  // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
+  const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
+  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
+  const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
+  const size_t fullGrid = (size_t)gridBlocks(c, dr, fullMaterials && !mode7) * 256;
+  const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : ((job.tidCount >= 2 * fullGrid && job.passNum >= 2u * PASS_SLICE_AUTO) ? PASS_SLICE_AUTO : 0u);
+  uint slice = (dr || inRays || naive || film || stats || blockLocal || streamCall || waveCall) ? 0u : sliceWanted;
+  while (slice != 0u && (uint64_t)job.tidCount * passSliceCount(job.passNum, slice) > (1ull << 31)) slice *= 2u;
+  if (slice >= job.passNum) slice = 0u;                           // one item per pixel either way: the plain form
+  const size_t items = (size_t)job.tidCount * passSliceCount(job.passNum, slice);
+  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, dr, fullMaterials && !mode7), (items + 255) / 256);
   HIPCHK(c, c->dQueue.alloc(1));
   HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
   job.queue = c->dQueue.p;
+  if (slice != 0u) {                                           // (the slice fields share storage with PathTraceDR's: hpt_decl.h)
+    job.passSlice = slice;
+    if (!c->sliceError) { HIPCHK(c, hipHostMalloc((void**)&c->sliceError, sizeof(uint), hipHostMallocMapped)); *c->sliceError = 0u; }
+    HIPCHK(c, c->dSliceDone.alloc(job.tidEnd));
+    HIPCHK(c, hipMemsetAsync(c->dSliceDone.p, 0, (size_t)job.tidEnd * 4, st));
+    job.sliceDone = c->dSliceDone.p; job.sliceError = c->sliceError;
+    // A waiting lane polls once per trip of its wave, or once per sleep (>= one trip's time) when the whole wave waits. What it waits for is at
+    // most the pixel's earlier passes, each at most traceDepth + 2 trips: 64 times that, and never less than 2^20 polls.
+    job.slicePollLimit = (uint)std::min<uint64_t>(0x7FFFFFFFull, std::max<uint64_t>(1ull << 20, 64ull * job.passNum * (c->S.traceDepth + 2u)));
+  }
   job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
   job.counters = nullptr;
   job.drSkipNonFinite = c->drSkipNonFinite ? 1u : 0u;
-  const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
   c->lastSchedule = 1;
   c->lastShadeRecords = c->S.shadeTris != nullptr ? 1u : 0u;
   // schedule 4 (experimental, never chosen automatically): the block-owned streaming form of the wavefront schedule - heavy static scenes with gltf / emissive materials
-  if (c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u) {
+  if (streamCall) {
     c->lastSchedule = 4; c->lastWide = 1u; c->lastDeep = c->stackNeeded4 > (uint)LDS_STACK ? 1u : 0u;
     return launch_stream(c, job, st);
   }
-  if (!inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount)) {
+  if (waveCall) {
     c->lastSchedule = 2; c->lastWide = (wfWide(c) && !c->instrument) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
     return launch_wavefront(c, job, st, dr);
   }
@@ -2043,16 +2094,10 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1)));
     job.record = c->dRecord.p;
   }
+  c->lastPassSlice = slice;
   return launchFrame(c, (size_t)blocks * 256, st, [&]() {
     job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
     const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
-    // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
-    // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
-    // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
-    // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
-    const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
-    const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
-    const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
     if (blockLocal) {
       const bool lean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
       const bool bwide = lean && (c->bwWide == 1 || (c->bwWide < 0 && c->S.megaWide != 0u)) && c->S.flatMode != 0u && c->nodes4Count != 0u && c->wideEnabled;      // heavy scenes: the 4-wide compressed tree, as the megakernel walks it
@@ -2068,7 +2113,8 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
       if (inRays) launchPTMotion<6>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<5>(c->S, job, blocks, st, deep); else launchPTMotion<4>(c->S, job, blocks, st, deep);
     }
     else if (motion) {
-      if (inRays) launchPTMotion<2>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<1>(c->S, job, blocks, st, deep); else launchPTMotion<0>(c->S, job, blocks, st, deep);
+      if (inRays) launchPTMotion<2>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<1>(c->S, job, blocks, st, deep);
+      else if (slice != 0u) launchPTMotion<0, true>(c->S, job, blocks, st, deep); else launchPTMotion<0>(c->S, job, blocks, st, deep);
     }
     else if (dr) {
       // the DR kernel's waves are emptier than the forward kernel's (lane utilisation 0.25), so leaving the inner-node loop when fewer than four
@@ -2092,9 +2138,9 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
       Sp.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;   // "stats_wide": the caller says the measured call ran there
       launchPT<true, false, 0>(Sp, job, blocks, st, deep || (Sp.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
     }
-    else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) launchPT<false, false, 3>(c->S, job, blocks, st, deep);
-    else if (mode7)  launchPT<false, false, 7>(c->S, job, blocks, st, deep);
-    else             launchPT<false, false, 0>(c->S, job, blocks, st, deep);
+    else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) { if (slice != 0u) launchPT<false, false, 3, true>(c->S, job, blocks, st, deep); else launchPT<false, false, 3>(c->S, job, blocks, st, deep); }
+    else if (mode7)  { if (slice != 0u) launchPT<false, false, 7, true>(c->S, job, blocks, st, deep); else launchPT<false, false, 7>(c->S, job, blocks, st, deep); }
+    else             { if (slice != 0u) launchPT<false, false, 0, true>(c->S, job, blocks, st, deep); else launchPT<false, false, 0>(c->S, job, blocks, st, deep); }
   });
 }
 
@@ -2123,6 +2169,7 @@ static int roundTrip(hpt_ctx* c, float* slots, KernelTime kt, Up up, Launch laun
   const double t1 = now_ms();
   if (int rc = launch()) return rc;
   HIPCHK(c, hipDeviceSynchronize());
+  if (int rc = sliceErrorCheck(c)) return rc;
   const double t2 = now_ms();
   if (int rc = down()) return rc;
   const double t3 = now_ms();
@@ -3358,6 +3405,7 @@ try {
   else if (k == "dbg_no_normal_lerp") { if (c->S.motion) c->S.motion = value ? 3u : 1u; }   // diagnostic: moving instances without the reference's normal interpolation (bit 1 of DevScene::motion)
   else if (k == "dbg_wf_iter_cap") c->wfIterCap = (uint)value;                         // diagnostic: make the wavefront loop's safety net reachable in a test
   else if (k == "dr_grad_mode") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_grad_mode: 0 forward only, 1 with the gradient"); c->drGradMode = value != 0; }   // IntegratorDR's a_gradMode: RayTraceDR only
+  else if (k == "pass_slice") c->passSlice = value;                              // forward megakernel: passes of a pixel per work item (0: the whole pixel; hpt_kernels.hip)
   else if (k == "dr_skip_nonfinite") c->drSkipNonFinite = value != 0;                  // PathTraceDR: drop samples whose radiance is not finite (default 0: PixelLossPT as in the reference)
   else if (k == "shade_records") c->shadeTrisEnabled = value != 0;                     // 0: no DevScene::shadeTris (A/B, diagnosis)
   else if (k == "build_threads") c->buildThreads = std::min(value, 64);                // host threads CommitScene builds its trees with (0: the usable cores, at most 16)
@@ -3423,10 +3471,10 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_schedule"); }
-extern "C" int hpt_get_last_launch(hpt_ctx* c, uint32_t out[4])
+extern "C" int hpt_get_last_launch(hpt_ctx* c, uint32_t out[5])
 try {
   if (!c || !out) return HPT_ERR_ARG;
-  out[0] = c->lastSchedule; out[1] = c->lastWide; out[2] = c->lastShadeRecords; out[3] = c->lastDeep;
+  out[0] = c->lastSchedule; out[1] = c->lastWide; out[2] = c->lastShadeRecords; out[3] = c->lastDeep; out[4] = c->lastPassSlice;
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_last_launch"); }
@@ -3461,6 +3509,6 @@ try {
   if (e == hipSuccess) e = hipEventElapsedTime(&k, c->ev0, c->ev1);
   if (e != hipSuccess) { *ms = c->lastKernelMs; return HPT_OK; }
   *ms = c->lastKernelMs = k;
-  return HPT_OK;
+  return sliceErrorCheck(c);
 }
 catch (...) { return hptGuard(c, "hpt_last_kernel_ms"); }

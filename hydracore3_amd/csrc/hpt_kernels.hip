@@ -11,16 +11,18 @@
 //     lanes of the wave;
 //   * pixels are handed out by a persistent-threads work queue: lanes that ran out of passes are compacted with a wave
 //     ballot + mbcnt prefix sum, and ONE atomicAdd per wave fetches a contiguous run of tids for them;
-//   * the grid is sized to the chip (blocksPerCU x 256 CUs), not to the image.
+//   * the grid is sized to the chip (blocksPerCU x 256 CUs), not to the image;
+//   * with pass slices (Job::passSlice) a work item is a run of passes of a pixel; the pixel and its generator pass from item to item
+//     through HBM behind an agent-scope release / acquire of sliceDone[tid] (DESIGN.md 2.1 has the protocol and its progress argument).
 //
 // Exit condition every wave reaches: the queue counter only grows, a lane that draws an index past the end never asks
-// again, and a wave leaves the loop when none of its lanes holds a live path or a pixel.
+// again, and a wave leaves the loop when none of its lanes holds a live path or a pixel or waits for a slice (a wait is bounded).
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 
 namespace hpt {
 
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job)
 {
   constexpr bool NAIVE = (MODE == 1 || MODE == 5), INRAYS = (MODE == 2 || MODE == 6), LEAN = (MODE == 3), FILM = (MODE >= 4 && MODE <= 6);   // (MODE 7 = MODE 0 built for one more wave per SIMD)
@@ -32,13 +34,21 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   // Cold per-PIXEL state (touched once per path, not per bounce) is parked in LDS so that it does not occupy VGPRs
   // across the two traversals and the shading code: running framebuffer value, packed (x,y), tid, passes left.
   __shared__ float coldPix[3 * 256];
-  __shared__ uint  coldU[3 * 256];
+  __shared__ uint  coldU[(SLICED ? 5 : 3) * 256];
   __shared__ uint  drStage[DR ? 4 * DR_STAGE_DWORDS : 1];               // PathTraceDR: the waves' staging areas of the cooperative gradient scatter
 #define PIX(k)      coldPix[(k) * 256 + threadIdx.x]
 #define PIX_XY      coldU[0 * 256 + threadIdx.x]
 #define PIX_TID     coldU[1 * 256 + threadIdx.x]
 #define PIX_PASSES  coldU[2 * 256 + threadIdx.x]
-  bool havePixel = false, alive = false, drained = false;
+#define PIX_SLICE   coldU[3 * 256 + threadIdx.x]      // SLICED: the slice of the pixel this lane holds or waits for
+#define PIX_POLLS   coldU[4 * 256 + threadIdx.x]      // ... and how often it has polled for it
+  // Pass slices (the SLICED instantiations, Job::passSlice > 0): an item is `passSlice` passes of a pixel, and a lane that drew a later slice is
+  // `pending` until the lane that holds the slice before it has published the pixel and its generator. The other
+  // instantiations hold none of this: their code is the whole-pixel loop as it was.
+  static_assert(!SLICED || (!DR && !STATS && MODE != 2 && MODE != 6), "pass slices: forward calls from the camera only");
+  const uint passSlice = SLICED ? job.passSlice : 0u;
+  const uint itemCount = SLICED ? job.tidCount * passSliceCount(job.passNum, passSlice) : job.tidCount;
+  bool havePixel = false, alive = false, drained = false, pending = false;
   uint bounce = 0, flags = 0;
   Rng  gen; gen.sx = gen.sy = 0;
   V3   rpos = v3(0, 0, 0), rdir = v3(0, 0, 1);
@@ -64,9 +74,12 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       else { float* o = job.outColor + (size_t)pixel * job.channels; o[0] = PIX(0); o[1] = PIX(1); o[2] = PIX(2); }
       job.gens[PIX_TID] = gen;                                           // kernel_ContributeToImage: m_randomGens[tid] = *gen (:605)
       havePixel = false;
+      // hand-over: the stores above become visible to every CU before the count of finished slices does (the last slice has no successor)
+      if (SLICED && (PIX_SLICE + 1u) * passSlice < job.passNum)
+        __hip_atomic_store(job.sliceDone + PIX_TID, PIX_SLICE + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- (2) work queue: ballot the idle lanes, one atomic per wave, prefix-sum the ranks --------------------------------
-    {
+    if constexpr (!SLICED) {
       const bool need = !alive && !havePixel && !drained;
       const unsigned long long mask = __ballot(need);
       if (mask != 0ull) {
@@ -75,7 +88,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
         base = __shfl(base, (int)(__ffsll((long long)mask) - 1));
         if (need) {
           const uint k = base + mbcnt64(mask);
-          const uint tid = job.tidBegin + (k / job.tidChunk) * job.tidChunk * job.tidStride + (k % job.tidChunk);
+          const uint tid = tidOfIndex(job.tidBegin, job.tidChunk, job.tidStride, k);
           if (k < job.tidCount && tid < job.tidEnd) {
             const uint XY = INRAYS ? 0u : job.packedXY[tid];
             gen = job.gens[tid];
@@ -86,6 +99,47 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
             havePixel = true;
           } else drained = true;
         }
+      }
+    } else {
+      const bool need = !alive && !havePixel && !drained && !pending;
+      bool ready = false;                                                   // this lane may load its pixel now
+      const unsigned long long mask = __ballot(need);
+      if (mask != 0ull) {
+        uint base = 0;
+        if (need && mbcnt64(mask) == 0u) base = atomicAdd(job.queue, (uint)__popcll(mask));
+        base = __shfl(base, (int)(__ffsll((long long)mask) - 1));
+        if (need) {
+          const uint k = base + mbcnt64(mask);
+          const SliceItem it = passSliceItem(k, job.tidCount, job.passNum, passSlice);
+          const uint tid = tidOfIndex(job.tidBegin, job.tidChunk, job.tidStride, it.index);
+          if (k < itemCount && tid < job.tidEnd) {
+            PIX_TID = tid; PIX_SLICE = it.slice; PIX_POLLS = 0u;
+            ready = it.slice == 0u; pending = it.slice != 0u;              // the first slice finds the pixel as the caller left it
+          } else drained = true;
+        }
+      }
+      // A pending lane polls ONCE per trip and never in a loop of its own: its wave-mates may hold the very slice it waits for. The poll is
+      // a relaxed agent-scope load; the acquire is one agent-scope fence, in wave-uniform control flow, once a lane's poll has matched.
+      bool matched = false;
+      if (pending) {
+        matched = __hip_atomic_load(job.sliceDone + PIX_TID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == PIX_SLICE;
+        if (matched) pending = false;
+        else if (++PIX_POLLS > job.slicePollLimit) {                        // bounded wait: give up, tell the host, take no more work
+          __hip_atomic_store(job.sliceError, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+          pending = false; drained = true;
+        }
+      }
+      if (__any(matched)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      ready = ready || matched;
+      if (ready) {
+        const uint tid = PIX_TID;
+        const uint XY = job.packedXY[tid];
+        gen = job.gens[tid];
+        const uint pixel = ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
+        if (job.channels == 1) { PIX(0) = job.outColor[pixel]; PIX(1) = 0.0f; PIX(2) = 0.0f; }
+        else { const float* o = job.outColor + (size_t)pixel * job.channels; PIX(0) = o[0]; PIX(1) = o[1]; PIX(2) = o[2]; }
+        PIX_XY = XY; PIX_PASSES = passSlicePasses(PIX_SLICE, job.passNum, passSlice);
+        havePixel = true;
       }
     }
     // ---- (3) regenerate: next pass of the pixel (kernel_InitEyeRay2) -----------------------------------------------------
@@ -109,7 +163,11 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       alive = true;
       if (STATS) nPaths++;
     }
-    if (!__any(alive)) break;
+    if (!__any(alive)) {
+      if (!SLICED || !__any(pending)) break;
+      __builtin_amdgcn_s_sleep(127);                                       // every lane that is left waits for a slice another wave holds
+      continue;
+    }
     STAMP(0); if (STATS) tTrips++;
 
     // ---- (4) closest hit: kernel_RayTrace2 -> RayQuery_NearestHit ----------------------------------------------------------
@@ -235,6 +293,8 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 #undef PIX_XY
 #undef PIX_TID
 #undef PIX_PASSES
+#undef PIX_SLICE
+#undef PIX_POLLS
   if (STATS) {
     // wave-reduce, one atomic per counter per wave
     unsigned long long v[8] = { nRays, st.nodes, st.tris, nHits, nShadow, nPaths, st.insts, 0ull };
@@ -279,8 +339,15 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   template __global__ void pathTraceKernel<STATS, DR, MODE, false, true,  false>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<STATS, DR, MODE, true,  true,  false>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<STATS, DR, MODE, false, false, false, true>(const DevScene, const Job);   /* the triangle sweep of tiny scenes */
+// the same five with pass slices (PathTrace from the camera: MODE 3, 0 and 7)
+#define HPT_INST4_SLICED(MODE) \
+  template __global__ void pathTraceKernel<false, false, MODE, false, false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, true,  false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, false, true,  false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, true,  true,  false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, false, false, false, true,  true>(const DevScene, const Job);
 #ifndef HPT_INST_GROUP
-#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..15"
+#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..19"
 #endif
 #if HPT_INST_GROUP == 1      // gltf + emissive scenes (every benchmark workload)
 HPT_INST4(false, false, 3)
@@ -304,6 +371,17 @@ HPT_INST4(false, false, 5)
 HPT_INST4(false, false, 6)
 #elif HPT_INST_GROUP == 14   // every BSDF branch, built for 4 waves per SIMD (scenes with few material types)
 HPT_INST4(false, false, 7)
+#elif HPT_INST_GROUP == 16   // pass slices: gltf + emissive scenes (the headline workload)
+HPT_INST4_SLICED(3)
+#elif HPT_INST_GROUP == 17   // pass slices: every BSDF branch
+HPT_INST4_SLICED(0)
+#elif HPT_INST_GROUP == 18   // pass slices: every BSDF branch at 4 waves per SIMD
+HPT_INST4_SLICED(7)
+#elif HPT_INST_GROUP == 19   // pass slices: moving instances (PathTrace only), both layouts
+template __global__ void pathTraceKernel<false, false, 0, false, false, true, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, true,  false, true, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, false, true,  true, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, true,  true,  true, false, true>(const DevScene, const Job);
 #elif HPT_INST_GROUP == 12   // thin films and moving instances
 template __global__ void pathTraceKernel<false, false, 4, false, false, true>(const DevScene, const Job);
 template __global__ void pathTraceKernel<false, false, 4, true,  false, true>(const DevScene, const Job);

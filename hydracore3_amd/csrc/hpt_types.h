@@ -277,6 +277,30 @@ HPT_HD bool sweepBoxMayHit(const float lo0, const float lo1, const float lo2, co
   return (fabsf(sd) < SWEEP_GRAZE * dSum) | (tn * 0.999999f <= tf * 1.000001f);
 }
 
+// ---- work items of the persistent megakernel (hpt_kernels.hip: pathTraceKernel; tests/cpp/pass_slice_items_test.cpp) ---------------------
+// A launch renders `tidCount` pixels with `passNum` passes each. With a pass slice s > 0 a pixel is handed out in ceil(passNum / s) items
+// of s passes (the last one shorter), slice-major: item k is slice k / tidCount of the pixel at index k % tidCount, so the slices of a pixel
+// enter the queue in ascending order and an item's predecessor (same index, slice - 1) is item k - tidCount. s = 0: one item per pixel.
+struct SliceItem { uint index, slice, first, passes; };     // pixel index in the launch, slice, first pass and number of passes of the slice
+HPT_HD uint passSliceCount(uint passNum, uint s) { return (s == 0u || s >= passNum) ? 1u : (passNum + s - 1u) / s; }
+HPT_HD uint passSliceFirst(uint slice, uint passNum, uint s) { return slice * ((s == 0u || s >= passNum) ? passNum : s); }
+HPT_HD uint passSlicePasses(uint slice, uint passNum, uint s)
+{
+  const uint len = (s == 0u || s >= passNum) ? passNum : s, first = slice * len;
+  return (passNum - first < len) ? passNum - first : len;
+}
+HPT_HD SliceItem passSliceItem(uint k, uint tidCount, uint passNum, uint s)
+{
+  SliceItem it;
+  it.slice = k / tidCount; it.index = k - it.slice * tidCount;
+  it.first = passSliceFirst(it.slice, passNum, s);
+  it.passes = passSlicePasses(it.slice, passNum, s);
+  return it;
+}
+// pixel index of a launch -> tid (Job::tidBegin / tidChunk / tidStride: every tidStride-th chunk of tidChunk tids, hpt_set_tid_interleave)
+HPT_HD uint tidOfIndex(uint tidBegin, uint tidChunk, uint tidStride, uint index)
+{ return tidBegin + (index / tidChunk) * tidChunk * tidStride + (index % tidChunk); }
+
 struct TexRec
 {
   uint w, h, format, flags, addrU, addrV, filter, pad;

@@ -547,6 +547,13 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               estimate at build time is followed, in the same hpt_commit_scene, by a build (on the device for a device-built tree, on the host
  *               for a host-built one). 1 .. 99 is an argument error.
  *   "node_min"  voted exit of the inner-node loop (0..63, applied at the next hpt_commit_scene; default chosen per scene).
+ *   "pass_slice"  PathTraceBlock under the persistent megakernel (not NaivePathTrace, not scenes with thin films): n > 0 hands a pixel out in work items of n passes; the pixel's
+ *               value and generator pass from item to item through device memory in pass order, so the frame and m_randomGens are bit for bit
+ *               those of n = 0 (a work item is a whole pixel). n >= a_passNum is n = 0. PathTraceDR, PathTraceFromInputRays and the other
+ *               schedules ignore it. A waiting lane that exceeds its poll limit makes the call (or, for the device-pointer forms, the next
+ *               call or hpt_last_kernel_ms) return HPT_ERR_STATE. The limit counts polls (about 3 us each when a whole wave waits; at least 2^20),
+ *               not time: with n set by hand on a heavy scene a healthy call could reach it. Never set: 256 in calls with at least two pixels per lane of the grid and at
+ *               least 512 passes, else 0. Environment: HPT_PASS_SLICE.
  * A member of the reference that is set in its constructor:
  *   "dr_grad_mode"  IntegratorDR's a_gradMode (integrator_dr.h; default 1). 0: RayTraceDR renders and returns the loss through the ordinary
  *               sampler and writes no gradient (integrator_dr.cpp:99, 432-438). PathTraceDR does not read it.
@@ -608,8 +615,8 @@ int  hpt_read_accel(hpt_ctx* ctx, int what, void* dst, uint64_t capacityBytes, u
 int  hpt_get_schedule(hpt_ctx* ctx, int* lastSchedule, uint32_t* lastIterations);
 /* What the last hpt_path_trace_* call walked (no counterpart in the reference: lets a test assert WHICH kernels produced a frame):
  * out[0] = schedule (1 .. 4), out[1] = 1 when rays walked the 4-wide compressed tree, out[2] = 1 when surface data came from the 64-byte
- * shading records, out[3] = 1 when the traversal stacks had an HBM part. */
-int  hpt_get_last_launch(hpt_ctx* ctx, uint32_t out[4]);
+ * shading records, out[3] = 1 when the traversal stacks had an HBM part, out[4] = passes per work item ("pass_slice"; 0 = whole pixels). */
+int  hpt_get_last_launch(hpt_ctx* ctx, uint32_t out[5]);
 /* With hpt_set_option("dbg_stack_witness", 1): out[0] = words of the traversal stacks' HBM part that no longer hold the fill word after the last
  * launch, i.e. that a lane pushed (the stack entries beyond the ones kept in LDS), out[1] = words that were filled before it. Waits for the device,
  * copies the buffer and counts on the host; it does not interpret the buffer's layout (the wavefront schedule's per-group slices count alike).
