@@ -92,6 +92,7 @@ ABI = {
     "hpt_set_option": (_i, [_vp, C.c_char_p, _i]),
     "hpt_get_commit_time": (_i, [_vp, C.POINTER(_f)]),
     "hpt_get_refit_info": (_i, [_vp, C.POINTER(_f)]),
+    "hpt_get_build_info": (_i, [_vp, C.POINTER(_f)]),
     "hpt_read_accel": (_i, [_vp, _i, _vp, _u64, C.POINTER(_u64), C.POINTER(_u32)]),
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
@@ -736,6 +737,13 @@ class HipIntegrator:
         out = (C.c_float * 4)()
         self._chk(self.L.hpt_get_refit_info(self.h, out))
         return {"build": out[0], "after": out[1], "levels": int(out[2]), "rejected": int(out[3]) == 1}
+
+    def build_info(self):
+        """hpt_get_build_info: the treelet passes ("device_build_quality") of the last CommitScene when it built on the device: passes run, treelets
+        examined and rewritten over all passes, device ms spent in them. All zero after a host build or a refit."""
+        out = (C.c_float * 4)()
+        self._chk(self.L.hpt_get_build_info(self.h, out))
+        return {"passes": int(out[0]), "examined": int(out[1]), "rewritten": int(out[2]), "ms": out[3]}
 
     def read_accel(self):
         """hpt_read_accel: the committed single-level tree as it lies in device memory: (nodes [BVH_NODE_DTYPE], tris [BVH_TRI_DTYPE], rootRef).

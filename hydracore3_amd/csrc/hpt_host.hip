@@ -213,6 +213,7 @@ struct hpt_ctx
   int  wfBlocksPerCU = 0;
   size_t instTris = 0;                   // instanced triangles of the committed scene
   // CommitScene on the device (hpt_lbvh.hip): -1 = by CommitScene's options (BUILD_LOW / BUILD_MEDIUM without BUILD_HIGH), 0 = never, 1 = whenever the single-level layout is built
+  int deviceBuildQuality = 0; float buildInfo[4] = { 0.0f, 0.0f, 0.0f, 0.0f };   // hpt_set_option("device_build_quality", passes); hpt_get_build_info: the last device build's treelet passes
   int deviceBuild = -1; void* lbvh = nullptr; unsigned long long geomVersion = 1, lbvhGeomVersion = 0; std::vector<size_t> lbvhPosOff, lbvhIdxOff;
   uint lastSchedule = 1, lastWfIters = 0;
   uint lastWide = 0, lastShadeRecords = 0, lastDeep = 0;          // what the last launch walked: 4-wide compressed tree, 64-byte shading records, HBM part of the stacks
@@ -599,7 +600,7 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   }
   const double tDev0 = now_ms();
   LbvhResult r;
-  if (!lbvhBuild(c->lbvh, li.data(), (uint)ni, n, c->dNodes.p, c->dTris.p, c->dNodes4.p, (uint)c->dNodes4.n, wantWide, refit, r, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build): " + err);
+  if (!lbvhBuild(c->lbvh, li.data(), (uint)ni, n, c->dNodes.p, c->dTris.p, c->dNodes4.p, (uint)c->dNodes4.n, wantWide, refit, (uint)c->deviceBuildQuality, r, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build): " + err);
   const double tDev1 = now_ms();
   if (r.depth + 1u > MAX_STACK) return HPT_ERR_STATE;         // a degenerate input (the Morton curve cannot separate it): the host's depth-capped build takes over
   c->instTris = instTris; c->anyMotion = false;
@@ -620,8 +621,9 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   c->S.nodeMin = c->nodeMinOverride >= 0 ? (uint)c->nodeMinOverride : (c->sahVisits >= HEAVY_SAH_VISITS ? 16u : 0u);
   c->S.nodeMin4 = c->nodeMinOverride >= 0 ? (uint)c->nodeMinOverride : (c->sahVisits >= HEAVY_SAH_VISITS ? 32u : 0u);
   c->stackNeeded = r.depth + 1u;
-  if (std::getenv("HPT_DEBUG_ACCEL")) std::fprintf(stderr, "[hydra_hip] device-built single-level BVH: %zu triangles, depth %u, sah visits %.2f; 4-wide: %u nodes, depth %u; %.2f ms of kernels\n",
-                                                  instTris, r.depth, c->sahVisits, r.nodes4Count, r.depth4, tDev1 - tDev0);
+  c->buildInfo[0] = (float)r.passesRun; c->buildInfo[1] = (float)r.treeletsExamined; c->buildInfo[2] = (float)r.treeletsRewritten; c->buildInfo[3] = r.passMs;
+  if (std::getenv("HPT_DEBUG_ACCEL")) std::fprintf(stderr, "[hydra_hip] device-built single-level BVH: %zu triangles, depth %u, sah visits %.2f; 4-wide: %u nodes, depth %u; %.2f ms of kernels; treelet passes %u (%u of %u treelets rewritten, %.2f ms)\n",
+                                                  instTris, r.depth, c->sahVisits, r.nodes4Count, r.depth4, tDev1 - tDev0, r.passesRun, r.treeletsRewritten, r.treeletsExamined, r.passMs);
   c->tCommit[0] = float(tDev0 - tBuild0); c->tCommit[1] = 0.0f; c->tCommit[2] = float(tDev1 - tDev0); c->tCommit[3] = 2.0f;   // host preparation + uploads, -, device build, "built on the device"
   c->accelCommitted = true; c->shadeTrisDirty = true;
   return HPT_OK;
@@ -697,6 +699,7 @@ try {
   if (!c) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
   c->refitRejected = false;
+  for (float& v : c->buildInfo) v = 0.0f;                     // (a device build that is kept fills it in)
   int onDevice = -1;                                         // 1 / 0: a rejected refit is followed by a build of the kind the tree came from
   if (c->flatRefittable && c->refitEnabled && c->S.flatMode == 1u && (!c->flatOnDevice || c->deviceRefit)) {
     const int rc = refit_flat(c);
@@ -3416,6 +3419,7 @@ try {
   else if (k == "bw_wide") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "bw_wide: -1 automatic, 0, 1"); c->bwWide = value; }
   else if (k == "bw_node_min") { if (value < 0 || value > 64) return c->fail(HPT_ERR_ARG, "bw_node_min: 0..64"); c->bwNodeMin = (uint)value; }
   else if (k == "device_build") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "device_build: -1 by CommitScene's options, 0 never, 1 always"); c->deviceBuild = value; c->accelCommitted = false; c->flatRefittable = false; }
+  else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
@@ -3438,6 +3442,13 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_get_commit_time"); }
+extern "C" int hpt_get_build_info(hpt_ctx* c, float out[4])
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  for (int i = 0; i < 4; i++) out[i] = c->buildInfo[i];
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_get_build_info"); }
 extern "C" int hpt_get_refit_info(hpt_ctx* c, float out[4])
 try {
   if (!c || !out) return HPT_ERR_ARG;

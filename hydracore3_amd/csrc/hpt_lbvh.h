@@ -16,6 +16,9 @@ struct LbvhResult
   uint rootRef = REF_NONE, numNodes = 0, depth = 0, nodes4Count = 0, depth4 = 0; float sahVisits = 1.0f;
   // what a refit needs (LbvhRefitOut): levelCount[l] nodes of level l, level 0 = the root's, the last level = the nodes over leaves only
   uint numLevels = 0, levelCount[LBVH_MAX_LEVELS] = {};
+  // the treelet passes ("device_build_quality"): passes run, treelets of three leaves or more examined and rewritten over all passes, milliseconds between
+  // the device events around the passes
+  uint passesRun = 0, treeletsExamined = 0, treeletsRewritten = 0; float passMs = 0.0f;
 };
 // Caller-owned device arrays the build fills for a later refit (hpt_host.hip: refit_flat), both optional:
 // levelIds (n - 1 entries): the emitted nodes grouped by level, a level = the node's height in the emitted tree counted down from the root's, so a
@@ -28,9 +31,10 @@ void  lbvhDestroy(void* scratch);
 // copies every mesh's positions (3 floats per vertex) and indices to the device; posOffset / idxOffset receive each mesh's place
 bool  lbvhUploadGeometry(void* scratch, const std::vector<const float*>& pos, const std::vector<size_t>& posFloats, const std::vector<const uint*>& idx, const std::vector<size_t>& idxCount,
                          std::vector<size_t>& posOffset, std::vector<size_t>& idxOffset, std::string& err);
-// builds into caller-owned device arrays: nodes (n - 1 entries), tris (n), nodes4 (cap4 entries; skipped when !wantWide)
+// builds into caller-owned device arrays: nodes (n - 1 entries), tris (n), nodes4 (cap4 entries; skipped when !wantWide).
+// qualityPasses: treelet restructuring passes over the hierarchy before anything is emitted (0: the plain Karras tree, nothing else launched)
 bool  lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNode* nodes, BvhTri* tris, BvhNode4* nodes4, uint cap4, bool wantWide, const LbvhRefitOut& refit,
-                 LbvhResult& out, std::string& err);
+                 uint qualityPasses, LbvhResult& out, std::string& err);
 // moved vertices of a built tree: copies the positions of the meshes listed in `geoms` to their place in the uploaded geometry (posOffset as
 // lbvhUploadGeometry returned it) and rewrites, in the build's expressions, the records in `tris` (n of them) of the instances flagged in
 // instDirty (ni bytes); everything else stays. The sorted order of the last build is kept by the scratch until the next one.

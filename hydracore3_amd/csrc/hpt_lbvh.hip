@@ -12,10 +12,12 @@
 // tree's (tests/test_gpu_parity.py::test_device_built_tree_*).
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 #include "hpt_lbvh.h"
+#include "treelet_opt.h"
 
 namespace hpt {
 
@@ -31,6 +33,8 @@ struct Scratch
   // hierarchy: inner node i in [0, n - 1)
   uint *childL = nullptr, *childR = nullptr, *parent = nullptr, *leafParent = nullptr, *first = nullptr, *last = nullptr, *flags = nullptr, *depth = nullptr;
   uint* height = nullptr;                 // per inner node: its height in the EMITTED tree (0 = both children are leaves), see lbvhFitKernel
+  unsigned char* folded = nullptr;        // per inner node: 1 = the emitter folds its subtree into one leaf; decided once, on the Karras tree (lbvhHierarchyKernel)
+  uint* passIds = nullptr;                // treelet passes only: the emitted nodes grouped by height (allocated with the first pass)
   float* nodeBox = nullptr;               // [6][n - 1]
   uint2 *frontA = nullptr, *frontB = nullptr;
   uint* counters = nullptr;               // see LbvhCounters
@@ -42,7 +46,7 @@ struct Scratch
   size_t cap = 0;
   void freeAll()
   {
-    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, height, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo, instDirty };
+    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, height, folded, passIds, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo, instDirty };
     for (void* p : ps) if (p) (void)hipFree(p);
     *this = Scratch();
   }
@@ -53,6 +57,7 @@ struct LbvhCounters
 {
   uint sceneLo[3], sceneHi[3]; uint count4; uint frontCount[2]; uint depth4; float sahSum; uint pad;
   uint levelCount[LBVH_MAX_LEVELS], levelFill[LBVH_MAX_LEVELS];       // emitted nodes per height; where the next node of that height goes in the level lists
+  uint treelet[2 * 64];                                               // treelet passes: {examined, rewritten}, spread over 64 slots to keep the atomics apart
 };
 
 HPT_HD uint floatKey(float f) { const uint b = hptFloatToBits(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }       // monotonic float -> uint
@@ -139,7 +144,7 @@ __device__ inline int delta(const unsigned long long* keys, int n, int i, int j)
   if (a != b) return __clzll((long long)(a ^ b));
   return 64 + __clz(i ^ j);                                             // equal keys: the index decides, so every pair differs
 }
-__global__ void __launch_bounds__(256) lbvhHierarchyKernel(const unsigned long long* __restrict__ keys, int n, uint* childL, uint* childR, uint* parent, uint* leafParent, uint* first, uint* last)
+__global__ void __launch_bounds__(256) lbvhHierarchyKernel(const unsigned long long* __restrict__ keys, int n, uint* childL, uint* childR, uint* parent, uint* leafParent, uint* first, uint* last, unsigned char* folded)
 {
   const int i = (int)(blockIdx.x * 256u + threadIdx.x);
   if (i >= n - 1) return;
@@ -161,12 +166,13 @@ __global__ void __launch_bounds__(256) lbvhHierarchyKernel(const unsigned long l
   if (leafL) leafParent[gamma] = (uint)i; else parent[gamma] = (uint)i;
   if (leafR) leafParent[gamma + 1] = (uint)i; else parent[gamma + 1] = (uint)i;
   first[i] = (uint)lo; last[i] = (uint)hi;
+  folded[i] = (uint)(hi - lo) + 1u <= (uint)BVH_LEAF_MAX ? 1 : 0;      // a contiguous record range: true of the Karras tree only, so it is decided here for good
   if (i == 0) parent[0] = 0xFFFFFFFFu;
 }
 
 // ---- 4. boxes bottom-up: the second thread to arrive at a node fits it ---------------------------------------------------------------------------
 __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ triBox, const uint* __restrict__ vals, uint n, const uint* __restrict__ childL, const uint* __restrict__ childR,
-                                                     const uint* __restrict__ parent, const uint* __restrict__ leafParent, const uint* __restrict__ first, const uint* __restrict__ last,
+                                                     const uint* __restrict__ parent, const uint* __restrict__ leafParent, const unsigned char* __restrict__ folded,
                                                      uint* flags, float* nodeBox, uint* depth, uint* height)
 {
   const uint k = blockIdx.x * 256u + threadIdx.x;
@@ -188,7 +194,7 @@ __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ t
       } else {
         for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __hip_atomic_load(&nodeBox[(size_t)a * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); hi[a] = fmaxf(hi[a], __hip_atomic_load(&nodeBox[(size_t)(3 + a) * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
         dep = max(dep, __hip_atomic_load(&depth[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        if (last[ch] - first[ch] + 1u > (uint)BVH_LEAF_MAX) hgt = max(hgt, __hip_atomic_load(&height[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u);
+        if (!folded[ch]) hgt = max(hgt, __hip_atomic_load(&height[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1u);
       }
     }
     for (int a = 0; a < 3; a++) { __hip_atomic_store(&nodeBox[(size_t)a * m + node], lo[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); __hip_atomic_store(&nodeBox[(size_t)(3 + a) * m + node], hi[a], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
@@ -198,25 +204,126 @@ __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ t
   }
 }
 
+// ---- 4b. treelet restructuring (Karras & Aila 2013; hpt_set_option("device_build_quality", passes)) ---------------------------------------------------
+// One wave = one treelet: the node `root` and up to 7 treelet leaves, grown from the root's two children by expanding, again and again, the leaf
+// with the largest half-area that may be expanded (an inner node the emitter does not fold; ties: the lowest leaf slot). The optimal topology over
+// the leaves is found by the subset recurrence of treelet_opt.h - the 128 subsets lie two per lane, areas, costs and partitions in LDS, one
+// barrier per subset size - and the treelet's inner nodes are rewritten in place (the root keeps its slot, box and parent) only when the optimum
+// is strictly below the present topology's cost, summed by the same formula. Boxes are unpadded unions of the leaf boxes: the same floats whatever
+// the order, so the pass moves no box of a node it keeps.
+// Schedule: one launch per height of the emitted tree as it was BEFORE the pass, ascending (lbvhBuild). Nodes of equal height are never nested and
+// a rewrite keeps the set of nodes below its root, so the waves of a launch touch disjoint nodes; kernel boundaries order the launches. No wave
+// waits for another.
+__device__ inline void treeletLoadLeaf(uint ref, uint n, const unsigned char* folded, const float* triBox, const uint* vals, const float* nodeBox, float box[6], float& area, bool& expandable)
+{
+  if (ref & 0x80000000u) { const uint t = vals[ref & 0x7FFFFFFFu]; for (int a = 0; a < 6; a++) box[a] = triBox[(size_t)a * n + t]; expandable = false; }
+  else { for (int a = 0; a < 6; a++) box[a] = nodeBox[(size_t)a * (n - 1u) + ref]; expandable = !folded[ref]; }
+  area = treeletHalfArea(box, box + 3);
+}
+__global__ void __launch_bounds__(64) lbvhTreeletKernel(const uint* __restrict__ ids, uint count, uint n, uint* childL, uint* childR, uint* parent, uint* leafParent,
+                                                        const unsigned char* __restrict__ folded, const float* __restrict__ triBox, const uint* __restrict__ vals, float* nodeBox, LbvhCounters* C)
+{
+  __shared__ float sLeafBox[TREELET_LEAVES][6];
+  __shared__ uint sLeafRef[TREELET_LEAVES], sSlot[TREELET_LEAVES - 1], sSlotMask[TREELET_LEAVES - 1], sSlotLeft[TREELET_LEAVES - 1], sStack[TREELET_LEAVES];
+  __shared__ float sArea[TREELET_SUBSETS], sCost[TREELET_SUBSETS], sNow[TREELET_SUBSETS];
+  __shared__ unsigned char sPart[TREELET_SUBSETS];
+  if (blockIdx.x >= count) return;
+  const int lane = (int)threadIdx.x;
+  const uint root = ids[blockIdx.x];
+  if (root + 1u >= n) return;
+  // -- the treelet: leaf j lives in lane j (reference, box, half-area), inner slot e in lane e (the leaves below it, and below its left child)
+  uint myRef = 0u; float myBox[6] = { 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f }, myArea = 0.0f; bool myExp = false;
+  uint slotMask = lane == 0 ? 3u : 0u, slotLeft = lane == 0 ? 1u : 0u;
+  if (lane < 2) { myRef = lane == 0 ? childL[root] : childR[root]; treeletLoadLeaf(myRef, n, folded, triBox, vals, nodeBox, myBox, myArea, myExp); }
+  if (lane == 0) sSlot[0] = root;
+  int k = 2;
+  while (k < TREELET_LEAVES) {
+    float a = (lane < k && myExp) ? myArea : -1.0f; int who = lane & 7;
+    for (int o = 4; o > 0; o >>= 1) {                                    // the largest half-area among lanes 0..7, ties to the lowest lane
+      const float oa = __shfl_xor(a, o); const int ow = __shfl_xor(who, o);
+      if (oa > a || (oa == a && ow < who)) { a = oa; who = ow; }
+    }
+    a = __shfl(a, 0); who = __shfl(who, 0);
+    if (a < 0.0f) break;                                                 // nothing left to expand
+    const uint node = __shfl(myRef, who);
+    if (lane == 0) sSlot[k - 1] = node;
+    if (lane < k - 1 && ((slotMask >> who) & 1u)) { slotMask |= 1u << k; if ((slotLeft >> who) & 1u) slotLeft |= 1u << k; }
+    if (lane == k - 1) { slotMask = (1u << who) | (1u << k); slotLeft = 1u << who; }
+    if (lane == who || lane == k) { myRef = lane == who ? childL[node] : childR[node]; treeletLoadLeaf(myRef, n, folded, triBox, vals, nodeBox, myBox, myArea, myExp); }
+    k++;
+  }
+  if (k < 3) return;                                                     // two leaves have one topology
+  if (lane < k) { sLeafRef[lane] = myRef; for (int a = 0; a < 6; a++) sLeafBox[lane][a] = myBox[a]; }
+  if (lane < k - 1) { sSlotMask[lane] = slotMask; sSlotLeft[lane] = slotLeft; }
+  for (int j = k + lane; j < TREELET_LEAVES; j += 64) for (int a = 0; a < 6; a++) sLeafBox[j][a] = 0.0f;   // (never selected: the subsets stay below 1 << k)
+  __syncthreads();
+  // -- the recurrence of treelet_opt.h, subsets lane and lane + 64
+  const uint full = (1u << k) - 1u;
+  for (uint s = (uint)lane; s < (uint)TREELET_SUBSETS; s += 64u) {
+    float lo[3], hi[3];
+    const float ar = (s != 0u && s <= full) ? treeletUnion(s, sLeafBox, lo, hi) : 0.0f;
+    sArea[s] = ar; sCost[s] = 0.0f; sNow[s] = 0.0f; sPart[s] = 0;
+  }
+  __syncthreads();
+  for (int size = 2; size <= k; size++) {
+    for (uint s = (uint)lane; s < (uint)TREELET_SUBSETS; s += 64u) if (s <= full && __popc(s) == size) {
+      uint p; const float c = treeletBestSplit(s, sCost, p);
+      sCost[s] = sArea[s] + c; sPart[s] = (unsigned char)p;
+    }
+    __syncthreads();
+  }
+  // -- the present topology's cost by the same formula (children of a slot have greater slot numbers), then the rewrite; one lane
+  if (lane == 0) {
+    for (int e = k - 2; e >= 0; e--) { const uint s = sSlotMask[e], l = sSlotLeft[e]; sNow[s] = sArea[s] + (sNow[l] + sNow[s ^ l]); }
+    const bool better = sCost[full] < sNow[full];
+    atomicAdd(&C->treelet[2u * (blockIdx.x & 63u)], 1u);
+    if (better) {
+      atomicAdd(&C->treelet[2u * (blockIdx.x & 63u) + 1u], 1u);
+      const size_t m = n - 1u;
+      int next = 1, sp = 1;
+      sStack[0] = full;                                                  // entries: inner slot << 8 | leaf set
+      while (sp > 0) {
+        const uint it = sStack[--sp], s = it & 0xFFu, node = sSlot[it >> 8];
+        const uint p = sPart[s];
+        for (int c = 0; c < 2; c++) {
+          const uint cs = c == 0 ? p : (s ^ p);
+          uint child;
+          if ((cs & (cs - 1u)) == 0u) {                                  // one leaf
+            child = sLeafRef[__ffs((int)cs) - 1];
+            if (child & 0x80000000u) leafParent[child & 0x7FFFFFFFu] = node; else parent[child] = node;
+          } else {
+            const int e = next++;
+            child = sSlot[e];
+            parent[child] = node;
+            float lo[3], hi[3]; treeletUnion(cs, sLeafBox, lo, hi);
+            for (int a = 0; a < 3; a++) { nodeBox[(size_t)a * m + child] = lo[a]; nodeBox[(size_t)(3 + a) * m + child] = hi[a]; }
+            sStack[sp++] = ((uint)e << 8) | cs;
+          }
+          if (c == 0) childL[node] = child; else childR[node] = child;
+        }
+      }
+    }
+  }
+}
+
 // ---- 5. BvhNode records (both child boxes in the parent, hpt_types.h), leaves of <= BVH_LEAF_MAX triangles; triangle records in leaf order ----
-__device__ inline uint childRef(uint ch, const uint* first, const uint* last, uint& leafFirst, uint& leafCount)
+__device__ inline uint childRef(uint ch, const uint* first, const uint* last, const unsigned char* folded, uint& leafFirst, uint& leafCount)
 {
   if (ch & 0x80000000u) { leafFirst = ch & 0x7FFFFFFFu; leafCount = 1u; return REF_LEAF | (1u << 28) | leafFirst; }
-  const uint cnt = last[ch] - first[ch] + 1u;
-  if (cnt <= (uint)BVH_LEAF_MAX) { leafFirst = first[ch]; leafCount = cnt; return REF_LEAF | (cnt << 28) | leafFirst; }
+  if (folded[ch]) { const uint cnt = last[ch] - first[ch] + 1u; leafFirst = first[ch]; leafCount = cnt; return REF_LEAF | (cnt << 28) | leafFirst; }   // (a folded subtree is never restructured: its range stays)
   leafCount = 0u; return ch;
 }
-__global__ void __launch_bounds__(256) lbvhEmitKernel(uint n, const uint* __restrict__ childL, const uint* __restrict__ childR, const uint* __restrict__ first, const uint* __restrict__ last,
+__global__ void __launch_bounds__(256) lbvhEmitKernel(uint n, const uint* __restrict__ childL, const uint* __restrict__ childR, const uint* __restrict__ first, const uint* __restrict__ last, const unsigned char* __restrict__ folded,
                                                       const float* __restrict__ triBox, const uint* __restrict__ vals, const float* __restrict__ nodeBox, BvhNode* nodes, LbvhCounters* C)
 {
   const uint i = blockIdx.x * 256u + threadIdx.x;
   float sah = 0.0f;
-  if (i + 1u < n && last[i] - first[i] + 1u > (uint)BVH_LEAF_MAX) {
+  if (i + 1u < n && !folded[i]) {
     const size_t m = n - 1;
     BvhNode nd;
     const uint cs[2] = { childL[i], childR[i] };
     for (int c = 0; c < 2; c++) {
-      uint lf, lc; const uint ref = childRef(cs[c], first, last, lf, lc);
+      uint lf, lc; const uint ref = childRef(cs[c], first, last, folded, lf, lc);
       float lo[3], hi[3];
       if (cs[c] & 0x80000000u) { const uint t = vals[cs[c] & 0x7FFFFFFFu]; for (int a = 0; a < 3; a++) { lo[a] = triBox[(size_t)a * n + t]; hi[a] = triBox[(size_t)(3 + a) * n + t]; } }
       else for (int a = 0; a < 3; a++) { lo[a] = nodeBox[(size_t)a * m + cs[c]]; hi[a] = nodeBox[(size_t)(3 + a) * m + cs[c]]; }
@@ -303,19 +410,19 @@ __global__ void lbvhResetFrontKernel(LbvhCounters* C, uint level) { C->frontCoun
 // Histogram over the heights, a scan over its <= 64 bins, a scatter. Level l of the lists holds the nodes of height (root's height - l): level 0 is
 // the root alone and the refit walks the levels from the last to the first, as it does for a host-built tree. The order inside a level is whatever
 // the atomics make it. Heights are clamped to the bins: a tree that deep is given back to the host's builder (hpt_host.hip) and its lists are not used.
-__device__ inline bool emittedHeight(uint i, uint n, const uint* first, const uint* last, const uint* height, uint& h)
+__device__ inline bool emittedHeight(uint i, uint n, const unsigned char* folded, const uint* height, uint& h)
 {
-  if (i + 1u >= n || last[i] - first[i] + 1u <= (uint)BVH_LEAF_MAX) return false;
+  if (i + 1u >= n || folded[i]) return false;
   h = min(height[i], LBVH_MAX_LEVELS - 1u);
   return true;
 }
-__global__ void __launch_bounds__(256) lbvhLevelHistKernel(uint n, const uint* __restrict__ first, const uint* __restrict__ last, const uint* __restrict__ height, LbvhCounters* C)
+__global__ void __launch_bounds__(256) lbvhLevelHistKernel(uint n, const unsigned char* __restrict__ folded, const uint* __restrict__ height, LbvhCounters* C)
 {
   __shared__ uint cnt[LBVH_MAX_LEVELS];
   if (threadIdx.x < LBVH_MAX_LEVELS) cnt[threadIdx.x] = 0u;
   __syncthreads();
   uint h;
-  if (emittedHeight(blockIdx.x * 256u + threadIdx.x, n, first, last, height, h)) atomicAdd(&cnt[h], 1u);
+  if (emittedHeight(blockIdx.x * 256u + threadIdx.x, n, folded, height, h)) atomicAdd(&cnt[h], 1u);
   __syncthreads();
   if (threadIdx.x < LBVH_MAX_LEVELS && cnt[threadIdx.x]) atomicAdd(&C->levelCount[threadIdx.x], cnt[threadIdx.x]);
 }
@@ -326,14 +433,14 @@ __global__ void __launch_bounds__(64) lbvhLevelScanKernel(const uint* __restrict
   for (uint g = h + 1u; g <= top; g++) before += C->levelCount[g];
   C->levelFill[h] = before;
 }
-__global__ void __launch_bounds__(256) lbvhLevelScatterKernel(uint n, const uint* __restrict__ first, const uint* __restrict__ last, const uint* __restrict__ height, LbvhCounters* C, uint* levelIds)
+__global__ void __launch_bounds__(256) lbvhLevelScatterKernel(uint n, const unsigned char* __restrict__ folded, const uint* __restrict__ height, LbvhCounters* C, uint* levelIds)
 {
   __shared__ uint cnt[LBVH_MAX_LEVELS], base[LBVH_MAX_LEVELS];
   if (threadIdx.x < LBVH_MAX_LEVELS) cnt[threadIdx.x] = 0u;
   __syncthreads();
   const uint i = blockIdx.x * 256u + threadIdx.x;
   uint h = 0u, rank = 0u;
-  const bool emitted = emittedHeight(i, n, first, last, height, h);
+  const bool emitted = emittedHeight(i, n, folded, height, h);
   if (emitted) rank = atomicAdd(&cnt[h], 1u);
   __syncthreads();
   if (threadIdx.x < LBVH_MAX_LEVELS && cnt[threadIdx.x]) base[threadIdx.x] = atomicAdd(&C->levelFill[threadIdx.x], cnt[threadIdx.x]);
@@ -386,7 +493,7 @@ bool lbvhUploadGeometry(void* scratch, const std::vector<const float*>& pos, con
   return true;
 }
 
-bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNode* nodes, BvhTri* tris, BvhNode4* nodes4, uint cap4, bool wantWide, const LbvhRefitOut& refit, LbvhResult& out, std::string& err)
+bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNode* nodes, BvhTri* tris, BvhNode4* nodes4, uint cap4, bool wantWide, const LbvhRefitOut& refit, uint qualityPasses, LbvhResult& out, std::string& err)
 {
   Scratch& S = *(Scratch*)scratch;
   out = LbvhResult();
@@ -395,10 +502,11 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   if (n > S.cap) {
     const size_t c = n;
     bool ok = ensure(S.triBox, 6 * c) && ensure(S.keysIn, c) && ensure(S.keysOut, c) && ensure(S.valsIn, c) && ensure(S.valsOut, c) && ensure(S.childL, c) && ensure(S.childR, c) &&
-              ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.height, c) && ensure(S.nodeBox, 6 * c) &&
+              ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.height, c) && ensure(S.folded, c) && ensure(S.nodeBox, 6 * c) &&
               ensure(S.frontA, c) && ensure(S.frontB, c);
     if (!ok) { err = "hipMalloc (build scratch)"; S.cap = 0; return false; }
     S.cap = c;
+    if (S.passIds) { (void)hipFree(S.passIds); S.passIds = nullptr; }
     size_t bytes = 0;
     LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 63, nullptr));
     if (S.sortTemp) (void)hipFree(S.sortTemp);
@@ -439,9 +547,54 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   LCHK(hipMemsetAsync(S.flags, 0, (size_t)n * sizeof(uint), nullptr));
   LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
   LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
-  lbvhHierarchyKernel<<<grdN, blk>>>(S.keysOut, (int)n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last);
-  lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.flags, S.nodeBox, S.depth, S.height);
-  lbvhEmitKernel<<<grdN, blk>>>(n, S.childL, S.childR, S.first, S.last, S.triBox, S.valsOut, S.nodeBox, nodes, C);
+  lbvhHierarchyKernel<<<grdN, blk>>>(S.keysOut, (int)n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.folded);
+  lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+  if (qualityPasses) {
+    // "device_build_quality": treelet passes over the whole tree. Per pass: the emitted nodes grouped by their present height (the kernels of section 7,
+    // into a list of the build's own), one lbvhTreeletKernel launch per height from 1 up, then the fit again for the new heights and depths
+    // (the boxes it writes are the ones the pass left: unions are exact). Everything below - records, cost, 4-wide tree, level lists - reads the result.
+    if (!S.passIds && !ensure(S.passIds, S.cap)) { err = "hipMalloc (treelet pass lists)"; return false; }
+    const size_t levelWords = offsetof(LbvhCounters, levelCount), levelBytes = 2 * LBVH_MAX_LEVELS * sizeof(uint);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    LCHK(hipEventCreate(&ev0));
+    if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); err = "hipEventCreate"; return false; }
+    auto passes = [&]() -> bool {
+      LCHK(hipEventRecord(ev0, nullptr));
+      for (uint pass = 0; pass < qualityPasses; pass++) {
+        uint rootHeight = 0;
+        LCHK(hipMemcpy(&rootHeight, S.height, sizeof(uint), hipMemcpyDeviceToHost));
+        // height 0: no treelet of three leaves. A height in the last bin is clamped there with every greater one (emittedHeight), so its list
+        // could hold nested nodes: such a tree is deeper than the traversal stack anyway and stays as it is
+        if (rootHeight == 0u || rootHeight >= LBVH_MAX_LEVELS - 1u) break;
+        lbvhLevelHistKernel<<<grdN, blk>>>(n, S.folded, S.height, C);
+        lbvhLevelScanKernel<<<1, LBVH_MAX_LEVELS>>>(S.height, C);
+        lbvhLevelScatterKernel<<<grdN, blk>>>(n, S.folded, S.height, C, S.passIds);
+        uint cnt[LBVH_MAX_LEVELS];
+        LCHK(hipMemcpy(cnt, (const char*)S.counters + levelWords, sizeof(cnt), hipMemcpyDeviceToHost));
+        std::vector<uint> off(rootHeight + 2u, 0u);                      // a height's nodes lie behind those of the greater heights (lbvhLevelScanKernel)
+        for (uint h = rootHeight; h-- > 0u;) off[h] = off[h + 1u] + cnt[h + 1u];
+        for (uint h = 1u; h <= rootHeight; h++) {
+          if (cnt[h] == 0u || (size_t)off[h] + cnt[h] > (size_t)n - 1u) continue;
+          lbvhTreeletKernel<<<dim3(cnt[h]), dim3(64)>>>(S.passIds + off[h], cnt[h], n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.triBox, S.valsOut, S.nodeBox, C);
+        }
+        LCHK(hipMemsetAsync((char*)S.counters + levelWords, 0, levelBytes, nullptr));
+        LCHK(hipMemsetAsync(S.flags, 0, (size_t)n * sizeof(uint), nullptr));
+        LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
+        LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
+        lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+        out.passesRun = pass + 1u;
+      }
+      LCHK(hipEventRecord(ev1, nullptr));
+      LCHK(hipEventSynchronize(ev1));
+      LCHK(hipEventElapsedTime(&out.passMs, ev0, ev1));
+      if (out.passesRun == 0u) out.passMs = 0.0f;                          // (nothing ran: nothing to report)
+      return true;
+    };
+    const bool ok = passes();
+    (void)hipEventDestroy(ev0); (void)hipEventDestroy(ev1);
+    if (!ok) return false;
+  }
+  lbvhEmitKernel<<<grdN, blk>>>(n, S.childL, S.childR, S.first, S.last, S.folded, S.triBox, S.valsOut, S.nodeBox, nodes, C);
   const uint MAX_LEVELS = 64u;
   if (wantWide && nodes4 && cap4) {
     const uint2 root = make_uint2(0u, 0u);
@@ -452,9 +605,9 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
     }
   }
   if (refit.levelIds) {
-    lbvhLevelHistKernel<<<grdN, blk>>>(n, S.first, S.last, S.height, C);
+    lbvhLevelHistKernel<<<grdN, blk>>>(n, S.folded, S.height, C);
     lbvhLevelScanKernel<<<1, LBVH_MAX_LEVELS>>>(S.height, C);
-    lbvhLevelScatterKernel<<<grdN, blk>>>(n, S.first, S.last, S.height, C, refit.levelIds);
+    lbvhLevelScatterKernel<<<grdN, blk>>>(n, S.folded, S.height, C, refit.levelIds);
   }
   LCHK(hipGetLastError());
   LbvhCounters res; uint rootDepth = 0, rootHeight = 0; float rootBox[6];
@@ -469,6 +622,7 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   }
   for (int a = 0; a < 6; a++) LCHK(hipMemcpy(&rootBox[a], S.nodeBox + (size_t)a * (n - 1), sizeof(float), hipMemcpyDeviceToHost));
   out.rootRef = 0u; out.numNodes = n - 1u; out.depth = rootDepth;
+  for (int k = 0; k < 64; k++) { out.treeletsExamined += res.treelet[2 * k]; out.treeletsRewritten += res.treelet[2 * k + 1]; }
   float lo[3] = { rootBox[0], rootBox[1], rootBox[2] }, hi[3] = { rootBox[3], rootBox[4], rootBox[5] };
   const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
   const float a0 = dx * dy + dy * dz + dz * dx;

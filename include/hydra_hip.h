@@ -543,6 +543,11 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *   "device_refit"  0 (default): an update of a DEVICE-built single-level tree is answered by another device build; 1: the device build leaves
  *               its level lists behind and such an update refits the tree (instance matrices and vertex positions; "refit", 0 still rebuilds).
  *               Read when the tree is built and again when the update is committed.
+ *   "device_build_quality"  p: 0 (default) = a device build leaves the plain linear BVH; 1 .. 4 = it runs p passes of treelet restructuring over the
+ *               hierarchy before the tree is emitted (every inner node with up to 7 descendants as leaves: the optimal topology over them by the
+ *               surface-area cost, rewritten when strictly cheaper). Applies to every device build - "device_build" 1, BUILD_LOW | BUILD_MEDIUM, the
+ *               build after a rejected refit, the rebuild of a device-built tree - and never to the host's. Anything else is an argument error.
+ *               Setting it uncommits the scene, as "device_build" does. Hits do not depend on it; hpt_get_build_info says what the passes did.
  *   "refit_max_sah_pct"  p: 0 (default) = never; p >= 100: a refit whose surface-area estimate (hpt_get_refit_info) exceeds p / 100 times the
  *               estimate at build time is followed, in the same hpt_commit_scene, by a build (on the device for a device-built tree, on the host
  *               for a host-built one). 1 .. 99 is an argument error.
@@ -602,6 +607,11 @@ int  hpt_get_commit_time(hpt_ctx* ctx, float out[4]);
  * out[2] = number of levels a refit launches (0: the tree cannot be refitted), out[3] = 1 when the last hpt_commit_scene attempted a refit and
  * "refit_max_sah_pct" rejected it. Schedule and kernel choices keep following out[0]. */
 int  hpt_get_refit_info(hpt_ctx* ctx, float out[4]);
+/* The treelet passes of the last hpt_commit_scene when it was a device build (hpt_set_option("device_build_quality", p)): out[0] = passes run
+ * (fewer than p when the tree has a single node, or is deeper than the level lists reach and goes back to the host's builder), out[1] = treelets of
+ * three leaves or more examined over all passes, out[2] = treelets rewritten, out[3] = device milliseconds spent in the passes (contained in
+ * hpt_get_commit_time's out[2]). All zeros after a host build, a refit, or with the option at 0. */
+int  hpt_get_build_info(hpt_ctx* ctx, float out[4]);
 /* Host copy of the committed single-level tree as it lies in device memory (tests, checkpoints; the counterpart of hpt_cam_read_state):
  * what = 0: the BvhNode array (64-byte records: q[12] = child 0 {lo.x hi.x lo.y hi.y lo.z hi.z}, child 1 {same}; ref0, ref1, two pad words),
  * what = 1: the BvhTri array (48-byte records: v0[3], primId, e1[3], instId, e2[3], pad). A reference with bit 31 set is a leaf
