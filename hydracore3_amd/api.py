@@ -94,6 +94,8 @@ ABI = {
     "hpt_get_refit_info": (_i, [_vp, C.POINTER(_f)]),
     "hpt_get_build_info": (_i, [_vp, C.POINTER(_f)]),
     "hpt_read_accel": (_i, [_vp, _i, _vp, _u64, C.POINTER(_u64), C.POINTER(_u32)]),
+    "hpt_get_two_level_info": (_i, [_vp, C.POINTER(_f)]),
+    "hpt_read_accel_two_level": (_i, [_vp, _i, _vp, _u64, C.POINTER(_u64), C.POINTER(_u32)]),
     "hpt_last_kernel_ms": (_i, [_vp, C.POINTER(_f)]),
     "hpt_eval_gbuffer": (_i, [_vp, _u32, _vp]),
     "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
@@ -137,6 +139,9 @@ assert GBUFFER_DTYPE.itemsize == 60
 BVH_NODE_DTYPE = np.dtype([("q", np.float32, (12,)), ("ref0", np.uint32), ("ref1", np.uint32), ("pad0", np.uint32), ("pad1", np.uint32)])
 BVH_TRI_DTYPE = np.dtype([("v0", np.float32, (3,)), ("primId", np.uint32), ("e1", np.float32, (3,)), ("instId", np.uint32), ("e2", np.float32, (3,)), ("pad1", np.uint32)])
 assert BVH_NODE_DTYPE.itemsize == 64 and BVH_TRI_DTYPE.itemsize == 48
+# the instance records of the two-level layout as hpt_read_accel_two_level returns them (hpt_types.h: BvhInst)
+BVH_INST_DTYPE = np.dtype([("rows", np.float32, (3, 4)), ("root", np.uint32), ("geomId", np.uint32), ("moving", np.uint32), ("pad1", np.uint32)])
+assert BVH_INST_DTYPE.itemsize == 64
 
 
 
@@ -758,6 +763,28 @@ class HipIntegrator:
                 self._chk(self.L.hpt_read_accel(self.h, what, a.ctypes.data, a.nbytes, C.byref(nbytes), C.byref(root)))
             out.append(a)
         return out[0], out[1], int(root.value)
+
+    def two_level_info(self):
+        """hpt_get_two_level_info: what the last CommitScene did when it built the two-level layout on the device
+        (set_option("device_build_two_level", 1)); every field is zero / False after any other kind of commit."""
+        out = (C.c_float * 8)()
+        self._chk(self.L.hpt_get_two_level_info(self.h, out))
+        return {"device_built": int(out[0]) == 1, "blas_built": int(out[1]), "blas_kept": int(out[2]), "tlas_only": int(out[3]) == 1,
+                "tlas_depth": int(out[4]), "blas_depth": int(out[5]), "blas_ms": out[6], "tlas_ms": out[7]}
+
+    def read_accel_two_level(self):
+        """hpt_read_accel_two_level: the committed two-level tree (either builder's) as it lies in device memory:
+        (nodes [BVH_NODE_DTYPE], tris [BVH_TRI_DTYPE], insts [BVH_INST_DTYPE], TLAS rootRef)."""
+        out = []
+        root = C.c_uint32(0)
+        for what, dt in ((0, BVH_NODE_DTYPE), (1, BVH_TRI_DTYPE), (2, BVH_INST_DTYPE)):
+            nbytes = C.c_uint64(0)
+            self._chk(self.L.hpt_read_accel_two_level(self.h, what, None, 0, C.byref(nbytes), C.byref(root)))
+            a = np.zeros(nbytes.value // dt.itemsize, dt)
+            if a.size:
+                self._chk(self.L.hpt_read_accel_two_level(self.h, what, a.ctypes.data, a.nbytes, C.byref(nbytes), C.byref(root)))
+            out.append(a)
+        return out[0], out[1], out[2], int(root.value)
 
     def UpdateGeom_Triangles3f(self, geom_id, vpos, indices):
         """ISceneObject::UpdateGeom_Triangles3f (CrossRT.h:85-86): new positions (float32 [n, 3] or [n, 4]) and indices for a mesh; takes effect at the

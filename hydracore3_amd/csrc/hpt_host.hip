@@ -215,6 +215,11 @@ struct hpt_ctx
   // CommitScene on the device (hpt_lbvh.hip): -1 = by CommitScene's options (BUILD_LOW / BUILD_MEDIUM without BUILD_HIGH), 0 = never, 1 = whenever the single-level layout is built
   int deviceBuildQuality = 0; float buildInfo[4] = { 0.0f, 0.0f, 0.0f, 0.0f };   // hpt_set_option("device_build_quality", passes); hpt_get_build_info: the last device build's treelet passes
   int deviceBuild = -1; void* lbvh = nullptr; unsigned long long geomVersion = 1, lbvhGeomVersion = 0; std::vector<size_t> lbvhPosOff, lbvhIdxOff;
+  // the two-level layout built on the device (hpt_set_option("device_build_two_level", 1); hpt_lbvh.hip section 9): every mesh's slot in dNodes / dTris
+  // and what the last batch left for it (host mirror); tlOnDevice: such a tree is committed; tlUpdatable: and nothing but instance matrices / vertex positions changed since - it is updated in place
+  int deviceBuildTwoLevel = 0; bool tlOnDevice = false, tlUpdatable = false; std::vector<LbvhMeshSlot> tlSlots; std::vector<LbvhMeshOut> tlMeshOut;
+  float tlInfo[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };          // hpt_get_two_level_info
+  size_t tlNodes = 0, tlTris = 0;                        // entries of dNodes / dTris that belong to the committed two-level tree (hpt_read_accel_two_level)
   uint lastSchedule = 1, lastWfIters = 0;
   uint lastWide = 0, lastShadeRecords = 0, lastDeep = 0;          // what the last launch walked: 4-wide compressed tree, 64-byte shading records, HBM part of the stacks
   bool stackWitness = false; size_t witnessWords = 0;             // "dbg_stack_witness": dStackOvf is filled with STACK_SENTINEL before a launch; words the last launch's fill covered
@@ -404,7 +409,7 @@ catch (...) { return hptGuard(c, "hpt_device_memset"); }
 extern "C" int hpt_clear_geom(hpt_ctx* c)
 try {
   if (!c) return HPT_ERR_ARG;
-  c->geoms.clear(); c->insts.clear(); c->accelCommitted = false; c->flatRefittable = false; c->geomVersion++;
+  c->geoms.clear(); c->insts.clear(); c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; c->geomVersion++;
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_clear_geom"); }
@@ -429,7 +434,7 @@ try {
   Geom g;
   if (fill_geom(c, g, vpos, nVert, idx, nIdx, stride) != HPT_OK) return 0xFFFFFFFFu;
   c->geoms.push_back(std::move(g));
-  c->accelCommitted = false; c->flatRefittable = false;
+  c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false;
   return (uint32_t)(c->geoms.size() - 1);
 }
 catch (...) { (void)hptGuard(c, "hpt_add_geom_triangles3f"); return 0xFFFFFFFFu; }
@@ -442,13 +447,13 @@ try {
   if (nIdx > g.idx.size() || nVert * 3 > g.pos.size()) return c->fail(HPT_ERR_ARG, "UpdateGeom_Triangles3f: growing a geometry is not supported");
   c->accelCommitted = false;
   // the committed single-level tree survives a change of vertex POSITIONS (same triangles): its boxes are refitted on the device
-  if ((nIdx / 3) * 3 != g.idx.size() || std::memcmp(idx, g.idx.data(), g.idx.size() * sizeof(uint32_t)) != 0) c->flatRefittable = false;
+  if ((nIdx / 3) * 3 != g.idx.size() || std::memcmp(idx, g.idx.data(), g.idx.size() * sizeof(uint32_t)) != 0) c->flatRefittable = c->tlUpdatable = false;
   else c->dirtyGeoms.push_back(geomId);
   return fill_geom(c, g, vpos, nVert, idx, nIdx, stride);
 }
 catch (...) { return hptGuard(c, "hpt_update_geom_triangles3f"); }
 
-extern "C" int hpt_clear_scene(hpt_ctx* c) try { if (!c) return HPT_ERR_ARG; c->insts.clear(); c->accelCommitted = false; c->flatRefittable = false; return HPT_OK; }
+extern "C" int hpt_clear_scene(hpt_ctx* c) try { if (!c) return HPT_ERR_ARG; c->insts.clear(); c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; return HPT_OK; }
 catch (...) { return hptGuard(c, "hpt_clear_scene"); }
 
 extern "C" uint32_t hpt_add_instance(hpt_ctx* c, uint32_t geomId, const float m[16])
@@ -456,7 +461,7 @@ try {
   if (!c || !m || geomId >= c->geoms.size()) return 0xFFFFFFFFu;
   Inst in; in.geomId = geomId; std::memcpy(in.m, m, 64);
   c->insts.push_back(in);
-  c->accelCommitted = false; c->flatRefittable = false;
+  c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false;
   return (uint32_t)(c->insts.size() - 1);
 }
 catch (...) { (void)hptGuard(c, "hpt_add_instance"); return 0xFFFFFFFFu; }
@@ -468,7 +473,7 @@ try {
   if (matrixNumber != 2) { c->fail(HPT_ERR_UNSUPPORTED, "AddInstanceMotion: two key matrices are supported (what LoadSceneInstances passes)"); return 0xFFFFFFFFu; }
   Inst in; in.geomId = geomId; std::memcpy(in.m, matrices, 64); std::memcpy(in.m1, matrices + 16, 64); in.motion = true;
   c->insts.push_back(in);
-  c->accelCommitted = false; c->flatRefittable = false;
+  c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false;
   return (uint32_t)(c->insts.size() - 1);
 }
 catch (...) { (void)hptGuard(c, "hpt_add_instance_motion"); return 0xFFFFFFFFu; }
@@ -556,6 +561,19 @@ template <class F> static void parallelRanges(size_t n, int threads, F fn)
   for (std::thread& t : pool) t.join();
 }
 
+// Which layout a scene resolves to (hpt_set_accel_layout; the measurements behind the automatic choice stand in hpt_commit_scene): the single-level
+// tree, or the two-level one - which tiny static scenes walk as a triangle sweep. A forced sweep with a moving instance is an error the caller reports.
+static bool resolvesFlat(const hpt_ctx* c, size_t instTris, bool anyMotion)
+{
+  const bool autoFlat = !anyMotion && (instTris >= FLAT_AUTO_TRIS || c->insts.size() >= MANY_INSTANCES);
+  return instTris <= FLAT_TRI_BUDGET && (c->accelLayout == 2 || (c->accelLayout == 0 && autoFlat));
+}
+static bool resolvesSweep(const hpt_ctx* c, size_t instTris, bool anyMotion)
+{
+  const size_t ni = c->insts.size();
+  return !anyMotion && ni >= 1 && (c->accelLayout == 3 || (c->accelLayout == 0 && instTris <= SWEEP_MAX_TRIS && ni <= SWEEP_MAX_INSTS));
+}
+
 // ---- CommitScene on the device: hpt_lbvh.hip builds the single-level BVH2, its triangle records and the 4-wide compressed tree -------------
 static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
 {
@@ -629,7 +647,111 @@ static int commit_flat_on_device(hpt_ctx* c, size_t instTris, double tBuild0)
   return HPT_OK;
 }
 
-static const int HPT_REFIT_REJECTED = -1;                     // refit_flat: the refitted tree's estimate is over "refit_max_sah_pct"; hpt_commit_scene builds instead
+// ---- CommitScene on the device, two-level layout (hpt_set_option("device_build_two_level", 1)): one BLAS per mesh in a fixed slot of dNodes / dTris,
+// all dirty ones built in one batch (hpt_lbvh.hip section 9), the TLAS over the live instances at the front of dNodes. update: the committed tree is
+// such a tree and only instance matrices / vertex positions of the meshes in `moved` changed since - those BLAS are built again in their slots
+// (none: nothing but the TLAS kernels runs) and the rest of both arrays stays byte for byte. Returns HPT_ERR_STATE when the host's builder must
+// take the whole commit (deeper than the traversal stack, past the reference widths).
+static int commit_two_level_on_device(hpt_ctx* c, size_t instTris, bool update, const std::vector<uint>& moved, double tBuild0)
+{
+  if (!c->lbvh) c->lbvh = lbvhCreate();
+  std::string err;
+  const size_t ng = c->geoms.size(), ni = c->insts.size();
+  update = update && c->tlSlots.size() == ng && c->tlMeshOut.size() == ng && c->lbvhPosOff.size() == ng;
+  std::vector<uint> dirty;
+  if (!update) {
+    c->tlSlots.assign(ng, LbvhMeshSlot());
+    size_t nodeBase = std::max<size_t>(ni, 1), triBase = 0;   // the TLAS' nodes lie in front: ni - 1 at the most
+    for (size_t g = 0; g < ng; g++) {
+      const size_t nt = c->geoms[g].idx.size() / 3;
+      if (nodeBase >= (size_t(1) << 31) || triBase >= (size_t(1) << 28)) return HPT_ERR_STATE;
+      c->tlSlots[g].nodeBase = (uint)nodeBase; c->tlSlots[g].triBase = (uint)triBase; c->tlSlots[g].nt = (uint)nt;
+      nodeBase += nt > 1 ? nt - 1 : 0; triBase += nt;
+      if (nt) dirty.push_back((uint)g);
+    }
+    if (nodeBase >= (size_t(1) << 31) || triBase >= (size_t(1) << 28)) return HPT_ERR_STATE;
+    if (c->lbvhGeomVersion != c->geomVersion) {               // the meshes' positions and indices: uploaded once, kept until a mesh changes
+      std::vector<const float*> pos; std::vector<size_t> posN; std::vector<const uint*> idx; std::vector<size_t> idxN;
+      for (const Geom& g : c->geoms) { pos.push_back(g.pos.data()); posN.push_back(g.pos.size()); idx.push_back(g.idx.data()); idxN.push_back(g.idx.size()); }
+      if (!lbvhUploadGeometry(c->lbvh, pos, posN, idx, idxN, c->lbvhPosOff, c->lbvhIdxOff, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build, two-level): " + err);
+      c->lbvhGeomVersion = c->geomVersion;
+    }
+    for (size_t g = 0; g < ng; g++) {
+      if ((c->lbvhPosOff[g] >> 32) != 0 || (c->lbvhIdxOff[g] >> 32) != 0) return HPT_ERR_STATE;
+      c->tlSlots[g].posOff = (uint)c->lbvhPosOff[g]; c->tlSlots[g].idxOff = (uint)c->lbvhIdxOff[g];
+    }
+    c->tlMeshOut.assign(ng, LbvhMeshOut());
+    for (LbvhMeshOut& o : c->tlMeshOut) lbvhMeshOutReset(o);
+    c->tlNodes = nodeBase; c->tlTris = triBase;
+    HIPCHK(c, c->dNodes.alloc(nodeBase));
+    HIPCHK(c, c->dTris.alloc(std::max<size_t>(triBase, 1)));
+    // (unused entries - the TLAS region past its nodes, the slots of folded subtrees - read back as zeros, not as whatever the allocation held)
+    HIPCHK(c, hipMemsetAsync(c->dNodes.p, 0, nodeBase * sizeof(BvhNode), nullptr));
+    HIPCHK(c, hipMemsetAsync(c->dTris.p, 0, std::max<size_t>(triBase, 1) * sizeof(BvhTri), nullptr));
+  } else {
+    std::vector<char> seen(ng, 0);
+    std::vector<const float*> pos; std::vector<size_t> posN;
+    for (const Geom& g : c->geoms) { pos.push_back(g.pos.data()); posN.push_back(g.pos.size()); }
+    for (uint g : moved) if (g < ng && !seen[g] && c->tlSlots[g].nt != 0u) { seen[g] = 1; dirty.push_back(g); lbvhMeshOutReset(c->tlMeshOut[g]); }
+    if (!dirty.empty() && !lbvhCopyPositions(c->lbvh, dirty, pos, posN, c->lbvhPosOff, err)) return c->fail(HPT_ERR_HIP, "CommitScene (device build, two-level): " + err);
+    c->lbvhGeomVersion = c->geomVersion;                      // (an updatable tree: nothing but these positions changed since the geometry was uploaded)
+  }
+  const double tDev0 = now_ms();
+  float blasMs = 0.0f, tlasMs = 0.0f;
+  if (!dirty.empty() && !lbvhBuildBlasBatch(c->lbvh, c->tlSlots.data(), (uint)ng, dirty.data(), (uint)dirty.size(), c->tlMeshOut.data(), c->dNodes.p, c->dTris.p, blasMs, err))
+    return c->fail(HPT_ERR_HIP, "CommitScene (device build, two-level): " + err);
+  const double tDev1 = now_ms();
+  uint maxBlasDepth = 0;
+  for (const LbvhMeshOut& o : c->tlMeshOut) maxBlasDepth = std::max(maxBlasDepth, o.depth);
+  if (maxBlasDepth + 2u > MAX_STACK) return HPT_ERR_STATE;
+  // instance records: the inverse rows decide hits and stay the host's (double, rounded once); the root is the mesh's patched BLAS root
+  std::vector<BvhInst> dinst(std::max<size_t>(ni, 1));
+  std::vector<uint> instGeom(std::max<size_t>(ni, 1), 0u);
+  std::vector<float> mo(24 * std::max<size_t>(ni, 1), 0.0f);
+  uint nLive = 0, firstLive = 0; bool anyMotion = false;
+  for (size_t i = 0; i < ni; i++) {
+    const Inst& in = c->insts[i];
+    inverse_rows(in.m, dinst[i].row0, dinst[i].row1, dinst[i].row2);
+    dinst[i].root = c->tlMeshOut[in.geomId].root; dinst[i].geomId = in.geomId; dinst[i].pad0 = in.motion ? 1u : 0u; dinst[i].pad1 = 0;
+    instGeom[i] = in.geomId; anyMotion = anyMotion || in.motion;
+    if (dinst[i].root != REF_NONE) { if (nLive == 0u) firstLive = (uint)i; nLive++; }
+    for (int key = 0; key < 2; key++) {
+      const float* m = (key && in.motion) ? in.m1 : in.m;
+      float* o = &mo[24 * i + 12 * (size_t)key];
+      for (int r = 0; r < 3; r++) { o[4 * r + 0] = m[r]; o[4 * r + 1] = m[4 + r]; o[4 * r + 2] = m[8 + r]; o[4 * r + 3] = m[12 + r]; }
+    }
+  }
+  HIPCHK(c, c->dInstMotion.upload(mo.data(), mo.size()));
+  HIPCHK(c, c->dInsts.upload(dinst.data(), dinst.size()));
+  const double tDev2 = now_ms();
+  LbvhTlasResult r;
+  if (!lbvhBuildTlas(c->lbvh, instGeom.data(), (uint)ni, nLive, firstLive, c->dInstMotion.p, c->tlMeshOut.data(), (uint)ng, c->dNodes.p, r, tlasMs, err))
+    return c->fail(HPT_ERR_HIP, "CommitScene (device build, two-level): " + err);
+  const double tDev3 = now_ms();
+  if (r.depth + 1u + maxBlasDepth + 1u > MAX_STACK) return HPT_ERR_STATE;
+  c->instTris = instTris; c->anyMotion = anyMotion;
+  c->sahVisits = r.sahVisits;
+  c->S.instMotion = c->dInstMotion.p;
+  c->S.nodes = c->dNodes.p; c->S.tris = c->dTris.p; c->S.insts = c->dInsts.p;
+  c->S.rootRef = r.rootRef; c->S.numInsts = (uint)ni; c->S.flatMode = 0;
+  c->S.sweep = 0; c->S.sweepInsts = nullptr; c->S.sweepTris = nullptr; c->S.sweepBoxes = nullptr; c->S.sweepPlanes = nullptr; c->S.sweepCull = 0u; c->S.sweepPairBoxes = nullptr; c->S.sweepLanes = 0u;
+  c->S.nodeMin = c->nodeMinOverride >= 0 ? (uint)c->nodeMinOverride : (c->sahVisits >= HEAVY_SAH_VISITS ? 16u : 0u);
+  c->nodes4Count = 0; c->stackNeeded4 = 0; c->S.nodes4 = nullptr; c->S.root4 = REF_NONE; c->S.statsWide = 0; c->S.megaWide = 0; c->S.nodeMin4 = 0;
+  c->flatOnDevice = false; c->flatNodes = 0; c->levelOffsets.assign(1, 0u); c->flatTris.clear();
+  c->tlOnDevice = true; c->tlUpdatable = true; c->flatRefittable = false;   // the next commit may update this tree in place
+  c->stackNeeded = r.depth + 1u + maxBlasDepth + 1u;
+  const uint kept = (uint)std::count_if(c->tlSlots.begin(), c->tlSlots.end(), [](const LbvhMeshSlot& s) { return s.nt != 0u; }) - (uint)dirty.size();
+  c->tlInfo[0] = 1.0f; c->tlInfo[1] = (float)dirty.size(); c->tlInfo[2] = (float)kept; c->tlInfo[3] = (update && dirty.empty()) ? 1.0f : 0.0f;
+  c->tlInfo[4] = (float)r.depth; c->tlInfo[5] = (float)maxBlasDepth; c->tlInfo[6] = blasMs; c->tlInfo[7] = tlasMs;
+  if (std::getenv("HPT_DEBUG_ACCEL")) std::fprintf(stderr, "[hydra_hip] device-built two-level BVH: %zu instances (%u live), %zu BLAS built, %u kept, TLAS depth %u, deepest BLAS %u, stack %u, sah visits %.2f; BLAS %.3f ms, TLAS %.3f ms\n",
+                                                  ni, nLive, dirty.size(), kept, r.depth, maxBlasDepth, c->stackNeeded, c->sahVisits, blasMs, tlasMs);
+  // host preparation + uploads, -, device build (both stages with their read-backs), "built on the device"
+  c->tCommit[0] = float((tDev0 - tBuild0) + (tDev2 - tDev1)); c->tCommit[1] = 0.0f; c->tCommit[2] = float((tDev1 - tDev0) + (tDev3 - tDev2)); c->tCommit[3] = 2.0f;
+  c->accelCommitted = true; c->shadeTrisDirty = true;
+  return HPT_OK;
+}
+
+static const int HPT_REFIT_REJECTED = -1;                    // refit_flat: the refitted tree's estimate is over "refit_max_sah_pct"; hpt_commit_scene builds instead
 
 // One body for both trees. They differ in where the moved vertices' records are rewritten: a host-built tree has a host copy of its records
 // (flatTris) that is patched and uploaded whole, a device-built tree has none - its meshes' positions are copied to the builder's device copy
@@ -700,6 +822,10 @@ try {
   (void)hipSetDevice(c->device);
   c->refitRejected = false;
   for (float& v : c->buildInfo) v = 0.0f;                     // (a device build that is kept fills it in)
+  for (float& v : c->tlInfo) v = 0.0f;
+  const bool tlUpdate = c->tlOnDevice && c->tlUpdatable && c->refitEnabled;   // a device-built two-level tree that only saw UpdateInstance / same-index UpdateGeom
+  c->tlOnDevice = false; c->tlUpdatable = false;
+  const std::vector<uint> movedGeoms(c->dirtyGeoms);
   int onDevice = -1;                                         // 1 / 0: a rejected refit is followed by a build of the kind the tree came from
   if (c->flatRefittable && c->refitEnabled && c->S.flatMode == 1u && (!c->flatOnDevice || c->deviceRefit)) {
     const int rc = refit_flat(c);
@@ -719,6 +845,12 @@ try {
     if (wantFlat && nTris > 0 && (onDevice == 1 || (onDevice < 0 && (c->deviceBuild == 1 || (c->deviceBuild < 0 && fast))))) {
       const int rc = commit_flat_on_device(c, nTris, tBuild0);
       if (rc != HPT_ERR_STATE) return rc;                    // (HPT_ERR_STATE: the tree came out deeper than the traversal stack - the host's depth-capped build takes over)
+    }
+    // "device_build_two_level": the same request on a scene that resolves to the two-level layout (the rules further down) and is no triangle sweep
+    // (a forced sweep never is: with a moving instance it is the host path's error)
+    if (c->deviceBuildTwoLevel == 1 && c->accelLayout != 3 && !resolvesFlat(c, nTris, moving) && !resolvesSweep(c, nTris, moving) && nTris > 0 && onDevice < 0 && (c->deviceBuild == 1 || (c->deviceBuild < 0 && fast))) {
+      const int rc = commit_two_level_on_device(c, nTris, tlUpdate, movedGeoms, tBuild0);
+      if (rc != HPT_ERR_STATE) return rc;                    // (HPT_ERR_STATE: deeper than the traversal stack, or past the reference widths - the whole commit goes to the host's builder)
     }
   }
   // ---- bottom level: one BVH2 per mesh over object-space triangles ----
@@ -774,8 +906,7 @@ try {
   // ten instances: two-level 1797, single-level 1065 Mpaths/s - profiles/ab_layout_full.sh).
   c->anyMotion = false;
   for (const Inst& in : c->insts) c->anyMotion = c->anyMotion || in.motion;
-  const bool autoFlat = !c->anyMotion && (instTris >= FLAT_AUTO_TRIS || c->insts.size() >= MANY_INSTANCES);
-  const bool flat = instTris <= FLAT_TRI_BUDGET && (c->accelLayout == 2 || (c->accelLayout == 0 && autoFlat));
+  const bool flat = resolvesFlat(c, instTris, c->anyMotion);
   {                                                          // object->world rows (3x4) at both keys for the moving instances (both layouts read them)
     const size_t nim = c->insts.size();
     std::vector<float> mo(24 * std::max<size_t>(nim, 1), 0.0f);
@@ -951,7 +1082,7 @@ try {
     dinst[i].root = geomRoot[c->insts[i].geomId]; dinst[i].geomId = c->insts[i].geomId; dinst[i].pad0 = c->insts[i].motion ? 1u : 0u; dinst[i].pad1 = 0;
   }
   // the triangle sweep keeps its own copy of the instance records: {rows, first triangle record, geomId, 0, number of record pairs}
-  const bool sweep = !c->anyMotion && ni >= 1 && (c->accelLayout == 3 || (c->accelLayout == 0 && instTris <= SWEEP_MAX_TRIS && ni <= SWEEP_MAX_INSTS));
+  const bool sweep = resolvesSweep(c, instTris, c->anyMotion);
   if (c->accelLayout == 3 && c->anyMotion) return c->fail(HPT_ERR_UNSUPPORTED, "CommitScene: the triangle sweep does not hold moving instances (two-level or single-level layout)");
   if (sweep) {
     std::vector<uint> geomTriBase(c->geoms.size(), 0u);
@@ -997,6 +1128,7 @@ try {
   c->S.sweep = sweep ? 1u : 0u; c->S.sweepInsts = sweep ? c->dSweepInsts.p : nullptr; c->S.sweepTris = sweep ? c->dSweepTris.p : nullptr; c->S.sweepBoxes = sweep ? (const float4*)c->dSweepBoxes.p : nullptr;
   c->S.sweepPlanes = sweep ? (const float4*)c->dSweepPlanes.p : nullptr; c->S.sweepCull = sweep ? c->sweepCull : 0u;
   c->S.sweepPairBoxes = sweep ? (const float4*)c->dSweepPairBoxes.p : nullptr; c->S.sweepLanes = sweep ? c->sweepLanes : 0u;
+  c->tlNodes = nodes.size(); c->tlTris = tris.size();
   if (nodes.empty()) nodes.push_back(BvhNode());           // keep the pointers valid
   if (tris.empty()) tris.push_back(BvhTri());
   HIPCHK(c, c->dNodes.upload(nodes.data(), nodes.size()));
@@ -1005,7 +1137,7 @@ try {
   c->S.nodes = c->dNodes.p; c->S.tris = c->dTris.p; c->S.insts = c->dInsts.p;
   c->S.rootRef = rootRef; c->S.numInsts = (uint)ni; c->S.flatMode = 0;
   c->nodes4Count = 0; c->stackNeeded4 = 0; c->S.nodes4 = nullptr; c->S.root4 = REF_NONE; c->S.statsWide = 0; c->S.megaWide = 0; c->S.nodeMin4 = 0;
-  c->flatRefittable = false; c->flatOnDevice = false; c->flatNodes = 0; c->levelOffsets.assign(1, 0u);
+  c->flatRefittable = c->tlUpdatable = false; c->flatOnDevice = false; c->flatNodes = 0; c->levelOffsets.assign(1, 0u);
   c->tCommit[0] = float(now_ms() - tBuild0); c->tCommit[1] = 0.0f; c->tCommit[2] = 0.0f; c->tCommit[3] = 0.0f;
   c->stackNeeded = tlas.depth + 1u + maxBlasDepth + 1u;
   if (std::getenv("HPT_DEBUG_ACCEL")) std::fprintf(stderr, "[hydra_hip] two-level BVH: %zu instances, TLAS depth %u, deepest BLAS %u, stack %u (LDS part %d)\n", ni, tlas.depth, maxBlasDepth, c->stackNeeded, LDS_STACK);
@@ -3401,7 +3533,7 @@ try {
   if (!c || !name || value < 0) return HPT_ERR_ARG;
   const std::string k(name);
   if (k == "wf_grace") c->wfGrace = (uint)value;                                      // trips after the queue ran dry before a trace wave suspends its rays (0: never)
-  else if (k == "node_min") { c->nodeMinOverride = value & 63; c->accelCommitted = false; c->flatRefittable = false; }
+  else if (k == "node_min") { c->nodeMinOverride = value & 63; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "refit") c->refitEnabled = value != 0;                                  // 0: UpdateInstance / UpdateGeom + CommitScene always rebuild the tree on the host   // voted exit of the inner-node loop; takes effect at the next CommitScene
   else if (k == "device_refit") { if (value > 1) return c->fail(HPT_ERR_ARG, "device_refit: 0 an update of a device-built tree is another device build, 1 it is a refit"); c->deviceRefit = value != 0; }
   else if (k == "refit_max_sah_pct") { if (value != 0 && value < 100) return c->fail(HPT_ERR_ARG, "refit_max_sah_pct: 0 never, else >= 100 (per cent of the estimate at build time)"); c->refitMaxSahPct = value; }
@@ -3418,8 +3550,9 @@ try {
   else if (k == "bw_refill_below") { if (value < 1 || value > 64) return c->fail(HPT_ERR_ARG, "bw_refill_below: 1..64"); c->bwRefillBelow = (uint)value; }
   else if (k == "bw_wide") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "bw_wide: -1 automatic, 0, 1"); c->bwWide = value; }
   else if (k == "bw_node_min") { if (value < 0 || value > 64) return c->fail(HPT_ERR_ARG, "bw_node_min: 0..64"); c->bwNodeMin = (uint)value; }
-  else if (k == "device_build") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "device_build: -1 by CommitScene's options, 0 never, 1 always"); c->deviceBuild = value; c->accelCommitted = false; c->flatRefittable = false; }
-  else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = false; }
+  else if (k == "device_build") { if (value < -1 || value > 1) return c->fail(HPT_ERR_ARG, "device_build: -1 by CommitScene's options, 0 never, 1 always"); c->deviceBuild = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
+  else if (k == "device_build_two_level") { if (value < 0 || value > 1) return c->fail(HPT_ERR_ARG, "device_build_two_level: 0 two-level scenes are built on the host, 1 on the device when a device build is asked for"); c->deviceBuildTwoLevel = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
+  else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
@@ -3474,6 +3607,30 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_read_accel"); }
+extern "C" int hpt_get_two_level_info(hpt_ctx* c, float out[8])
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  for (int i = 0; i < 8; i++) out[i] = c->tlInfo[i];
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_get_two_level_info"); }
+extern "C" int hpt_read_accel_two_level(hpt_ctx* c, int what, void* dst, uint64_t capacityBytes, uint64_t* outBytes, uint32_t* outRootRef)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (what < 0 || what > 2) return c->fail(HPT_ERR_ARG, "hpt_read_accel_two_level: what = 0 (BvhNode array), 1 (BvhTri array) or 2 (BvhInst array)");
+  if (!c->accelCommitted || c->S.flatMode != 0u) return c->fail(HPT_ERR_STATE, "hpt_read_accel_two_level: no two-level tree is committed");
+  const uint64_t bytes = what == 0 ? (uint64_t)std::min(c->tlNodes, c->dNodes.n) * sizeof(BvhNode) : what == 1 ? (uint64_t)std::min(c->tlTris, c->dTris.n) * sizeof(BvhTri)
+                                   : (uint64_t)std::min(c->insts.size(), c->dInsts.n) * sizeof(BvhInst);
+  if (outBytes) *outBytes = bytes;
+  if (outRootRef) *outRootRef = c->S.rootRef;
+  if (!dst) return HPT_OK;
+  if (capacityBytes < bytes) return c->fail(HPT_ERR_ARG, "hpt_read_accel_two_level: the destination is too small");
+  (void)hipSetDevice(c->device);
+  HIPCHK(c, hipDeviceSynchronize());
+  if (bytes) HIPCHK(c, hipMemcpy(dst, what == 0 ? (const void*)c->dNodes.p : what == 1 ? (const void*)c->dTris.p : (const void*)c->dInsts.p, bytes, hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_read_accel_two_level"); }
 extern "C" int hpt_get_schedule(hpt_ctx* c, int* lastSchedule, uint32_t* lastIterations)
 try {
   if (!c) return HPT_ERR_ARG;
@@ -3507,7 +3664,7 @@ catch (...) { return hptGuard(c, "hpt_get_stack_witness"); }
 extern "C" int hpt_set_accel_layout(hpt_ctx* c, int layout)
 try {
   if (!c || layout < 0 || layout > 3) return HPT_ERR_ARG;
-  c->accelLayout = layout; c->accelCommitted = false; c->flatRefittable = false;
+  c->accelLayout = layout; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false;
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_set_accel_layout"); }

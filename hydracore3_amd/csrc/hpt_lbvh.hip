@@ -44,9 +44,14 @@ struct Scratch
   unsigned char* instDirty = nullptr; size_t instDirtyCap = 0;   // lbvhUpdatePositions: 1 = the instance's mesh moved
   uint ni = 0, n = 0;                     // what the last build was over (valsOut, instInfo and the geometry stay as it left them)
   size_t cap = 0;
+  // the two-level layout (section 9): per mesh its slot and the batch's results, per dirty mesh its place in the batch, per instance its mesh, the TLAS stage's result words
+  LbvhMeshSlot* meshSlot = nullptr; LbvhMeshOut* meshOut = nullptr; size_t meshCap = 0;
+  uint2* batch = nullptr; size_t batchCap = 0;
+  uint* instGeom = nullptr; size_t instGeomCap = 0;
+  void* tlasResult = nullptr;
   void freeAll()
   {
-    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, height, folded, passIds, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo, instDirty };
+    void* ps[] = { triBox, keysIn, keysOut, valsIn, valsOut, sortTemp, childL, childR, parent, leafParent, first, last, flags, depth, height, folded, passIds, nodeBox, frontA, frontB, counters, geomPos, geomIdx, instMat, instInfo, instDirty, meshSlot, meshOut, batch, instGeom, tlasResult };
     for (void* p : ps) if (p) (void)hipFree(p);
     *this = Scratch();
   }
@@ -59,9 +64,6 @@ struct LbvhCounters
   uint levelCount[LBVH_MAX_LEVELS], levelFill[LBVH_MAX_LEVELS];       // emitted nodes per height; where the next node of that height goes in the level lists
   uint treelet[2 * 64];                                               // treelet passes: {examined, rewritten}, spread over 64 slots to keep the atomics apart
 };
-
-HPT_HD uint floatKey(float f) { const uint b = hptFloatToBits(f); return (b & 0x80000000u) ? ~b : (b | 0x80000000u); }       // monotonic float -> uint
-HPT_HD float keyFloat(uint k) { return hptBitsToFloat((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
 
 __device__ inline void padBox(float lo[3], float hi[3])      // Aabb::pad (bvh_build.h): the same formula as the host build's
 {
@@ -116,24 +118,29 @@ __device__ inline unsigned long long expand21(unsigned long long v)   // bit k o
   v = (v | (v << 2))  & 0x1249249249249249ull;
   return v;
 }
-__global__ void __launch_bounds__(256) lbvhMortonKernel(const float* __restrict__ triBox, uint n, const LbvhCounters* C, unsigned long long* keys, uint* vals)
+// the 63-bit code of box k's centre within the bounds (loKey, hiKey: floatKey words)
+__device__ inline unsigned long long mortonOfBox(const float* __restrict__ triBox, size_t n, uint k, const uint* loKey, const uint* hiKey)
 {
-  const uint k = blockIdx.x * 256u + threadIdx.x;
-  if (k >= n) return;
   unsigned long long key = 0ull;
   // one scale for the three axes (the scene's longest extent): the Morton cells are cubes whatever the scene's proportions, so a split never
   // halves an axis that is already the shortest of its cell (a 10 x 4 x 10 room normalised per axis splits y as often as x and z)
   float ext = 0.0f;
-  for (int a = 0; a < 3; a++) ext = fmaxf(ext, keyFloat(C->sceneHi[a]) - keyFloat(C->sceneLo[a]));
+  for (int a = 0; a < 3; a++) ext = fmaxf(ext, keyFloat(hiKey[a]) - keyFloat(loKey[a]));
   for (int a = 0; a < 3; a++) {
-    const float lo = keyFloat(C->sceneLo[a]);
+    const float lo = keyFloat(loKey[a]);
     const float c = 0.5f * (triBox[(size_t)a * n + k] + triBox[(size_t)(3 + a) * n + k]);
     float u = ext > 0.0f ? (c - lo) / ext : 0.0f;
     u = fminf(fmaxf(u, 0.0f), 1.0f);
     const unsigned long long q = (unsigned long long)fminf(u * 2097152.0f, 2097151.0f);
     key |= expand21(q) << (2 - a);
   }
-  keys[k] = key; vals[k] = k;
+  return key;
+}
+__global__ void __launch_bounds__(256) lbvhMortonKernel(const float* __restrict__ triBox, uint n, const LbvhCounters* C, unsigned long long* keys, uint* vals)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  keys[k] = mortonOfBox(triBox, n, k, C->sceneLo, C->sceneHi); vals[k] = k;
 }
 
 // ---- 3. hierarchy (Karras 2012) ---------------------------------------------------------------------------------------------------------------------
@@ -171,7 +178,8 @@ __global__ void __launch_bounds__(256) lbvhHierarchyKernel(const unsigned long l
 }
 
 // ---- 4. boxes bottom-up: the second thread to arrive at a node fits it ---------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ triBox, const uint* __restrict__ vals, uint n, const uint* __restrict__ childL, const uint* __restrict__ childR,
+// (boxStride: the row length of triBox - n, but for the TLAS of section 9, whose boxes are indexed by instance)
+__global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ triBox, size_t boxStride, const uint* __restrict__ vals, uint n, const uint* __restrict__ childL, const uint* __restrict__ childR,
                                                      const uint* __restrict__ parent, const uint* __restrict__ leafParent, const unsigned char* __restrict__ folded,
                                                      uint* flags, float* nodeBox, uint* depth, uint* height)
 {
@@ -190,7 +198,7 @@ __global__ void __launch_bounds__(256) lbvhFitKernel(const float* __restrict__ t
       const uint ch = cs[c];
       if (ch & 0x80000000u) {
         const uint t = vals[ch & 0x7FFFFFFFu];
-        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], triBox[(size_t)a * n + t]); hi[a] = fmaxf(hi[a], triBox[(size_t)(3 + a) * n + t]); }
+        for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], triBox[(size_t)a * boxStride + t]); hi[a] = fmaxf(hi[a], triBox[(size_t)(3 + a) * boxStride + t]); }
       } else {
         for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], __hip_atomic_load(&nodeBox[(size_t)a * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); hi[a] = fmaxf(hi[a], __hip_atomic_load(&nodeBox[(size_t)(3 + a) * m + ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)); }
         dep = max(dep, __hip_atomic_load(&depth[ch], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
@@ -468,6 +476,229 @@ __global__ void __launch_bounds__(256) lbvhRegatherTrisKernel(const float* __res
   tris[k] = t;
 }
 
+// ---- 9. the two-level layout: the BLAS of all dirty meshes in one batch, then the TLAS (interface and key layout: hpt_lbvh.h) -------------------------
+// Batch: the dirty meshes' triangles back to back, slot d of the batch = batch[d] {first triangle, mesh}. Sections 3 and 4 run over the whole batch
+// unchanged; tlCutKernel, between them, takes every mesh's subtree off the nodes that span several meshes, so the fit stops at the mesh roots.
+struct TlasResult { uint lo[3], hi[3]; float a0; uint depth; double sahSum, instSum; };   // bounds of the instance boxes' centres' domain (floatKey), TLAS root half-area and depth, the two sums of the estimate
+
+__device__ inline uint findSlot(const uint2* batch, uint D, uint k)
+{
+  uint lo = 0, hi = D;                        // last d with batch[d].x <= k
+  while (hi - lo > 1u) { const uint mid = (lo + hi) >> 1; if (batch[mid].x <= k) lo = mid; else hi = mid; }
+  return lo;
+}
+__device__ inline float halfAreaOf(const float lo[3], const float hi[3])      // Aabb::halfArea (bvh_build.h)
+{
+  const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+  return dx < 0.0f ? 0.0f : dx * dy + dy * dz + dz * dx;
+}
+// object-space triangle boxes; per-mesh bounds by integer-keyed atomics, block-reduced for the mesh the block's first triangle belongs to
+__global__ void __launch_bounds__(256) tlTriBoxKernel(const float* __restrict__ geomPos, const uint* __restrict__ geomIdx, const LbvhMeshSlot* __restrict__ slots, const uint2* __restrict__ batch,
+                                                      uint D, uint n, float* __restrict__ triBox, LbvhMeshOut* mesh)
+{
+  __shared__ uint sLo[3], sHi[3], sGeom;
+  if (threadIdx.x < 3) { sLo[threadIdx.x] = 0xFFFFFFFFu; sHi[threadIdx.x] = 0u; }
+  if (threadIdx.x == 0) sGeom = batch[findSlot(batch, D, min(blockIdx.x * 256u, n - 1u))].y;
+  __syncthreads();
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k < n) {
+    const uint2 b = batch[findSlot(batch, D, k)];
+    const LbvhMeshSlot sl = slots[b.y];
+    const uint t = k - b.x;
+    float lo[3] = { 3.0e38f, 3.0e38f, 3.0e38f }, hi[3] = { -3.0e38f, -3.0e38f, -3.0e38f };
+    for (int v = 0; v < 3; v++) {
+      const float* p = geomPos + sl.posOff + 3 * (size_t)geomIdx[sl.idxOff + 3 * (size_t)t + v];
+      for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], p[a]); hi[a] = fmaxf(hi[a], p[a]); }
+    }
+    const bool inBlockMesh = b.y == sGeom;
+    for (int a = 0; a < 3; a++) {
+      triBox[(size_t)a * n + k] = lo[a]; triBox[(size_t)(3 + a) * n + k] = hi[a];
+      if (inBlockMesh) { atomicMin(&sLo[a], floatKey(lo[a])); atomicMax(&sHi[a], floatKey(hi[a])); }
+      else { atomicMin(&mesh[b.y].lo[a], floatKey(lo[a])); atomicMax(&mesh[b.y].hi[a], floatKey(hi[a])); }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && sLo[threadIdx.x] <= sHi[threadIdx.x]) { atomicMin(&mesh[sGeom].lo[threadIdx.x], sLo[threadIdx.x]); atomicMax(&mesh[sGeom].hi[threadIdx.x], sHi[threadIdx.x]); }
+}
+__global__ void __launch_bounds__(256) tlMortonKernel(const float* __restrict__ triBox, const uint2* __restrict__ batch, uint D, uint n, const LbvhMeshOut* __restrict__ mesh, uint slotBits,
+                                                      unsigned long long* keys, uint* vals)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const uint d = findSlot(batch, D, k);
+  const LbvhMeshOut* m = mesh + batch[d].y;
+  keys[k] = lbvhPackKey(d, slotBits, mortonOfBox(triBox, n, k, m->lo, m->hi)); vals[k] = k;
+}
+// After the hierarchy: a node whose range lies in one mesh and is that mesh's whole range is the mesh's root - it loses its parent; a node that spans
+// several meshes lets go of a leaf child (a mesh of one triangle). Such a node's other children are mesh roots, which let go themselves.
+__global__ void __launch_bounds__(256) tlCutKernel(const unsigned long long* __restrict__ keys, uint n, uint slotBits, const uint2* __restrict__ batch, const LbvhMeshSlot* __restrict__ slots,
+                                                   const uint* __restrict__ childL, const uint* __restrict__ childR, const uint* __restrict__ first, const uint* __restrict__ last,
+                                                   uint* parent, uint* leafParent, LbvhMeshOut* mesh)
+{
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  if (i + 1u >= n) return;
+  const uint a = first[i], b = last[i];
+  const uint sa = lbvhKeySlot(keys[a], slotBits), sb = lbvhKeySlot(keys[b], slotBits);
+  if (sa != sb) {
+    const uint cs[2] = { childL[i], childR[i] };
+    for (int c = 0; c < 2; c++) if (cs[c] & 0x80000000u) leafParent[cs[c] & 0x7FFFFFFFu] = 0xFFFFFFFFu;
+    return;
+  }
+  const uint2 bt = batch[sa];
+  if (a == bt.x && b == bt.x + slots[bt.y].nt - 1u) { parent[i] = 0xFFFFFFFFu; mesh[bt.y].karrasRoot = i; }
+}
+// BvhNode records of every mesh into its slot (lbvhEmitKernel's rules); a mesh's nodes are the Karras nodes of its range but one - the end of the
+// range its root does not sit on - so node i lies at nodeBase + i - (the first node of the range that is one)
+__device__ inline uint tlFirstNode(uint karrasRoot, uint batchFirst) { return karrasRoot == batchFirst ? batchFirst : batchFirst + 1u; }
+__global__ void __launch_bounds__(256) tlEmitBlasKernel(const unsigned long long* __restrict__ keys, uint n, uint slotBits, const uint2* __restrict__ batch, const LbvhMeshSlot* __restrict__ slots,
+                                                        const uint* __restrict__ childL, const uint* __restrict__ childR, const uint* __restrict__ first, const uint* __restrict__ last,
+                                                        const unsigned char* __restrict__ folded, const float* __restrict__ triBox, const uint* __restrict__ vals, const float* __restrict__ nodeBox,
+                                                        BvhNode* nodes, LbvhMeshOut* mesh)
+{
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  double sah = 0.0; uint geom = 0xFFFFFFFFu;
+  if (i + 1u < n && !folded[i]) {
+    const uint sa = lbvhKeySlot(keys[first[i]], slotBits);
+    if (sa == lbvhKeySlot(keys[last[i]], slotBits)) {
+      const uint2 bt = batch[sa];
+      const LbvhMeshSlot sl = slots[bt.y];
+      const uint node0 = tlFirstNode(mesh[bt.y].karrasRoot, bt.x);
+      const size_t m = n - 1;
+      if (i - node0 + 1u < sl.nt) {                                      // (always: the mesh's nodes are node0 .. node0 + nt - 2; nothing is written outside the slot)
+      geom = bt.y;
+      BvhNode nd;
+      const uint cs[2] = { childL[i], childR[i] };
+      for (int c = 0; c < 2; c++) {
+        uint lf, lc; uint ref = childRef(cs[c], first, last, folded, lf, lc);
+        ref = lc ? (REF_LEAF | (lc << 28) | (sl.triBase + (lf - bt.x))) : (sl.nodeBase + (ref - node0));
+        float lo[3], hi[3];
+        if (cs[c] & 0x80000000u) { const uint t = vals[cs[c] & 0x7FFFFFFFu]; for (int a = 0; a < 3; a++) { lo[a] = triBox[(size_t)a * n + t]; hi[a] = triBox[(size_t)(3 + a) * n + t]; } }
+        else for (int a = 0; a < 3; a++) { lo[a] = nodeBox[(size_t)a * m + cs[c]]; hi[a] = nodeBox[(size_t)(3 + a) * m + cs[c]]; }
+        padBox(lo, hi);
+        for (int a = 0; a < 3; a++) { nd.q[6 * c + 2 * a] = lo[a]; nd.q[6 * c + 2 * a + 1] = hi[a]; }
+        if (c == 0) nd.ref0 = ref; else nd.ref1 = ref;
+        if (lc == 0u) { const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2]; sah += (double)(dx * dy + dy * dz + dz * dx); }
+      }
+      nd.pad0 = nd.pad1 = 0u;
+      nodes[sl.nodeBase + (i - node0)] = nd;
+      }
+    }
+  }
+  // per mesh: one atomic per wave when the wave's nodes belong to one mesh (large meshes), else one per lane
+  const unsigned long long has = __ballot(geom != 0xFFFFFFFFu);
+  if (has == 0ull) return;
+  const uint g0 = __shfl(geom, __ffsll((long long)has) - 1);
+  if (__all(geom == 0xFFFFFFFFu || geom == g0)) {
+    for (int o = 32; o > 0; o >>= 1) sah += __shfl_down(sah, o);
+    if ((threadIdx.x & 63u) == 0u && sah != 0.0) atomicAdd(&mesh[g0].sahSum, sah);
+  } else if (geom != 0xFFFFFFFFu && sah != 0.0) atomicAdd(&mesh[geom].sahSum, sah);
+}
+__global__ void __launch_bounds__(256) tlGatherTrisKernel(const float* __restrict__ geomPos, const uint* __restrict__ geomIdx, const LbvhMeshSlot* __restrict__ slots, const uint2* __restrict__ batch,
+                                                          const unsigned long long* __restrict__ keys, uint slotBits, uint n, const uint* __restrict__ vals, BvhTri* tris)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= n) return;
+  const uint2 bt = batch[lbvhKeySlot(keys[k], slotBits)];               // (sorted by slot first: position k and the triangle it holds belong to the same mesh)
+  const LbvhMeshSlot sl = slots[bt.y];
+  const uint p = vals[k] - bt.x;
+  const uint* ix = geomIdx + sl.idxOff + 3 * (size_t)p;
+  const float* A = geomPos + sl.posOff + 3 * (size_t)ix[0]; const float* B = geomPos + sl.posOff + 3 * (size_t)ix[1]; const float* Cc = geomPos + sl.posOff + 3 * (size_t)ix[2];
+  BvhTri t;
+  for (int a = 0; a < 3; a++) { t.v0[a] = A[a]; t.e1[a] = B[a] - A[a]; t.e2[a] = Cc[a] - A[a]; }   // the host build's object-space record
+  t.primId = p; t.instId = 0u; t.pad1 = 0u;
+  tris[sl.triBase + (k - bt.x)] = t;
+}
+// per dirty mesh: its root as the instances will hold it, and the inner levels of its emitted tree
+__global__ void __launch_bounds__(256) tlMeshRootKernel(const uint2* __restrict__ batch, uint D, const LbvhMeshSlot* __restrict__ slots, const uint* __restrict__ height, LbvhMeshOut* mesh)
+{
+  const uint d = blockIdx.x * 256u + threadIdx.x;
+  if (d >= D) return;
+  const uint2 bt = batch[d];
+  const LbvhMeshSlot sl = slots[bt.y];
+  LbvhMeshOut* o = mesh + bt.y;
+  if (sl.nt <= (uint)BVH_LEAF_MAX) { o->root = REF_LEAF | (sl.nt << 28) | sl.triBase; o->depth = 0u; return; }
+  const uint r = o->karrasRoot;
+  if (r - bt.x >= sl.nt) return;                                        // (never: the cut found no root; the mesh stays out of the TLAS)
+  o->root = sl.nodeBase + (r - tlFirstNode(r, bt.x)); o->depth = height[r] + 1u;
+}
+// TLAS: the padded world box of every instance of a non-empty mesh - the eight corners of the BLAS bounds through the object -> world rows at both
+// keys, the host build's expressions - and the bounds of those boxes; an instance of an empty mesh gets an inverted box
+__global__ void __launch_bounds__(256) tlInstBoxKernel(const uint* __restrict__ instGeom, const float* __restrict__ instMotion, const LbvhMeshOut* __restrict__ mesh, uint ni, float* __restrict__ box, TlasResult* R)
+{
+  __shared__ uint sLo[3], sHi[3];
+  if (threadIdx.x < 3) { sLo[threadIdx.x] = 0xFFFFFFFFu; sHi[threadIdx.x] = 0u; }
+  __syncthreads();
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  if (i < ni) {
+    const LbvhMeshOut mo = mesh[instGeom[i]];
+    float lo[3] = { 1.0f, 1.0f, 1.0f }, hi[3] = { -1.0f, -1.0f, -1.0f };
+    if (mo.root != REF_NONE) {
+      float blo[3], bhi[3];
+      for (int a = 0; a < 3; a++) { blo[a] = keyFloat(mo.lo[a]); bhi[a] = keyFloat(mo.hi[a]); lo[a] = 3.402823466e+38f; hi[a] = -3.402823466e+38f; }
+      for (int key = 0; key < 2; key++) {
+        const float* m = instMotion + 24 * (size_t)i + 12 * key;
+        for (int k = 0; k < 8; k++) {
+          const float p[3] = { (k & 1) ? bhi[0] : blo[0], (k & 2) ? bhi[1] : blo[1], (k & 4) ? bhi[2] : blo[2] };
+          const float q[3] = { m[0] * p[0] + m[1] * p[1] + m[2] * p[2] + m[3], m[4] * p[0] + m[5] * p[1] + m[6] * p[2] + m[7], m[8] * p[0] + m[9] * p[1] + m[10] * p[2] + m[11] };
+          for (int a = 0; a < 3; a++) { lo[a] = fminf(lo[a], q[a]); hi[a] = fmaxf(hi[a], q[a]); }
+        }
+      }
+      padBox(lo, hi);
+      for (int a = 0; a < 3; a++) { atomicMin(&sLo[a], floatKey(lo[a])); atomicMax(&sHi[a], floatKey(hi[a])); }
+    }
+    for (int a = 0; a < 3; a++) { box[(size_t)a * ni + i] = lo[a]; box[(size_t)(3 + a) * ni + i] = hi[a]; }
+  }
+  __syncthreads();
+  if (threadIdx.x < 3 && sLo[threadIdx.x] <= sHi[threadIdx.x]) { atomicMin(&R->lo[threadIdx.x], sLo[threadIdx.x]); atomicMax(&R->hi[threadIdx.x], sHi[threadIdx.x]); }
+}
+// an instance of an empty mesh sorts behind every live one: the hierarchy is built over the first nLive entries of the sorted arrays
+__global__ void __launch_bounds__(256) tlInstMortonKernel(const float* __restrict__ box, uint ni, const TlasResult* R, unsigned long long* keys, uint* vals)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  if (k >= ni) return;
+  keys[k] = box[k] > box[(size_t)3 * ni + k] ? 0xFFFFFFFFFFFFFFFFull : mortonOfBox(box, ni, k, R->lo, R->hi); vals[k] = k;
+}
+// TLAS nodes (node = Karras node, the TLAS occupies the front of the node array), leaves of exactly one instance with the instance's own padded
+// box; the two sums of the estimate: half-areas of the inner children, and per live instance halfArea(box) / halfArea(root) x its BLAS' visits
+__global__ void __launch_bounds__(256) tlEmitTlasKernel(uint nLive, uint ni, const uint* __restrict__ childL, const uint* __restrict__ childR, const float* __restrict__ box, const uint* __restrict__ vals,
+                                                        const float* __restrict__ nodeBox, const uint* __restrict__ depth, const uint* __restrict__ instGeom, const LbvhMeshOut* __restrict__ mesh,
+                                                        BvhNode* nodes, TlasResult* R)
+{
+  const uint k = blockIdx.x * 256u + threadIdx.x;
+  const size_t m = nLive - 1u;
+  double sah = 0.0, inst = 0.0;
+  float rlo[3], rhi[3];
+  for (int a = 0; a < 3; a++) { rlo[a] = nodeBox[(size_t)a * m]; rhi[a] = nodeBox[(size_t)(3 + a) * m]; }   // (node 0 is the root)
+  const float a0 = halfAreaOf(rlo, rhi);
+  if (k + 1u < nLive) {
+    BvhNode nd;
+    const uint cs[2] = { childL[k], childR[k] };
+    for (int c = 0; c < 2; c++) {
+      float lo[3], hi[3]; uint ref;
+      if (cs[c] & 0x80000000u) { const uint t = vals[cs[c] & 0x7FFFFFFFu]; ref = REF_LEAF | t; for (int a = 0; a < 3; a++) { lo[a] = box[(size_t)a * ni + t]; hi[a] = box[(size_t)(3 + a) * ni + t]; } }
+      else {
+        ref = cs[c];
+        for (int a = 0; a < 3; a++) { lo[a] = nodeBox[(size_t)a * m + cs[c]]; hi[a] = nodeBox[(size_t)(3 + a) * m + cs[c]]; }
+        padBox(lo, hi);
+        sah += (double)halfAreaOf(lo, hi);
+      }
+      for (int a = 0; a < 3; a++) { nd.q[6 * c + 2 * a] = lo[a]; nd.q[6 * c + 2 * a + 1] = hi[a]; }
+      if (c == 0) nd.ref0 = ref; else nd.ref1 = ref;
+    }
+    nd.pad0 = nd.pad1 = 0u;
+    nodes[k] = nd;
+  }
+  if (k < nLive && a0 > 0.0f) {
+    const uint t = vals[k];
+    float lo[3], hi[3];
+    for (int a = 0; a < 3; a++) { lo[a] = box[(size_t)a * ni + t]; hi[a] = box[(size_t)(3 + a) * ni + t]; }
+    inst = (double)halfAreaOf(lo, hi) / (double)a0 * (double)lbvhBlasVisits(mesh[instGeom[t]]);
+  }
+  if (k == 0u) { R->a0 = a0; R->depth = depth[0]; }
+  for (int o = 32; o > 0; o >>= 1) { sah += __shfl_down(sah, o); inst += __shfl_down(inst, o); }
+  if ((threadIdx.x & 63u) == 0u) { if (sah != 0.0) atomicAdd(&R->sahSum, sah); if (inst != 0.0) atomicAdd(&R->instSum, inst); }
+}
+
 template <class T> bool ensure(T*& p, size_t count) { if (p) (void)hipFree(p); p = nullptr; return hipMalloc((void**)&p, count * sizeof(T)) == hipSuccess; }
 
 } // namespace
@@ -476,6 +707,27 @@ void* lbvhCreate() { return new Scratch(); }
 void lbvhDestroy(void* s) { if (s) { ((Scratch*)s)->freeAll(); delete (Scratch*)s; } }
 
 #define LCHK(call) do { hipError_t _e = (call); if (_e != hipSuccess) { err = std::string(#call) + ": " + hipGetErrorString(_e); return false; } } while (0)
+
+// the per-primitive arrays and the sort's temporary storage, for builds over up to n primitives
+static bool growScratch(Scratch& S, size_t n, std::string& err)
+{
+  if (n <= S.cap) return true;
+  const size_t c = n;
+  bool ok = ensure(S.triBox, 6 * c) && ensure(S.keysIn, c) && ensure(S.keysOut, c) && ensure(S.valsIn, c) && ensure(S.valsOut, c) && ensure(S.childL, c) && ensure(S.childR, c) &&
+            ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.height, c) && ensure(S.folded, c) && ensure(S.nodeBox, 6 * c) &&
+            ensure(S.frontA, c) && ensure(S.frontB, c);
+  if (!ok) { err = "hipMalloc (build scratch)"; S.cap = 0; return false; }
+  S.cap = c;
+  if (S.passIds) { (void)hipFree(S.passIds); S.passIds = nullptr; }
+  size_t bytes = 0, bytes64 = 0;                                       // (the single-level build sorts 63 bits, section 9 all 64)
+  LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 63, nullptr));
+  LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes64, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 64, nullptr));
+  if (bytes64 > bytes) bytes = bytes64;
+  if (S.sortTemp) (void)hipFree(S.sortTemp);
+  S.sortTemp = nullptr;
+  LCHK(hipMalloc(&S.sortTemp, bytes + 16)); S.sortTempBytes = bytes;
+  return true;
+}
 
 bool lbvhUploadGeometry(void* scratch, const std::vector<const float*>& pos, const std::vector<size_t>& posFloats, const std::vector<const uint*>& idx, const std::vector<size_t>& idxCount,
                         std::vector<size_t>& posOffset, std::vector<size_t>& idxOffset, std::string& err)
@@ -499,20 +751,7 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   out = LbvhResult();
   S.ni = 0; S.n = 0;
   if (n == 0u) { out.rootRef = REF_NONE; return true; }
-  if (n > S.cap) {
-    const size_t c = n;
-    bool ok = ensure(S.triBox, 6 * c) && ensure(S.keysIn, c) && ensure(S.keysOut, c) && ensure(S.valsIn, c) && ensure(S.valsOut, c) && ensure(S.childL, c) && ensure(S.childR, c) &&
-              ensure(S.parent, c) && ensure(S.leafParent, c) && ensure(S.first, c) && ensure(S.last, c) && ensure(S.flags, c) && ensure(S.depth, c) && ensure(S.height, c) && ensure(S.folded, c) && ensure(S.nodeBox, 6 * c) &&
-              ensure(S.frontA, c) && ensure(S.frontB, c);
-    if (!ok) { err = "hipMalloc (build scratch)"; S.cap = 0; return false; }
-    S.cap = c;
-    if (S.passIds) { (void)hipFree(S.passIds); S.passIds = nullptr; }
-    size_t bytes = 0;
-    LCHK(hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 63, nullptr));
-    if (S.sortTemp) (void)hipFree(S.sortTemp);
-    S.sortTemp = nullptr;
-    LCHK(hipMalloc(&S.sortTemp, bytes + 16)); S.sortTempBytes = bytes;
-  }
+  if (!growScratch(S, n, err)) return false;
   if (!S.counters) LCHK(hipMalloc((void**)&S.counters, sizeof(LbvhCounters)));
   if (ni > S.instCap) { if (!ensure(S.instMat, 12 * (size_t)ni) || !ensure(S.instInfo, (size_t)ni)) { err = "hipMalloc (instances)"; return false; } S.instCap = ni; }
   {
@@ -548,7 +787,7 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
   LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
   LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
   lbvhHierarchyKernel<<<grdN, blk>>>(S.keysOut, (int)n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.folded);
-  lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+  lbvhFitKernel<<<grdN, blk>>>(S.triBox, n, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
   if (qualityPasses) {
     // "device_build_quality": treelet passes over the whole tree. Per pass: the emitted nodes grouped by their present height (the kernels of section 7,
     // into a list of the build's own), one lbvhTreeletKernel launch per height from 1 up, then the fit again for the new heights and depths
@@ -581,7 +820,7 @@ bool lbvhBuild(void* scratch, const LbvhInstance* insts, uint ni, uint n, BvhNod
         LCHK(hipMemsetAsync(S.flags, 0, (size_t)n * sizeof(uint), nullptr));
         LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
         LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
-        lbvhFitKernel<<<grdN, blk>>>(S.triBox, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+        lbvhFitKernel<<<grdN, blk>>>(S.triBox, n, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
         out.passesRun = pass + 1u;
       }
       LCHK(hipEventRecord(ev1, nullptr));
@@ -648,6 +887,118 @@ bool lbvhUpdatePositions(void* scratch, const std::vector<uint>& geoms, const st
   lbvhRegatherTrisKernel<<<dim3((n + 255u) / 256u), dim3(256)>>>(S.geomPos, S.geomIdx, S.instInfo, S.instDirty, ni, n, tris);
   LCHK(hipGetLastError());
   LCHK(hipStreamSynchronize(nullptr));                                 // (the caller's staging leaves scope)
+  return true;
+}
+
+// ---- the two-level layout (section 9's kernels). Launches and synchronisations per call do not depend on the number of meshes or instances -------------
+namespace {
+struct StageTimer                          // device time between two events on the null stream
+{
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  ~StageTimer() { if (e0) (void)hipEventDestroy(e0); if (e1) (void)hipEventDestroy(e1); }
+  bool start() { return hipEventCreate(&e0) == hipSuccess && hipEventCreate(&e1) == hipSuccess && hipEventRecord(e0, nullptr) == hipSuccess; }
+  bool stop(float& ms) { return hipEventRecord(e1, nullptr) == hipSuccess && hipEventSynchronize(e1) == hipSuccess && hipEventElapsedTime(&ms, e0, e1) == hipSuccess; }
+};
+}
+
+bool lbvhCopyPositions(void* scratch, const std::vector<uint>& geoms, const std::vector<const float*>& pos, const std::vector<size_t>& posFloats, const std::vector<size_t>& posOffset, std::string& err)
+{
+  Scratch& S = *(Scratch*)scratch;
+  for (uint g : geoms) {
+    if (!S.geomPos || g >= pos.size() || g >= posFloats.size() || g >= posOffset.size() || posOffset[g] + posFloats[g] > S.geomPosCap) { err = "a mesh outside the uploaded geometry"; return false; }
+    if (posFloats[g]) LCHK(hipMemcpyAsync(S.geomPos + posOffset[g], pos[g], posFloats[g] * sizeof(float), hipMemcpyHostToDevice, nullptr));
+  }
+  LCHK(hipStreamSynchronize(nullptr));                                 // (the caller's staging leaves scope)
+  return true;
+}
+
+bool lbvhBuildBlasBatch(void* scratch, const LbvhMeshSlot* slots, uint numGeoms, const uint* dirty, uint numDirty, LbvhMeshOut* meshOut, BvhNode* nodes, BvhTri* tris, float& ms, std::string& err)
+{
+  Scratch& S = *(Scratch*)scratch;
+  ms = 0.0f;
+  S.ni = 0; S.n = 0;                                                   // (the scratch no longer holds a single-level build's order)
+  if (numGeoms > S.meshCap) { if (!ensure(S.meshSlot, (size_t)numGeoms) || !ensure(S.meshOut, (size_t)numGeoms)) { err = "hipMalloc (meshes)"; S.meshCap = 0; return false; } S.meshCap = numGeoms; }
+  if (numDirty > S.batchCap) { if (!ensure(S.batch, (size_t)numDirty)) { err = "hipMalloc (batch)"; S.batchCap = 0; return false; } S.batchCap = numDirty; }
+  std::vector<uint2> batch(numDirty);
+  size_t total = 0;
+  for (uint d = 0; d < numDirty; d++) {
+    if (dirty[d] >= numGeoms || slots[dirty[d]].nt == 0u) { err = "an empty mesh in the batch"; return false; }
+    batch[d] = make_uint2((uint)total, dirty[d]); total += slots[dirty[d]].nt;
+  }
+  if (total >= (size_t(1) << 31)) { err = "more than 2^31 triangles in one batch"; return false; }
+  const uint n = (uint)total, D = numDirty;
+  if (numGeoms) {
+    LCHK(hipMemcpyAsync(S.meshSlot, slots, (size_t)numGeoms * sizeof(LbvhMeshSlot), hipMemcpyHostToDevice, nullptr));
+    LCHK(hipMemcpyAsync(S.meshOut, meshOut, (size_t)numGeoms * sizeof(LbvhMeshOut), hipMemcpyHostToDevice, nullptr));
+  }
+  if (n == 0u) { LCHK(hipStreamSynchronize(nullptr)); return true; }
+  if (!growScratch(S, n, err)) return false;
+  LCHK(hipMemcpyAsync(S.batch, batch.data(), (size_t)D * sizeof(uint2), hipMemcpyHostToDevice, nullptr));
+  StageTimer timer;
+  if (!timer.start()) { err = "hipEventCreate / hipEventRecord"; return false; }
+  const uint slotBits = lbvhSlotBits(D);
+  const dim3 blk(256), grdN((n + 255u) / 256u);
+  tlTriBoxKernel<<<grdN, blk>>>(S.geomPos, S.geomIdx, S.meshSlot, S.batch, D, n, S.triBox, S.meshOut);
+  tlMortonKernel<<<grdN, blk>>>(S.triBox, S.batch, D, n, S.meshOut, slotBits, S.keysIn, S.valsIn);
+  size_t bytes = S.sortTempBytes;
+  LCHK(hipcub::DeviceRadixSort::SortPairs(S.sortTemp, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)n, 0, 64, nullptr));
+  tlGatherTrisKernel<<<grdN, blk>>>(S.geomPos, S.geomIdx, S.meshSlot, S.batch, S.keysOut, slotBits, n, S.valsOut, tris);
+  if (n >= 2u) {
+    LCHK(hipMemsetAsync(S.flags, 0, (size_t)n * sizeof(uint), nullptr));
+    LCHK(hipMemsetAsync(S.depth, 0, (size_t)n * sizeof(uint), nullptr));
+    LCHK(hipMemsetAsync(S.height, 0, (size_t)n * sizeof(uint), nullptr));
+    lbvhHierarchyKernel<<<grdN, blk>>>(S.keysOut, (int)n, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.folded);
+    tlCutKernel<<<grdN, blk>>>(S.keysOut, n, slotBits, S.batch, S.meshSlot, S.childL, S.childR, S.first, S.last, S.parent, S.leafParent, S.meshOut);
+    lbvhFitKernel<<<grdN, blk>>>(S.triBox, n, S.valsOut, n, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+    tlEmitBlasKernel<<<grdN, blk>>>(S.keysOut, n, slotBits, S.batch, S.meshSlot, S.childL, S.childR, S.first, S.last, S.folded, S.triBox, S.valsOut, S.nodeBox, nodes, S.meshOut);
+  }
+  tlMeshRootKernel<<<dim3((D + 255u) / 256u), blk>>>(S.batch, D, S.meshSlot, S.height, S.meshOut);
+  LCHK(hipGetLastError());
+  if (!timer.stop(ms)) { err = "hipEventSynchronize"; return false; }
+  LCHK(hipMemcpy(meshOut, S.meshOut, (size_t)numGeoms * sizeof(LbvhMeshOut), hipMemcpyDeviceToHost));
+  return true;
+}
+
+bool lbvhBuildTlas(void* scratch, const uint* instGeom, uint ni, uint nLive, uint firstLive, const float* instMotion, const LbvhMeshOut* meshOut, uint numGeoms, BvhNode* nodes, LbvhTlasResult& out, float& ms, std::string& err)
+{
+  Scratch& S = *(Scratch*)scratch;
+  out = LbvhTlasResult(); ms = 0.0f;
+  if (nLive == 0u || firstLive >= ni || instGeom[firstLive] >= numGeoms) return true;
+  if (nLive == 1u) {                                                   // the root is the instance's leaf: no node, nothing to launch
+    out.rootRef = REF_LEAF | firstLive; out.depth = 0u; out.sahVisits = lbvhBlasVisits(meshOut[instGeom[firstLive]]);
+    return true;
+  }
+  if (numGeoms > S.meshCap || !S.meshOut) { err = "no batch was built for these meshes"; return false; }
+  if (!growScratch(S, ni, err)) return false;
+  S.ni = 0; S.n = 0;
+  if (ni > S.instGeomCap) { if (!ensure(S.instGeom, (size_t)ni)) { err = "hipMalloc (instances)"; S.instGeomCap = 0; return false; } S.instGeomCap = ni; }
+  if (!S.tlasResult) LCHK(hipMalloc(&S.tlasResult, sizeof(TlasResult)));
+  TlasResult init; std::memset(&init, 0, sizeof(init));
+  for (int a = 0; a < 3; a++) { init.lo[a] = 0xFFFFFFFFu; init.hi[a] = 0u; }
+  LCHK(hipMemcpyAsync(S.instGeom, instGeom, (size_t)ni * sizeof(uint), hipMemcpyHostToDevice, nullptr));
+  LCHK(hipMemcpyAsync(S.tlasResult, &init, sizeof(init), hipMemcpyHostToDevice, nullptr));
+  StageTimer timer;
+  if (!timer.start()) { err = "hipEventCreate / hipEventRecord"; return false; }
+  TlasResult* R = (TlasResult*)S.tlasResult;
+  const dim3 blk(256), grdI((ni + 255u) / 256u), grdL((nLive + 255u) / 256u);
+  tlInstBoxKernel<<<grdI, blk>>>(S.instGeom, instMotion, S.meshOut, ni, S.triBox, R);
+  tlInstMortonKernel<<<grdI, blk>>>(S.triBox, ni, R, S.keysIn, S.valsIn);
+  size_t bytes = S.sortTempBytes;
+  LCHK(hipcub::DeviceRadixSort::SortPairs(S.sortTemp, bytes, S.keysIn, S.keysOut, S.valsIn, S.valsOut, (int)ni, 0, 64, nullptr));
+  LCHK(hipMemsetAsync(S.flags, 0, (size_t)nLive * sizeof(uint), nullptr));
+  LCHK(hipMemsetAsync(S.depth, 0, (size_t)nLive * sizeof(uint), nullptr));
+  LCHK(hipMemsetAsync(S.height, 0, (size_t)nLive * sizeof(uint), nullptr));
+  lbvhHierarchyKernel<<<grdL, blk>>>(S.keysOut, (int)nLive, S.childL, S.childR, S.parent, S.leafParent, S.first, S.last, S.folded);
+  lbvhFitKernel<<<grdL, blk>>>(S.triBox, ni, S.valsOut, nLive, S.childL, S.childR, S.parent, S.leafParent, S.folded, S.flags, S.nodeBox, S.depth, S.height);
+  tlEmitTlasKernel<<<grdL, blk>>>(nLive, ni, S.childL, S.childR, S.triBox, S.valsOut, S.nodeBox, S.depth, S.instGeom, S.meshOut, nodes, R);
+  LCHK(hipGetLastError());
+  if (!timer.stop(ms)) { err = "hipEventSynchronize"; return false; }
+  TlasResult res;
+  LCHK(hipMemcpy(&res, S.tlasResult, sizeof(res), hipMemcpyDeviceToHost));
+  out.rootRef = 0u; out.depth = res.depth;
+  // TLAS visits + the chance of entering each instance x its BLAS visits (hpt_host.hip's two-level estimate)
+  const float tlasVisits = res.a0 > 0.0f ? (float)(1.0 + res.sahSum / (double)res.a0) : 0.0f;
+  out.sahVisits = (float)((double)tlasVisits + res.instSum);
   return true;
 }
 

@@ -59,6 +59,8 @@ public:
   uint32_t AddInstance(uint32_t a_geomId, const float4x4& a_matrix) { return hpt_add_instance(m_ctx, a_geomId, a_matrix.m); }
   uint32_t AddInstanceMotion(uint32_t a_geomId, const float4x4* a_matrices, uint32_t a_matrixNumber) { return hpt_add_instance_motion(m_ctx, a_geomId, a_matrices[0].m, a_matrixNumber); }
   void     UpdateInstance(uint32_t a_instanceId, const float4x4& a_matrix) { hpt_update_instance(m_ctx, a_instanceId, a_matrix.m); }
+  // options as BuildOptions (CrossRT.h:8-14): BUILD_LOW | BUILD_MEDIUM ask for the device build - of the single-level layout, and under
+  // hpt_set_option(ctx, "device_build_two_level", 1) of the two-level one too (then UpdateInstance + CommitScene rebuilds only the TLAS)
   void     CommitScene(uint32_t options = 4) { hpt_commit_scene(m_ctx, options); }
   // single-ray forms of the reference interface; the batched C entry points are what a throughput caller should use
   CRT_Hit  RayQuery_NearestHit(const float posAndNear[4], const float dirAndFar[4])

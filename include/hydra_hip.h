@@ -548,6 +548,15 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               surface-area cost, rewritten when strictly cheaper). Applies to every device build - "device_build" 1, BUILD_LOW | BUILD_MEDIUM, the
  *               build after a rejected refit, the rebuild of a device-built tree - and never to the host's. Anything else is an argument error.
  *               Setting it uncommits the scene, as "device_build" does. Hits do not depend on it; hpt_get_build_info says what the passes did.
+ *   "device_build_two_level"  0 (default): scenes that take the two-level layout (a moving instance, hpt_set_accel_layout(ctx, 1), more instanced
+ *               triangles than the single-level budget) are built by the host whatever is asked; 1: when a device build is asked for ("device_build" 1,
+ *               or BUILD_LOW | BUILD_MEDIUM without BUILD_HIGH) and the scene is no triangle sweep and has a triangle, the BLAS of all meshes are
+ *               built by ONE batched linear-BVH build in object space and the TLAS over the live instances by a second one. A later commit that
+ *               only saw hpt_update_instance rebuilds the TLAS alone (BLAS nodes and all triangle records stay byte for byte); one that saw
+ *               hpt_update_geom_triangles3f with unchanged indices rebuilds those meshes' BLAS in their slots, then the TLAS; anything else is a
+ *               full device build ("refit", 0 forces that too). A tree deeper than the traversal stack goes to the host's builder as a whole.
+ *               No treelet passes, no 4-wide form, no shading records on this layout. Anything but 0 / 1 is an argument error; setting it
+ *               uncommits the scene. Hits do not depend on it; hpt_get_two_level_info says what the last commit did.
  *   "refit_max_sah_pct"  p: 0 (default) = never; p >= 100: a refit whose surface-area estimate (hpt_get_refit_info) exceeds p / 100 times the
  *               estimate at build time is followed, in the same hpt_commit_scene, by a build (on the device for a device-built tree, on the host
  *               for a host-built one). 1 .. 99 is an argument error.
@@ -620,6 +629,18 @@ int  hpt_get_build_info(hpt_ctx* ctx, float out[4]);
  * dst == NULL: only *outBytes is set. HPT_ERR_ARG when capacityBytes is too small, HPT_ERR_STATE when no single-level tree is committed
  * (the two-level and sweep layouts are not read back). */
 int  hpt_read_accel(hpt_ctx* ctx, int what, void* dst, uint64_t capacityBytes, uint64_t* outBytes, uint32_t* outRootRef);
+/* The last hpt_commit_scene when it built the two-level layout on the device (hpt_set_option("device_build_two_level", 1)): out[0] = 1,
+ * out[1] = BLAS built by that commit, out[2] = BLAS kept from earlier commits, out[3] = 1 when it rebuilt only the TLAS, out[4] = inner levels
+ * of the TLAS, out[5] = of the deepest BLAS, out[6] / out[7] = device milliseconds of the BLAS / TLAS stage (between device events; contained in
+ * hpt_get_commit_time's out[2]). All zeros after any other kind of commit. */
+int  hpt_get_two_level_info(hpt_ctx* ctx, float out[8]);
+/* Host copy of the committed two-level tree (either builder's) as it lies in device memory, with hpt_read_accel's conventions: what = 0 the BvhNode
+ * array (the TLAS first; an instance leaf is a reference with bit 31 set, count bits 0 and the instance id in bits 0..27), what = 1 the BvhTri
+ * array (every mesh's records in its BLAS' leaf order, instId 0), what = 2 the BvhInst array (64-byte records: three world -> object rows of four
+ * floats, the mesh's BLAS root as a reference into the two arrays, geomId, 1 for a moving instance, a pad word). *outRootRef receives the TLAS
+ * root. A device-built tree's node array has unused entries (the TLAS region past its nodes, slots of subtrees folded into leaves): zeros after a
+ * full build, stale nodes after an in-place update; only what the roots reach is a node. HPT_ERR_STATE unless a two-level tree is committed. */
+int  hpt_read_accel_two_level(hpt_ctx* ctx, int what, void* dst, uint64_t capacityBytes, uint64_t* outBytes, uint32_t* outRootRef);
 /* Schedule the last hpt_path_trace_block(_dev) call used (1 .. 4, as hpt_set_schedule numbers them) and, for the wavefront one, its number of
  * shade+trace rounds. */
 int  hpt_get_schedule(hpt_ctx* ctx, int* lastSchedule, uint32_t* lastIterations);
