@@ -110,6 +110,7 @@ ABI = {
     "hpt_qmc_sample_count": (_u32, [_u32, _u32]),
     "hpt_path_trace_qmc_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
     "hpt_path_trace_qmc_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp]),
+    "hpt_path_trace_qmc_block_dev2": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "hpt_kmlt_state_size": (_u32, [_u32]),
     "hpt_path_trace_pss_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
     "hpt_kmlt_chain_count": (_i, [_vp, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
@@ -251,6 +252,7 @@ class HipIntegrator:
         self.scene = None
         self.params = None
         self.W = self.H = self.N = 0
+        self._qmc_spectral = False       # set_option("qmc_spectral", 1) was called
         if accel_layout:
             self._chk(self.L.hpt_set_accel_layout(self.h, accel_layout))   # 1 = two-level TLAS/BLAS, 2 = single-level, 3 = triangle sweep (tiny scenes)
         if scene is not None:
@@ -365,23 +367,36 @@ class HipIntegrator:
     # ---- IntegratorQMC (mlt/integrator_qmc.cpp) -----------------------------------------------------------------------
     def PathTraceBlockQMC(self, pixelsNum, channels, out_color, a_passNum):
         """IntegratorQMC::PathTraceBlock(pixelsNum, channels, out_color, a_passNum): min(2^32 - 1, pixelsNum * a_passNum) samples of the
-        Niederreiter sequence, each ADDED (float atomics) to the pixel its first two dimensions select; out_color float32 [winHeight, winWidth, channels]."""
-        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and (channels not in (1, 3, 4) or out_color.size == self.N * channels)
+        Niederreiter sequence, each ADDED (float atomics) to the pixel its first two dimensions select; out_color float32 [winHeight, winWidth, channels].
+        After set_option("qmc_spectral", 1) a spectral scene is served; channels above 4 are then wavelength layers: out_color float32
+        [channels, winHeight, winWidth] (without the option the library refuses them, whatever the array's size)."""
+        served = channels in (1, 3, 4) or (channels > 4 and self._qmc_spectral)
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and (not served or out_color.size == self.N * channels)
         self._chk(self.L.hpt_path_trace_qmc_block(self.h, pixelsNum, channels, out_color.ctypes.data, a_passNum))
 
-    def path_trace_qmc_block_dev(self, dev_ptr, pass_num, pixels_num=None, channels=4, sample_color_ptr=None, sample_pixel_ptr=None, stream=None):
-        """PathTraceBlockQMC on a device frame (may be None when both record pointers are given); asynchronous on `stream`."""
+    def path_trace_qmc_block_dev(self, dev_ptr, pass_num, pixels_num=None, channels=4, sample_color_ptr=None, sample_pixel_ptr=None, stream=None,
+                                 sample_waves_ptr=None):
+        """PathTraceBlockQMC on a device frame (may be None when both record pointers are given); asynchronous on `stream`. sample_waves_ptr: the
+        third record of spectral QMC (hpt_path_trace_qmc_block_dev2), four wavelengths per sample."""
+        if sample_waves_ptr is not None:
+            self._chk(self.L.hpt_path_trace_qmc_block_dev2(self.h, self.N if pixels_num is None else pixels_num, channels, dev_ptr, pass_num,
+                                                           sample_color_ptr, sample_pixel_ptr, sample_waves_ptr, stream))
+            return
         self._chk(self.L.hpt_path_trace_qmc_block_dev(self.h, self.N if pixels_num is None else pixels_num, channels, dev_ptr, pass_num,
                                                       sample_color_ptr, sample_pixel_ptr, stream))
 
-    def render_qmc(self, spp, channels=4, frame=True, records=False, pixels_num=None):
+    def render_qmc(self, spp, channels=4, frame=True, records=False, pixels_num=None, waves=False):
         """One PathTraceBlockQMC call through the device-pointer form. Returns (frame or None, colours [S, 4] or None, pixel indices [S] or None):
-        the frame is the atomic sum (zeros before the call), the records are the per-sample values in sample order."""
+        the frame is the atomic sum (zeros before the call), the records are the per-sample values in sample order. waves=True (spectral QMC,
+        implies records): a fourth element, the samples' wavelengths [S, 4]. channels above 4: the frame is [channels, H, W] wavelength layers
+        and a colour record is the sample's four exposure * accumColor[i]."""
         pixels_num = self.N if pixels_num is None else pixels_num
+        records = records or waves
         S = qmc_sample_count(pixels_num, spp)
-        img = np.zeros((self.H, self.W, channels), np.float32) if frame else None
+        img = np.zeros((self.H, self.W, channels) if channels <= 4 else (channels, self.H, self.W), np.float32) if frame else None
         col = np.zeros((S, 4), np.float32) if records else None
         pix = np.zeros(S, np.uint32) if records else None
+        wav = np.zeros((S, 4), np.float32) if waves else None
         ptrs = []
 
         def dev(nbytes):
@@ -393,18 +408,21 @@ class HipIntegrator:
             d_img = dev(img.nbytes) if frame else None
             d_col = dev(col.nbytes) if records else None
             d_pix = dev(pix.nbytes) if records else None
+            d_wav = dev(wav.nbytes) if waves else None
             if frame:
                 self._chk(self.L.hpt_device_copy(self.h, d_img, img.ctypes.data, img.nbytes, 1))
-            self.path_trace_qmc_block_dev(d_img, spp, pixels_num, channels, d_col, d_pix)
+            self.path_trace_qmc_block_dev(d_img, spp, pixels_num, channels, d_col, d_pix, sample_waves_ptr=d_wav)
             if frame:
                 self._chk(self.L.hpt_device_copy(self.h, img.ctypes.data, d_img, img.nbytes, 2))
             if records:
                 self._chk(self.L.hpt_device_copy(self.h, col.ctypes.data, d_col, col.nbytes, 2))
                 self._chk(self.L.hpt_device_copy(self.h, pix.ctypes.data, d_pix, pix.nbytes, 2))
+            if waves:
+                self._chk(self.L.hpt_device_copy(self.h, wav.ctypes.data, d_wav, wav.nbytes, 2))
         finally:
             for p in ptrs:
                 self.L.hpt_device_free(self.h, p)
-        return img, col, pix
+        return (img, col, pix, wav) if waves else (img, col, pix)
 
     # ---- IntegratorKMLT (mlt/integrator_kmlt.cpp) ---------------------------------------------------------------------
     def _dev_scope(self):
@@ -723,6 +741,8 @@ class HipIntegrator:
 
     def set_option(self, name: str, value: int):
         self._chk(self.L.hpt_set_option(self.h, name.encode(), value))
+        if name == "qmc_spectral":
+            self._qmc_spectral = bool(value)     # PathTraceBlockQMC then takes frames of more than 4 channels
 
     def accel_info(self):
         out = (C.c_float * 4)()

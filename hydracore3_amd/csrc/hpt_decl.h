@@ -255,11 +255,47 @@ struct QmcJob
   uint   dofDim, motionDim, matDim, lgtDim;   // EnableQMC's dimension offsets (0: that draw stays pseudo)
   float4* sampleColor;            // per-sample records, indexed by s (both null or both set): the colour as added ...
   uint*   samplePixel;            // ... and the pixel index y * winWidth + x
+  uint    spdDim;                 // spectral QMC: the hero-wavelength dimension (0: pseudo) ...
+  float4* sampleWaves;            // ... and a third record, the sample's four wavelengths (null, or set with the other two)
+};
+// qmc::rndFloat (rnd_qmc.cpp:189-196). `dim` is wave-uniform, so the 31 columns are scalar loads from the 1364-byte table.
+HPT_DEV float qmcFloat(const uint* __restrict__ table, uint pos, uint dim)
+{
+  const uint* __restrict__ col = table + dim * QMC_RESOLUTION;
+  uint r = 0u;
+#pragma unroll
+  for (uint bit = 0; bit < QMC_RESOLUTION; bit++) r ^= ((pos >> bit) & 1u) ? col[bit] : 0u;
+  return (float)(r + 1u) * (1.0f / 2147483648.0f);             // uint -> float rounds to nearest; INT_SCALE = 1 / float(0x80000001) = 2^-31
+}
+// IntegratorQMC::GetRandomNumbersLgts / GetRandomNumbersMats (integrator_qmc.cpp:117-139): the pseudo draws are made at every bounce - the
+// lights' float4 BEFORE the selection float, the reverse of the base class - and the first bounce's .x / .y (and the light selection)
+// are then replaced by the sample's QMC dimensions, unless EnableQMC left them to the generator (dimension 0).
+// The policy of shadeVertex (hpt_qmc.hip) and of shadeVertexSpec (hpt_spectral.hip: pathTraceQmcSpectralKernel).
+struct QmcRands
+{
+  const uint* table; uint s, matDim, lgtDim;
+  HPT_DEV V4 lights(Rng& gen, uint bounce, float& rndId) const
+  {
+    V4 r = rng_float4(gen);
+    rndId = rng_float1(gen);
+    if (bounce == 0u && lgtDim != 0u) { r.x = qmcFloat(table, s, lgtDim); r.y = qmcFloat(table, s, lgtDim + 1u); rndId = qmcFloat(table, s, lgtDim + 2u); }
+    return r;
+  }
+  HPT_DEV V4 mats(Rng& gen, uint bounce) const
+  {
+    V4 r = rng_float4(gen);
+    if (bounce == 0u && matDim != 0u) { r.x = qmcFloat(table, s, matDim); r.y = qmcFloat(table, s, matDim + 1u); }
+    return r;
+  }
+  HPT_DEV float blend(Rng& gen, uint /*bounce*/, uint /*layer*/) const { return rng_float1(gen); }   // IntegratorQMC::GetRandomNumbersMatB: pseudo
 };
 // Job carries outColor (may be null when the records are asked for), channels, gens, queue, packedXY / packedCount (camera back plate),
 // the stack overflow area and tidCount = min(N, S) generator slots with work
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q);
+// the same sample loop on four wavelengths per path (hpt_spectral.hip); SCOPE and its launch bounds as pathTraceSpectralKernel
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
+__global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceQmcSpectralKernel(const DevScene S, const Job job, const QmcJob q);
 
 // ---- IntegratorKMLT (mlt/integrator_kmlt.cpp; hpt_kmlt.hip) ------------------------------------------------------------------------------
 // PathTraceF over caller-supplied number vectors: lane i < n reads vector i at x[i * vecStride + slot] and writes color[i], pixel[i]

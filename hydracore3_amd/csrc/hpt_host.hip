@@ -171,6 +171,7 @@ struct hpt_ctx
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
+  bool qmcSpectral = false;                              // hpt_set_option("qmc_spectral", 1): PathTraceBlockQMC serves m_spectral_mode (pathTraceQmcSpectralKernel) instead of refusing it
   uint kmltChains = 0;                                   // hpt_set_option("kmlt_chains", n): 0 = one chain per lane of the resident grid
   uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
@@ -2910,24 +2911,42 @@ static int needPacked(hpt_ctx* c, const std::string& who)
 { return c->packedCount != (uint)(c->S.winWidth * c->S.winHeight) ? c->fail(HPT_ERR_STATE, who + " before PackXYBlock") : HPT_OK; }
 static int needFilmTablesRGB(hpt_ctx* c)
 { return (c->hasFilm && !c->filmTablesRGB) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)") : HPT_OK; }
-static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void* sampleColor, const void* samplePixel)
+static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void* sampleColor, const void* samplePixel, const void* sampleWaves = nullptr)
 {
   const std::string who("PathTraceBlockQMC");
-  if (!out && !sampleColor && !samplePixel) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: no frame and no sample records to write");
+  if (!out && !sampleColor && !samplePixel && !sampleWaves) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: no frame and no sample records to write");
   if ((sampleColor == nullptr) != (samplePixel == nullptr)) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: the sample records come as a pair (colours and pixel indices)");
+  if (sampleWaves != nullptr && sampleColor == nullptr) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC: the wavelength records come with the colour and pixel records, not alone");
   if (int rc = needCommitted(c, who)) return rc;
-  if (int rc = refuseSpectral(c, who, "the spectral kernels are a separate family; hpt_qmc_layout still answers for it")) return rc;
-  if (channels > 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: channels above 4 are the wavelength layers of spectral rendering");
+  const bool spectral = c->qmcSpectral && c->S.spectralMode != 0u;        // hpt_set_option("qmc_spectral", 1): pathTraceQmcSpectralKernel
+  if (!spectral) {
+    if (int rc = refuseSpectral(c, who, "the spectral kernels are a separate family; hpt_qmc_layout still answers for it, hpt_set_option(\"qmc_spectral\", 1) turns spectral QMC on")) return rc;
+    if (channels > 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: channels above 4 are the wavelength layers of spectral rendering");
+  }
   if (channels == 2u || channels == 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: a framebuffer of 1, 3 or 4 channels (three components are written per pixel)");
   if (int rc = needPacked(c, who)) return rc;
   if (c->gensCount == 0u) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC before InitRandomGens: sample s runs on generator s % m_randomGens.size()");
+  if (spectral) return (c->hasFilm && !c->filmTablesSpectral) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)") : HPT_OK;
   return needFilmTablesRGB(c);
 }
-extern "C" int hpt_path_trace_qmc_block_dev(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
-                                            float* sampleColorDev, uint32_t* samplePixelDev, void* stream)
+// pathTraceQmcSpectralKernel<.., SCOPE> over the traversal variants of launchSpectral
+template <int SCOPE>
+static void launchQmcSpectral(const DevScene& S, const Job& job, const QmcJob& q, int blocks, hipStream_t st, bool deep)
+{
+  const dim3 g(blocks), b(256);
+  if (S.motion) {
+    if (S.flatMode) { if (deep) pathTraceQmcSpectralKernel<true, true, false, true, SCOPE><<<g, b, 0, st>>>(S, job, q); else pathTraceQmcSpectralKernel<false, true, false, true, SCOPE><<<g, b, 0, st>>>(S, job, q); }
+    else            { if (deep) pathTraceQmcSpectralKernel<true, false, false, true, SCOPE><<<g, b, 0, st>>>(S, job, q); else pathTraceQmcSpectralKernel<false, false, false, true, SCOPE><<<g, b, 0, st>>>(S, job, q); }
+  }
+  else if (S.sweep)     pathTraceQmcSpectralKernel<false, false, true, false, SCOPE><<<g, b, 0, st>>>(S, job, q);
+  else if (S.flatMode)  { if (deep) pathTraceQmcSpectralKernel<true, true, false, false, SCOPE><<<g, b, 0, st>>>(S, job, q); else pathTraceQmcSpectralKernel<false, true, false, false, SCOPE><<<g, b, 0, st>>>(S, job, q); }
+  else                  { if (deep) pathTraceQmcSpectralKernel<true, false, false, false, SCOPE><<<g, b, 0, st>>>(S, job, q); else pathTraceQmcSpectralKernel<false, false, false, false, SCOPE><<<g, b, 0, st>>>(S, job, q); }
+}
+extern "C" int hpt_path_trace_qmc_block_dev2(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                             float* sampleColorDev, uint32_t* samplePixelDev, float* sampleWavesDev, void* stream)
 try {
   if (!c) return HPT_ERR_ARG;
-  if (int rc = qmc_check(c, channels, outDev, sampleColorDev, samplePixelDev)) return rc;
+  if (int rc = qmc_check(c, channels, outDev, sampleColorDev, samplePixelDev, sampleWavesDev)) return rc;
   (void)hipSetDevice(c->device);
   hipStream_t st = (hipStream_t)stream;
   const uint32_t samples = hpt_qmc_sample_count(pixelsNum, passNum);
@@ -2940,20 +2959,39 @@ try {
   DevScene Sq = c->S; Sq.shadeTris = nullptr;                             // every BSDF branch gathers through the index chain: the walk reports primitive ids
   const uint n = c->gensCount;
   uint32_t lay[5];
-  hpt_qmc::layout(c->S.camLensRadius > 0.0f || c->S.lensCount != 0u, false, c->S.motion != 0u, lay);          // EnableQMC
+  const bool spectral = c->S.spectralMode != 0u;                          // (qmc_check let it through: the option is on)
+  hpt_qmc::layout(c->S.camLensRadius > 0.0f || c->S.lensCount != 0u, spectral, c->S.motion != 0u, lay);       // EnableQMC
   QmcJob q; std::memset(&q, 0, sizeof(q));
   q.table = c->dQmcTable.p; q.samples = samples; q.gensCount = n;
-  q.dofDim = lay[0]; q.motionDim = lay[2]; q.matDim = lay[3]; q.lgtDim = lay[4];
-  q.sampleColor = (float4*)sampleColorDev; q.samplePixel = samplePixelDev;
+  q.dofDim = lay[0]; q.spdDim = lay[1]; q.motionDim = lay[2]; q.matDim = lay[3]; q.lgtDim = lay[4];
+  q.sampleColor = (float4*)sampleColorDev; q.samplePixel = samplePixelDev; q.sampleWaves = (float4*)sampleWavesDev;
   Job job; std::memset(&job, 0, sizeof(job));
   job.tidCount = std::min(n, samples); job.passNum = passNum; job.channels = channels; job.outColor = outDev;
   job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
-  const int blocks = (int)std::min<size_t>((size_t)gridBlocks(c, false, true), ((size_t)job.tidCount + 255) / 256);
+  int scope = 0;                                                          // spectral: the scope the scene needs, chosen as PathTraceBlock chooses it
+  if (spectral) {
+    bool heavy = c->S.lensCount != 0u || c->S.envTexId != 0xFFFFFFFFu || c->S.envCamBackId != 0xFFFFFFFFu || c->spectralHeavyMats;
+    for (const uint lg : c->hLightGeom) heavy = heavy || lg == LIGHT_GEOM_ENV;
+    scope = (heavy && c->fewMaterialTypes) ? 3 : (heavy ? 2 : (c->spectralGltfMats ? 1 : 0));
+  }
+  const int grid = !spectral ? gridBlocks(c, false, true) : c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : (scope == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES));
+  const int blocks = (int)std::min<size_t>((size_t)grid, ((size_t)job.tidCount + 255) / 256);
   HIPCHK(c, c->dQueue.alloc(1));
   HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
   job.queue = c->dQueue.p;
   const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
   const dim3 g(blocks), b(256);
+  if (spectral) {
+    return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+      c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
+      c->lastWide = (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u;
+      job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
+      if (scope == 3) launchQmcSpectral<3>(c->S, job, q, blocks, st, deep);
+      else if (scope == 2) launchQmcSpectral<2>(c->S, job, q, blocks, st, deep);
+      else if (scope == 1) launchQmcSpectral<1>(c->S, job, q, blocks, st, deep);
+      else launchQmcSpectral<0>(c->S, job, q, blocks, st, deep);
+    });
+  }
   return launchFrame(c, (size_t)blocks * 256, st, [&]() {
     c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
     c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
@@ -2967,7 +3005,10 @@ try {
     else                    { if (deep) pathTraceQmcKernel<true, false, false, false><<<g, b, 0, st>>>(Sq, job, q); else pathTraceQmcKernel<false, false, false, false><<<g, b, 0, st>>>(Sq, job, q); }
   });
 }
-catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block_dev"); }
+catch (...) { return hptGuard(c, "hpt_path_trace_qmc_block_dev2"); }
+extern "C" int hpt_path_trace_qmc_block_dev(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                            float* sampleColorDev, uint32_t* samplePixelDev, void* stream)
+{ return hpt_path_trace_qmc_block_dev2(c, pixelsNum, channels, outDev, passNum, sampleColorDev, samplePixelDev, nullptr, stream); }
 // host-pointer form: the caller's frame goes up, is added to and comes back; slots as path_trace_host fills them
 extern "C" int hpt_path_trace_qmc_block(hpt_ctx* c, uint32_t pixelsNum, uint32_t channels, float* out, uint32_t passNum)
 try {
@@ -3554,6 +3595,7 @@ try {
   else if (k == "device_build_two_level") { if (value < 0 || value > 1) return c->fail(HPT_ERR_ARG, "device_build_two_level: 0 two-level scenes are built on the host, 1 on the device when a device build is asked for"); c->deviceBuildTwoLevel = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
+  else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
   else if (k == "dbg_stack_witness") { c->stackWitness = value != 0; c->witnessWords = 0; }   // diagnostic: sentinel fill of the stacks' HBM part before every launch (hpt_get_stack_witness)

@@ -8,44 +8,14 @@
 //   * the pixel is derived from dimensions 0 and 1 of s, so many samples of many lanes land on one pixel: the film is summed with hardware
 //     float atomics (no-return global_atomic_add_f32, as the DR adjoint's gradient scatter), one per channel and sample;
 //   * optionally every sample's colour and pixel index are stored at index s: those records do not depend on the order of the atomics.
-// Every BSDF branch and the thin films (shadeVertex<.., FILM>); RGB only (the host refuses m_spectral_mode); this schedule only.
+// Every BSDF branch and the thin films (shadeVertex<.., FILM>); RGB only - m_spectral_mode runs pathTraceQmcSpectralKernel (hpt_spectral.hip)
+// when hpt_set_option("qmc_spectral", 1) asked for it and is refused otherwise; this schedule only.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 
 namespace hpt {
 
-// qmc::rndFloat (rnd_qmc.cpp:189-196). `dim` is wave-uniform, so the 31 columns are scalar loads from the 1364-byte table.
-HPT_DEV float qmcFloat(const uint* __restrict__ table, uint pos, uint dim)
-{
-  const uint* __restrict__ col = table + dim * QMC_RESOLUTION;
-  uint r = 0u;
-#pragma unroll
-  for (uint bit = 0; bit < QMC_RESOLUTION; bit++) r ^= ((pos >> bit) & 1u) ? col[bit] : 0u;
-  return (float)(r + 1u) * (1.0f / 2147483648.0f);             // uint -> float rounds to nearest; INT_SCALE = 1 / float(0x80000001) = 2^-31
-}
-
-// IntegratorQMC::GetRandomNumbersLgts / GetRandomNumbersMats (integrator_qmc.cpp:117-139): the pseudo draws are made at every bounce - the
-// lights' float4 BEFORE the selection float, the reverse of the base class - and the first bounce's .x / .y (and the light selection)
-// are then replaced by the sample's QMC dimensions, unless EnableQMC left them to the generator (dimension 0)
-struct QmcRands
-{
-  const uint* table; uint s, matDim, lgtDim;
-  HPT_DEV V4 lights(Rng& gen, uint bounce, float& rndId) const
-  {
-    V4 r = rng_float4(gen);
-    rndId = rng_float1(gen);
-    if (bounce == 0u && lgtDim != 0u) { r.x = qmcFloat(table, s, lgtDim); r.y = qmcFloat(table, s, lgtDim + 1u); rndId = qmcFloat(table, s, lgtDim + 2u); }
-    return r;
-  }
-  HPT_DEV V4 mats(Rng& gen, uint bounce) const
-  {
-    V4 r = rng_float4(gen);
-    if (bounce == 0u && matDim != 0u) { r.x = qmcFloat(table, s, matDim); r.y = qmcFloat(table, s, matDim + 1u); }
-    return r;
-  }
-  HPT_DEV float blend(Rng& gen, uint /*bounce*/, uint /*layer*/) const { return rng_float1(gen); }   // IntegratorQMC::GetRandomNumbersMatB: pseudo
-};
-
+// qmcFloat and the QmcRands policy (GetRandomNumbersLgts / Mats / MatB) live in hpt_decl.h: the spectral form of this kernel shares them
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q)
 {

@@ -367,9 +367,12 @@ HPT_DEV SpecSample materialSampleSpec(const DevScene& S, const MaterialRec& m, V
 // (integrator_pt.cpp:238-548 with m_spectral_mode != 0), shared by the one-thread-per-pixel kernel below and by the block-local schedule
 // (pathTraceBlockSpectralKernel). As shadeVertex for the RGB kernels: the light sample's BSDF is evaluated before the shadow ray is traced,
 // the caller traces it (wantShadow) and adds `contrib` when it comes back unoccluded. A miss only sets the OUT_OF_SCENE flags.
-template <int SCOPE, bool MOTION>
+// RANDS: where the light, material and blend numbers come from, as in shadeVertex (hpt_shade.h: PseudoRands - the generator in the base
+// class's order; hpt_decl.h: QmcRands - pathTraceQmcSpectralKernel below).
+template <int SCOPE, bool MOTION, class RANDS = PseudoRands>
 HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3& rdir, const V4 waves, V4& accum, V4& thr, float& misPdf, float& misIor, uint& flags,
-                             const uint bounce, Rng& gen, const bool naive, bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V4& contrib, const float pathTime)
+                             const uint bounce, Rng& gen, const bool naive, bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V4& contrib, const float pathTime,
+                             const RANDS rands_ = RANDS())
 {
   if (hit.inst == 0xFFFFFFFFu) {
     flags |= (bounce == 0) ? (RAY_FLAG_PRIME_RAY_MISS | RAY_FLAG_IS_DEAD | RAY_FLAG_OUT_OF_SCENE) : (RAY_FLAG_IS_DEAD | RAY_FLAG_OUT_OF_SCENE);
@@ -409,8 +412,8 @@ HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3&
     // -- kernel_SampleLightSource (integrator_pt.cpp:350-424) --
     V4 shade = v4s(0.0f);
     if (!naive) {
-      const float rndId = rng_float1(gen);
-      const V4 r4 = rng_float4(gen);
+      float rndId;
+      const V4 r4 = rands_.lights(gen, bounce, rndId);                  // GetRandomNumbersLgts
       const int nLights = (int)S.numLights;
       const int lightId = min((int)floorf(rndId * float(nLights)), nLights - 1);
       if (lightId >= 0 && mtype != MAT_TYPE_LIGHT_SOURCE) {
@@ -464,10 +467,11 @@ HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3&
       // blend descent (BlendSampleAndEval, integrator_pt_mat.cpp:23-54, 123-130): one generator step per layer BEFORE the float4
       const MaterialRec* lm = &m; uint lt = mtype; V4 ltexColor = texColor; float pdf0 = 1.0f;
       if (SCOPE >= 2 && mtype == MAT_TYPE_BLEND) {
+        uint layer = 0;
         while (lt == MAT_TYPE_BLEND) {
           const V4 wd = texSample(S.textures, lm->texid[0], mulRows2x4(lm->row0[0], lm->row1[0], uv));
           const float weight = lm->data[0] * wd.x;
-          const float select = rng_float1(gen);                        // GetRandomNumbersMatB (integrator_pt.cpp:37)
+          const float select = rands_.blend(gen, bounce, layer++);     // GetRandomNumbersMatB (integrator_pt.cpp:37)
           if (select < weight) { pdf0 *= weight; lm = &S.materials[lm->datai[1]]; }
           else                 { pdf0 *= 1.0f - weight; lm = &S.materials[lm->datai[0]]; }
           lt = lm->mtype;
@@ -477,7 +481,7 @@ HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3&
       const MaterialRec& ml = *lm;
       const bool leafBump = SCOPE >= 2 && ml.texid[1] != 0xFFFFFFFFu;                // the leaf's normal map bends the shading normal (:131-139)
       const V3 sNorm = leafBump ? bumpNormal(S, ml, hitNorm, hitTang, uv) : hitNorm;
-      const V4 rands = rng_float4(gen);                                // GetRandomNumbersMats
+      const V4 rands = rands_.mats(gen, bounce);                       // GetRandomNumbersMats
       SpecSample ms = materialSampleSpec<SCOPE>(S, ml, waves, rands, vdir, sNorm, hitNorm, ltexColor, (flags & 0xFF000000u) | matId, misIor, uv, pdf0);
       if (lt == MAT_TYPE_DIELECTRIC || lt == MAT_TYPE_THIN_FILM || lt == MAT_TYPE_GLASS) misIor = ms.ior;
       if (leafBump) {                                                  // the caller multiplies by the cosine to the geometric normal (:298-303)
@@ -604,6 +608,147 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
     else if (job.channels <= 4) { float* o = job.outColor + (size_t)pixel * job.channels; o[0] = pix[0]; o[1] = pix[1]; o[2] = pix[2]; if (inRays && job.channels == 4) o[3] = pix[3]; }
     job.gens[tid] = gen;
   }
+}
+
+// ---- IntegratorQMC::PathTraceBlock under m_spectral_mode (mlt/integrator_qmc.cpp; `hydra --qmc --spectral`) ---------------------------------------
+// The sample loop of pathTraceQmcKernel (hpt_qmc.hip) around the path state of the kernel above: a lane owns a generator slot g and runs samples
+// g, g + N, g + 2N, ... in order; slot, sample and pixel index are cold state in LDS; one queue atomic per wave. Order of a sample's draws
+// (IntegratorQMC::SampleCameraRay, :204-209): the lens float4 (pseudo, .xy / .zw overwritten), the time (MOTION; pseudo only when its dimension
+// is 0), then the wavelength sample - dimension q.spdDim, which every spectral layout of EnableQMC sets, else a pseudo float. Each vertex draws
+// through QmcRands. Contribution (kernel_ContributeToImage, :218-282): one more lens float4, SpectralCamRespoceToRGB instead of the camRespoceRGB
+// product, the exposure, then float atomics - many samples of many lanes land on a pixel, and with channels > 4 on a pixel's wavelength layers:
+// all four wavelengths scatter exposure * accum[i] into layer min(int(channels * t_i), channels - 1), WAVES_DIVERGED or not, as the reference does.
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE_>
+__global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceQmcSpectralKernel(const DevScene S, const Job job, const QmcJob q)
+{
+  constexpr int SCOPE = SCOPE_ == 3 ? 2 : SCOPE_;
+  __shared__ uint stackMem[LDS_STACK * 256];
+  __shared__ uint coldU[3 * 256];
+  const uint glane = blockIdx.x * 256u + threadIdx.x;
+  TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = job.stackOverflow + glane; stk.ovfStride = job.gridLanes;
+  TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
+#define SLOT    coldU[0 * 256 + threadIdx.x]
+#define SAMPLE  coldU[1 * 256 + threadIdx.x]
+#define PIXEL   coldU[2 * 256 + threadIdx.x]
+  bool haveSlot = false, more = false, alive = false, drained = false;     // more: the slot has a sample left to start
+  uint bounce = 0, flags = 0;
+  Rng  gen; gen.sx = gen.sy = 0;
+  V3   rpos = v3(0, 0, 0), rdir = v3(0, 0, 1);
+  V4   waves = v4s(0.0f), accum = v4s(0.0f), thr = v4s(1.0f);
+  float misPdf = 1.0f, misIor = 1.0f;
+  float pathTime = 0.0f;
+  const uint maxBounce = S.traceDepth;
+  const bool dof = S.camLensRadius > 0.0f || S.lensCount != 0u;
+  const size_t layerStride = (size_t)(S.winWidth * S.winHeight);
+
+  while (true) {
+    // ---- (1) a slot that has run its last sample stores its generator ------------------------------------------------------------------------
+    if (!alive && haveSlot && !more) { job.gens[SLOT] = gen; haveSlot = false; }
+    // ---- (2) work queue over the generator slots 0 .. min(N, S): one atomic per wave -----------------------------------------------------------
+    {
+      const bool need = !alive && !haveSlot && !drained;
+      const unsigned long long mask = __ballot(need);
+      if (mask != 0ull) {
+        uint base = 0;
+        if (need && mbcnt64(mask) == 0u) base = atomicAdd(job.queue, (uint)__popcll(mask));
+        base = __shfl(base, (int)(__ffsll((long long)mask) - 1));
+        if (need) {
+          const uint g = base + mbcnt64(mask);
+          if (g < job.tidCount) { gen = job.gens[g]; SLOT = g; SAMPLE = g; haveSlot = true; more = true; }
+          else drained = true;
+        }
+      }
+    }
+    // ---- (3) regenerate: the slot's next sample (kernel_InitEyeRay2 with IntegratorQMC::SampleCameraRay) ----------------------------------------
+    if (!alive && haveSlot) {
+      const uint s = SAMPLE;
+      accum = v4s(0.0f); thr = v4s(1.0f); flags = 0; bounce = 0;
+      misPdf = 1.0f; misIor = 1.0f;
+      V4 lens = rng_float4(gen);                                           // GetRandomNumbersLens: the pseudo float4 first, then the overwrites
+      lens.x = qmcFloat(q.table, s, 0u);
+      lens.y = qmcFloat(q.table, s, 1u);
+      if (dof && q.dofDim != 0u) { lens.z = qmcFloat(q.table, s, 2u); lens.w = qmcFloat(q.table, s, 3u); }
+      cameraRayAt<(SCOPE >= 2)>(S, lens.x, lens.y, lens, rpos, rdir);
+      uint x = (uint)(lens.x * float(S.winWidth)), y = (uint)(lens.y * float(S.winHeight));
+      if (x >= (uint)(S.winWidth - 1)) x = (uint)(S.winWidth - 1);
+      if (y >= (uint)(S.winHeight - 1)) y = (uint)(S.winHeight - 1);
+      PIXEL = y * (uint)S.winWidth + x;
+      if (MOTION) pathTime = (q.motionDim != 0u) ? qmcFloat(q.table, s, q.motionDim) : rng_float1(gen);   // GetRandomNumbersTime, before the wavelength
+      const float waveSam = (q.spdDim != 0u) ? qmcFloat(q.table, s, q.spdDim) : rng_float1(gen);          // GetRandomNumbersSpec: no pseudo draw when the dimension is set
+      waves = sampleWavelengths(waveSam, LAMBDA_MIN, LAMBDA_MAX);
+      alive = true;
+    }
+    if (!__any(alive)) break;
+
+    // ---- (4) - (6) closest hit, vertex, shadow ray ------------------------------------------------------------------------------------------------
+    if (maxBounce != 0u) {                                                   // (depth 0: the path is its camera ray and ends below)
+      HitRec hit; hit.inst = 0xFFFFFFFFu; hit.prim = 0; hit.t = 0; hit.u = hit.v = 0;
+      if (alive) traceAny<false, false, DEEP, FLAT, MOTION, SWEEP>(S, rpos, rdir, 0.0f, HPT_FLT_MAX, hit, stk, st, pathTime);
+      bool wantShadow = false;
+      V3 shPos = v3(0, 0, 0), shDir = v3(0, 0, 1); float shFar = 0.0f;
+      V4 contrib = v4s(0.0f);
+      if (alive) {
+        QmcRands rs; rs.table = q.table; rs.s = SAMPLE; rs.matDim = q.matDim; rs.lgtDim = q.lgtDim;
+        shadeVertexSpec<SCOPE, MOTION, QmcRands>(S, hit, rpos, rdir, waves, accum, thr, misPdf, misIor, flags, bounce, gen, false, wantShadow, shPos, shDir, shFar, contrib, pathTime, rs);
+      }
+      if (wantShadow) {
+        HitRec sh;
+        const bool occluded = traceAny<true, false, DEEP, FLAT, MOTION, SWEEP>(S, shPos, shDir, 0.0f, shFar, sh, stk, st, pathTime);
+        if (!occluded) accum = accum + contrib;
+      }
+      bounce++;
+    }
+    // ---- (7) end of path: kernel_HitEnvironment, IntegratorQMC::kernel_ContributeToImage ---------------------------------------------------------
+    if (alive && ((flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= maxBounce)) {
+      const uint s = SAMPLE;
+      if ((flags & RAY_FLAG_OUT_OF_SCENE) != 0) {
+        V4 env = ld4(S.envColor);
+        if (SCOPE >= 2) {                                                    // the back plate reads m_packedXY[tid], tid = the sample index; past the vector's end: 0
+          const uint backXY = (S.envCamBackId != 0xFFFFFFFFu && s < job.packedCount) ? job.packedXY[s] : 0u;
+          env = environmentRadianceSpec(S, rdir, waves, misPdf, flags, backXY);
+        }
+        else if (S.envSpecId != 0xFFFFFFFFu) env = sampleUniformSpectrum(S.specValues, S.specOffsetSz[2u * S.envSpecId], waves) * (S.envSpecMult / 106.856895f);
+        if (S.integratorType == INTEGRATOR_STUPID_PT) accum = thr * env; else accum = accum + thr * env;
+      }
+      (void)rng_float4(gen);                                                 // GetRandomNumbersLens once more before *gen is stored (integrator_qmc.cpp:225-226)
+      const uint pixel = PIXEL;
+      float4 rec;
+      if (job.channels > 4u) {                                               // the wavelength layers: all four wavelengths, diverged or not (:268-280)
+        const V4 color = accum * S.exposureMult;
+        rec = make_float4(color.x, color.y, color.z, color.w);
+        if (job.outColor != nullptr) {
+          for (int i = 0; i < 4; i++) {
+            const float t = (comp(waves, i) - LAMBDA_MIN) / (LAMBDA_MAX - LAMBDA_MIN);
+            const int channelId = min(int(float(job.channels) * t), int(job.channels) - 1);
+            atomicAdd(job.outColor + (size_t)channelId * layerStride + pixel, comp(color, i));
+          }
+        }
+      } else {
+        const V3 c = spectralCamResponseToRGB(S, accum, waves, flags);
+        const V3 rgb = v3(S.exposureMult * c.x, S.exposureMult * c.y, S.exposureMult * c.z);
+        const float mono = 0.2126f * rgb.x + 0.7152f * rgb.y + 0.0722f * rgb.z;
+        rec = (job.channels == 1u) ? make_float4(mono, 0.0f, 0.0f, 0.0f) : make_float4(rgb.x, rgb.y, rgb.z, 0.0f);
+        if (job.outColor != nullptr) {
+          if (job.channels == 1u) atomicAdd(job.outColor + pixel, mono);
+          else {
+            float* o = job.outColor + (size_t)pixel * job.channels;
+            atomicAdd(o + 0, rgb.x); atomicAdd(o + 1, rgb.y); atomicAdd(o + 2, rgb.z);
+          }
+        }
+      }
+      if (q.sampleColor != nullptr) {
+        q.sampleColor[s] = rec;
+        q.samplePixel[s] = pixel;
+        if (q.sampleWaves != nullptr) q.sampleWaves[s] = make_float4(waves.x, waves.y, waves.z, waves.w);
+      }
+      more = (q.samples - 1u - s) >= q.gensCount;                            // s + N < S without wrapping at 2^32
+      if (more) SAMPLE = s + q.gensCount;
+      alive = false;
+    }
+  }
+#undef SLOT
+#undef SAMPLE
+#undef PIXEL
 }
 
 // ---- spectral rendering under the block-local schedule (hpt_block.hip's structure on four wavelengths) ------------------------------------------
@@ -871,7 +1016,8 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   if (qShad) stP(&rayQ[ks], s | 0x80000000u);
 }
 
-// one translation unit per scope (-DHPT_SPEC_INST=1 / 2 / 3 / 4: scope 0 / 1 / 2 / 2 at 4 waves; 0: all), see __graft_entry__.build
+// one translation unit per scope (-DHPT_SPEC_INST=1 / 2 / 3 / 4: scope 0 / 1 / 2 / 2 at 4 waves; 5 / 6 / 7 / 8: the QMC kernel of those scopes;
+// 0: all), see __graft_entry__.build
 #ifndef HPT_SPEC_INST
 #define HPT_SPEC_INST 0
 #endif
@@ -892,6 +1038,28 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   template __global__ void pathTraceSpectralKernel<true,  false, false, true,  SCOPE>(const DevScene, const Job); \
   template __global__ void pathTraceSpectralKernel<false, true,  false, true,  SCOPE>(const DevScene, const Job); \
   template __global__ void pathTraceSpectralKernel<true,  true,  false, true,  SCOPE>(const DevScene, const Job);
+#define HPT_SPEC_QMC(SCOPE)   /* the traversal variants of HPT_SPEC: DEEP x FLAT, SWEEP, MOTION */ \
+  template __global__ void pathTraceQmcSpectralKernel<false, false, false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<true,  false, false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<false, true,  false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<true,  true,  false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<false, false, true,  false, SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<false, false, false, true,  SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<true,  false, false, true,  SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<false, true,  false, true,  SCOPE>(const DevScene, const Job, const QmcJob); \
+  template __global__ void pathTraceQmcSpectralKernel<true,  true,  false, true,  SCOPE>(const DevScene, const Job, const QmcJob);
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 5
+HPT_SPEC_QMC(0)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 6
+HPT_SPEC_QMC(1)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 7
+HPT_SPEC_QMC(2)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 8
+HPT_SPEC_QMC(3)
+#endif
 #if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 1
 HPT_SPEC(0)
 HPT_SPEC_BLOCK(0)

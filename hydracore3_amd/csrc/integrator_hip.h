@@ -260,11 +260,14 @@ protected:
 
 // ---- IntegratorDR-shaped front end (diff_render/integrator_dr.h:27-136) -------------------------------------------------------
 // IntegratorQMC (mlt/integrator_qmc.h): the subclass whose PathTraceBlock runs the Niederreiter sequence over pixels x passes samples. `tid`
-// is the reference's pixelsNum; the sampler's table lives with the context (hpt_qmc_table gives a copy).
+// is the reference's pixelsNum; the sampler's table lives with the context (hpt_qmc_table gives a copy). m_spectral_mode (`hydra --qmc
+// --spectral`) is refused by the C entry unless EnableSpectralQMC(true) set the context's "qmc_spectral" option; channels above 4 are then the
+// wavelength layers, summed with float atomics like the rest of the QMC film.
 class IntegratorQMCHIP : public IntegratorHIP
 {
 public:
   using IntegratorHIP::IntegratorHIP;
+  void EnableSpectralQMC(bool a_on) { if (m_ctx) report(hpt_set_option(m_ctx, "qmc_spectral", a_on ? 1 : 0), "EnableSpectralQMC"); }
   void PathTraceBlock(uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t a_passNum) override
   { if (m_ctx) report(hpt_path_trace_qmc_block(m_ctx, pixelsNum, channels, out_color, a_passNum), "PathTraceBlockQMC"); }
 };

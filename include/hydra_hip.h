@@ -317,9 +317,16 @@ int  hpt_qmc_layout(int dof, int spectral, int motion, uint32_t out[5]);
  * pixel is x = min(uint(u0 * winWidth), winWidth - 1), y likewise from u1, and exposure * (colour * camRespoceRGB) is ADDED to that pixel
  * (channels 3 / 4: rgb; channels 1: the luma 0.2126 / 0.7152 / 0.0722). out_color = winWidth * winHeight * channels floats in host memory.
  * Samples s, s + N, s + 2N ... run in that order on generator s % N (what the reference computes on one thread: DESIGN.md 7); the sum
- * into a pixel is made with float atomics, so the frame is reproducible to rounding only. HPT_ERR_UNSUPPORTED with m_spectral_mode on and
- * for channels 2 or above 4; HPT_ERR_ARG for a null context or buffer and before InitRandomGens (N = 0); HPT_ERR_STATE before
- * CommitDeviceData, UpdateMembersPlainData or PackXYBlock. Megakernel schedule only. hpt_get_execution_time("PathTraceBlockQMC") gives its four slots. */
+ * into a pixel is made with float atomics, so the frame is reproducible to rounding only. HPT_ERR_UNSUPPORTED for channels 2 and,
+ * unless the option "qmc_spectral" is set (below), with m_spectral_mode on and for channels above 4; HPT_ERR_ARG for a null context or buffer and before InitRandomGens (N = 0); HPT_ERR_STATE before
+ * CommitDeviceData, UpdateMembersPlainData or PackXYBlock. Megakernel schedule only. hpt_get_execution_time("PathTraceBlockQMC") gives its four slots.
+ * Spectral QMC (`hydra --qmc --spectral`) is opt-in: after hpt_set_option(ctx, "qmc_spectral", 1) a context with m_spectral_mode on is served
+ * instead of refused (with m_spectral_mode off nothing changes). A sample then carries four wavelengths, SampleWavelengths of dimension
+ * m_qmcSpdDim (hpt_qmc_layout; taken after the time sample), and SpectralCamRespoceToRGB(accumColor, wavelengths, rayFlags) takes the place of
+ * the camRespoceRGB product: exposure * rgb is added for channels 3 / 4, its luma for channels 1. channels above 4 are wavelength layers of
+ * winWidth * winHeight floats each: every one of the four wavelengths adds exposure * accumColor[i] to pixel y * winWidth + x of layer
+ * min(int(channels * (lambda_i - LAMBDA_MIN) / (LAMBDA_MAX - LAMBDA_MIN)), channels - 1), with float atomics too. channels 2 stays
+ * HPT_ERR_UNSUPPORTED; thin films whose tables are not of spectral size are HPT_ERR_ARG, as in PathTraceBlock. */
 int  hpt_path_trace_qmc_block(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t passNum);
 /* The same on device memory, asynchronous on stream. sampleColorDev (4 floats per sample) and samplePixelDev (one uint32 per sample),
  * either both NULL or both S elements long, receive for sample index s the colour as it was added (rgb and 0; channels 1: the luma and three
@@ -327,6 +334,11 @@ int  hpt_path_trace_qmc_block(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channel
  * be NULL when the records are asked for; all three NULL is HPT_ERR_ARG. */
 int  hpt_path_trace_qmc_block_dev(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
                                   float* sampleColorDev, uint32_t* samplePixelDev, void* stream);
+/* The same with a third record: sampleWavesDev (4 floats per sample; NULL, or S elements long together with the other two records - alone it is
+ * HPT_ERR_ARG) receives the sample's four wavelengths in spectral QMC (untouched in RGB). With channels above 4 the colour record is the four
+ * exposure * accumColor[i], which the wavelengths place in their layers. hpt_path_trace_qmc_block_dev forwards here with NULL. */
+int  hpt_path_trace_qmc_block_dev2(hpt_ctx* ctx, uint32_t pixelsNum, uint32_t channels, float* outDev, uint32_t passNum,
+                                   float* sampleColorDev, uint32_t* samplePixelDev, float* sampleWavesDev, void* stream);
 /* S of the two calls above for (pixelsNum, passNum): min(2^32 - 1, pixelsNum * passNum). Host code; no context. */
 uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum);
 
