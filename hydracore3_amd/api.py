@@ -113,6 +113,7 @@ ABI = {
     "hpt_path_trace_qmc_block_dev2": (_i, [_vp, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _vp]),
     "hpt_kmlt_state_size": (_u32, [_u32]),
     "hpt_path_trace_pss_dev": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp]),
+    "hpt_path_trace_pss_dev2": (_i, [_vp, _vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "hpt_kmlt_chain_count": (_i, [_vp, _u32, _u32, C.POINTER(_u32), C.POINTER(_u32)]),
     "hpt_path_trace_kmlt_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
     "hpt_path_trace_kmlt_block_dev": (_i, [_vp, _u32, _u32, _vp, _u32, _i, _vp, _vp, _vp]),
@@ -440,25 +441,35 @@ class HipIntegrator:
                 self.L.hpt_device_free(self.h, p)
         return dev, free_all
 
-    def path_trace_pss(self, x):
+    def path_trace_pss(self, x, waves=False, accum=False):
         """IntegratorKMLT::PathTraceF for the vectors x, float32 [n, stride] with stride >= kmlt_state_size(traceDepth): returns
-        (colours float32 [n, 4], pixel indices uint32 [n]). Every random number of path i is read from x[i]; m_randomGens is not touched."""
+        (colours float32 [n, 4], pixel indices uint32 [n]). Every random number of path i is read from x[i]; m_randomGens is not touched.
+        Spectral MLT (set_option("kmlt_spectral", 1) on a spectral scene): waves=True appends the paths' wavelengths [n, 4], accum=True their
+        raw exposure * accumColor [n, 4] (hpt_path_trace_pss_dev2), in that order."""
         x = np.ascontiguousarray(x, np.float32)
         assert x.ndim == 2
         n, stride = x.shape
         col, pix = np.zeros((n, 4), np.float32), np.zeros(n, np.uint32)
+        extra = [np.zeros((n, 4), np.float32) if want else None for want in (waves, accum)]
         dev, free_all = self._dev_scope()
         try:
             d_x, d_col, d_pix = dev(x.nbytes), dev(col.nbytes), dev(pix.nbytes)
+            d_extra = [dev(e.nbytes) if e is not None else None for e in extra]
             if n:
                 self._chk(self.L.hpt_device_copy(self.h, d_x, x.ctypes.data, x.nbytes, 1))
-            self._chk(self.L.hpt_path_trace_pss_dev(self.h, d_x, n, stride, d_col, d_pix, None))
+            if waves or accum:
+                self._chk(self.L.hpt_path_trace_pss_dev2(self.h, d_x, n, stride, d_col, d_pix, d_extra[0], d_extra[1], None))
+            else:
+                self._chk(self.L.hpt_path_trace_pss_dev(self.h, d_x, n, stride, d_col, d_pix, None))
             if n:
                 self._chk(self.L.hpt_device_copy(self.h, col.ctypes.data, d_col, col.nbytes, 2))
                 self._chk(self.L.hpt_device_copy(self.h, pix.ctypes.data, d_pix, pix.nbytes, 2))
+                for e, d in zip(extra, d_extra):
+                    if e is not None:
+                        self._chk(self.L.hpt_device_copy(self.h, e.ctypes.data, d, e.nbytes, 2))
         finally:
             free_all()
-        return col, pix
+        return (col, pix) + tuple(e for e in extra if e is not None)
 
     def PathTraceBlockKMLT(self, pixelsNum, channels, out_color, a_passNum):
         """IntegratorKMLT::PathTraceBlock(pixelsNum, channels, out_color, a_passNum): Markov chains in primary sample space, then the brightness
@@ -743,6 +754,7 @@ class HipIntegrator:
         self._chk(self.L.hpt_set_option(self.h, name.encode(), value))
         if name == "qmc_spectral":
             self._qmc_spectral = bool(value)     # PathTraceBlockQMC then takes frames of more than 4 channels
+        # ("kmlt_spectral" needs no state here: path_trace_pss / render_kmlt pass through, and the library refuses what the option does not allow)
 
     def accel_info(self):
         out = (C.c_float * 4)()

@@ -298,6 +298,29 @@ template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceQmcSpectralKernel(const DevScene S, const Job job, const QmcJob q);
 
 // ---- IntegratorKMLT (mlt/integrator_kmlt.cpp; hpt_kmlt.hip) ------------------------------------------------------------------------------
+static const uint KMLT_BOUNCE_START = 6u, KMLT_LGHT_ID = 0u, KMLT_MATS_ID = 4u, KMLT_BLND_ID = 8u, KMLT_PER_BOUNCE = 10u;   // integrator_kmlt.cpp:33-37
+// IntegratorKMLT::GetRandomNumbers* (:87-151): slot i of the lane's vector is x[i * stride]. A blend layer of 2 or more reads into the next
+// bounce's light numbers, as the reference indexes it; a slot past the vector's end reads 0. Slots 0 - 3 are the film and lens
+// point, 4 the wavelength sample (GetRandomNumbersSpec; read under m_spectral_mode only), 5 the time.
+// The policy of shadeVertex (hpt_kmlt.hip: pssEval) and of shadeVertexSpec (hpt_spectral.hip: pssEvalSpec).
+struct PssRands
+{
+  const float* x; size_t stride; uint n;
+  HPT_DEV float at(uint i) const { return i < n ? x[(size_t)i * stride] : 0.0f; }
+  HPT_DEV V4 lights(Rng&, uint bounce, float& rndId) const
+  {
+    const uint b = KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_LGHT_ID;
+    const V4 r = v4(at(b), at(b + 1u), at(b + 2u), at(b + 3u));
+    rndId = r.w;
+    return r;
+  }
+  HPT_DEV V4 mats(Rng&, uint bounce) const
+  {
+    const uint b = KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_MATS_ID;
+    return v4(at(b), at(b + 1u), at(b + 2u), at(b + 3u));
+  }
+  HPT_DEV float blend(Rng&, uint bounce, uint layer) const { return at(KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_BLND_ID + layer); }
+};
 // PathTraceF over caller-supplied number vectors: lane i < n reads vector i at x[i * vecStride + slot] and writes color[i], pixel[i]
 struct PssJob
 {
@@ -305,9 +328,13 @@ struct PssJob
   float4* color; uint* pixel;
   const uint* packedXY; uint packedCount;    // the camera back plate reads m_packedXY[tid], tid = the lane (past the vector's end: 0)
   uint* stackOverflow; uint gridLanes;
+  float4* waves; float4* accum;              // spectral pass only, each may be null: the path's four wavelengths, its raw exposure * accumColor[i]
 };
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTracePssKernel(const DevScene S, const PssJob job);
+// the same pass under m_spectral_mode (hpt_spectral.hip: pssEvalSpec); SCOPE and its launch bounds as pathTraceSpectralKernel
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
+__global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTracePssSpectralKernel(const DevScene S, const PssJob job);
 // the Markov chains: lane c < chains runs chain c for `steps` steps; cur / prop: the chain's current vector and its proposal, [slot][chain]
 struct KmltJob
 {
@@ -324,6 +351,9 @@ struct KmltJob
 };
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) kmltChainKernel(const DevScene S, const KmltJob job);
+// the same chains (hpt_kmlt_chain.h: kmltChainBody) around pssEvalSpec
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
+__global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) kmltChainSpectralKernel(const DevScene S, const KmltJob job);
 // stats4 = { avgBrightness, actualBrightness, acceptance rate, normConst } from the per-chain sums and the frame (one block); then frame *= normConst
 __global__ void __launch_bounds__(256) kmltStatsKernel(const float4* frame, uint pixelsNum, uint passNum, uint chains, const double* accumBrightness,
                                                        const uint* largeSteps, const uint* accept, double* stats4);

@@ -172,6 +172,7 @@ struct hpt_ctx
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
   bool qmcSpectral = false;                              // hpt_set_option("qmc_spectral", 1): PathTraceBlockQMC serves m_spectral_mode (pathTraceQmcSpectralKernel) instead of refusing it
+  bool kmltSpectral = false;                             // hpt_set_option("kmlt_spectral", 1): PathTraceBlockKMLT and the PSS pass serve m_spectral_mode (kmltChainSpectralKernel / pathTracePssSpectralKernel)
   uint kmltChains = 0;                                   // hpt_set_option("kmlt_chains", n): 0 = one chain per lane of the resident grid
   uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
@@ -2911,6 +2912,20 @@ static int needPacked(hpt_ctx* c, const std::string& who)
 { return c->packedCount != (uint)(c->S.winWidth * c->S.winHeight) ? c->fail(HPT_ERR_STATE, who + " before PackXYBlock") : HPT_OK; }
 static int needFilmTablesRGB(hpt_ctx* c)
 { return (c->hasFilm && !c->filmTablesRGB) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films holds no RGB table for a film (LoadScene precomputes every film in RGB mode, sized by its thickness map)") : HPT_OK; }
+static int needFilmTablesSpectral(hpt_ctx* c)
+{ return (c->hasFilm && !c->filmTablesSpectral) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)") : HPT_OK; }
+// The scope of the spectral kernels the scene needs, chosen as PathTraceBlock chooses it (0 .. 3: hpt_decl.h), and the resident grid of a
+// persistent spectral kernel of that scope: what spectral QMC and spectral MLT both launch with
+static int spectralScope(const hpt_ctx* c)
+{
+  bool heavy = c->S.lensCount != 0u || c->S.envTexId != 0xFFFFFFFFu || c->S.envCamBackId != 0xFFFFFFFFu || c->spectralHeavyMats;
+  for (const uint lg : c->hLightGeom) heavy = heavy || lg == LIGHT_GEOM_ENV;
+  return (heavy && c->fewMaterialTypes) ? 3 : (heavy ? 2 : (c->spectralGltfMats ? 1 : 0));
+}
+static int spectralGridBlocks(const hpt_ctx* c, int scope)
+{ return c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : (scope == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES)); }
+static uint spectralLastWide(const hpt_ctx* c)
+{ return (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u; }
 static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void* sampleColor, const void* samplePixel, const void* sampleWaves = nullptr)
 {
   const std::string who("PathTraceBlockQMC");
@@ -2926,7 +2941,7 @@ static int qmc_check(hpt_ctx* c, uint32_t channels, const void* out, const void*
   if (channels == 2u || channels == 0u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockQMC: a framebuffer of 1, 3 or 4 channels (three components are written per pixel)");
   if (int rc = needPacked(c, who)) return rc;
   if (c->gensCount == 0u) return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC before InitRandomGens: sample s runs on generator s % m_randomGens.size()");
-  if (spectral) return (c->hasFilm && !c->filmTablesSpectral) ? c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)") : HPT_OK;
+  if (spectral) return needFilmTablesSpectral(c);
   return needFilmTablesRGB(c);
 }
 // pathTraceQmcSpectralKernel<.., SCOPE> over the traversal variants of launchSpectral
@@ -2968,13 +2983,8 @@ try {
   Job job; std::memset(&job, 0, sizeof(job));
   job.tidCount = std::min(n, samples); job.passNum = passNum; job.channels = channels; job.outColor = outDev;
   job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
-  int scope = 0;                                                          // spectral: the scope the scene needs, chosen as PathTraceBlock chooses it
-  if (spectral) {
-    bool heavy = c->S.lensCount != 0u || c->S.envTexId != 0xFFFFFFFFu || c->S.envCamBackId != 0xFFFFFFFFu || c->spectralHeavyMats;
-    for (const uint lg : c->hLightGeom) heavy = heavy || lg == LIGHT_GEOM_ENV;
-    scope = (heavy && c->fewMaterialTypes) ? 3 : (heavy ? 2 : (c->spectralGltfMats ? 1 : 0));
-  }
-  const int grid = !spectral ? gridBlocks(c, false, true) : c->numCUs * (c->blocksPerCU > 0 ? c->blocksPerCU : (scope == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES));
+  const int scope = spectral ? spectralScope(c) : 0;
+  const int grid = !spectral ? gridBlocks(c, false, true) : spectralGridBlocks(c, scope);
   const int blocks = (int)std::min<size_t>((size_t)grid, ((size_t)job.tidCount + 255) / 256);
   HIPCHK(c, c->dQueue.alloc(1));
   HIPCHK(c, hipMemsetAsync(c->dQueue.p, 0, 4, st));
@@ -2984,7 +2994,7 @@ try {
   if (spectral) {
     return launchFrame(c, (size_t)blocks * 256, st, [&]() {
       c->lastSchedule = 1; c->lastShadeRecords = 0u; c->lastDeep = deep ? 1u : 0u;
-      c->lastWide = (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u;
+      c->lastWide = spectralLastWide(c);
       job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)blocks * 256u;
       if (scope == 3) launchQmcSpectral<3>(c->S, job, q, blocks, st, deep);
       else if (scope == 2) launchQmcSpectral<2>(c->S, job, q, blocks, st, deep);
@@ -3035,9 +3045,19 @@ static int kmlt_check(hpt_ctx* c, const char* who)
 {
   const std::string w(who);
   if (int rc = needCommitted(c, w)) return rc;
-  if (int rc = refuseSpectral(c, w, "spectral MLT stays in the reference")) return rc;
+  const bool spectral = c->kmltSpectral && c->S.spectralMode != 0u;       // hpt_set_option("kmlt_spectral", 1): the spectral MLT kernels
+  if (!spectral) { if (int rc = refuseSpectral(c, w, "spectral MLT is opt-in: hpt_set_option(\"kmlt_spectral\", 1) turns it on")) return rc; }
   if (int rc = needPacked(c, w)) return rc;
-  return needFilmTablesRGB(c);
+  return spectral ? needFilmTablesSpectral(c) : needFilmTablesRGB(c);
+}
+// f gets the spectral scope (0 .. 3) as a compile-time constant
+template <class F>
+static void spectralScopeDispatch(int scope, F f)
+{
+  if (scope == 3) f(std::integral_constant<int, 3>());
+  else if (scope == 2) f(std::integral_constant<int, 2>());
+  else if (scope == 1) f(std::integral_constant<int, 1>());
+  else f(std::integral_constant<int, 0>());
 }
 // the traversal variants pathTraceQmcKernel is dispatched over; f gets (DEEP, FLAT, MOTION, SWEEP) as compile-time constants
 template <class F>
@@ -3058,11 +3078,14 @@ static void kmltNoteLaunch(hpt_ctx* c, bool deep)
   c->lastWide = (c->S.motion == 0u && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
 }
 
-extern "C" int hpt_path_trace_pss_dev(hpt_ctx* c, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev, void* stream)
+extern "C" int hpt_path_trace_pss_dev2(hpt_ctx* c, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev,
+                                       float* waves4fDev, float* accum4fDev, void* stream)
 try {
   if (!c) return HPT_ERR_ARG;
   if (!xDev || !color4fDev || !pixelDev) return c->fail(HPT_ERR_ARG, "PathTracePSS: null pointer (the vectors, the colours and the pixel indices are all needed)");
   if (int rc = kmlt_check(c, "PathTracePSS")) return rc;
+  const bool spectral = c->S.spectralMode != 0u;                          // (kmlt_check let it through: the option is on)
+  if (!spectral && (waves4fDev || accum4fDev)) return c->fail(HPT_ERR_ARG, "PathTracePSS: the wavelength and raw-radiance records exist under m_spectral_mode only (an RGB path has no wavelengths)");
   const uint32_t stateSize = hpt_kmlt_state_size(c->S.traceDepth);
   if (strideFloats < stateSize) return c->fail(HPT_ERR_ARG, "PathTracePSS: strideFloats is below hpt_kmlt_state_size(traceDepth) = " + std::to_string(stateSize));
   (void)hipSetDevice(c->device);
@@ -3075,13 +3098,26 @@ try {
   const uint blocks = (uint)(((size_t)n + 255) / 256);
   const bool deep = megaStackNeeded(c) > (uint)LDS_STACK;
   const dim3 g(blocks), b(256);
+  if (spectral) {
+    job.waves = (float4*)waves4fDev; job.accum = (float4*)accum4fDev;
+    return launchFrame(c, (size_t)blocks * 256, st, [&]() {
+      kmltNoteLaunch(c, deep); c->lastWide = spectralLastWide(c);
+      job.stackOverflow = c->dStackOvf.p; job.gridLanes = blocks * 256u;
+      spectralScopeDispatch(spectralScope(c), [&](auto sc) {
+        constexpr int SC = decltype(sc)::value;
+        kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { pathTracePssSpectralKernel<dp(), flat(), sweep(), motion(), SC><<<g, b, 0, st>>>(c->S, job); });
+      });
+    });
+  }
   return launchFrame(c, (size_t)blocks * 256, st, [&]() {
     kmltNoteLaunch(c, deep);
     job.stackOverflow = c->dStackOvf.p; job.gridLanes = blocks * 256u;
     kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { pathTracePssKernel<dp(), flat(), motion(), sweep()><<<g, b, 0, st>>>(Sq, job); });
   });
 }
-catch (...) { return hptGuard(c, "hpt_path_trace_pss_dev"); }
+catch (...) { return hptGuard(c, "hpt_path_trace_pss_dev2"); }
+extern "C" int hpt_path_trace_pss_dev(hpt_ctx* c, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev, void* stream)
+{ return hpt_path_trace_pss_dev2(c, xDev, n, strideFloats, color4fDev, pixelDev, nullptr, nullptr, stream); }
 
 // C of a call: the option, or one chain per lane of the resident grid, reduced until every chain has a step
 static int kmlt_chain_count(hpt_ctx* c, unsigned long long total, uint& chains)
@@ -3089,7 +3125,11 @@ static int kmlt_chain_count(hpt_ctx* c, unsigned long long total, uint& chains)
   if (c->kmltChains != 0u) {
     if ((unsigned long long)c->kmltChains > total) return c->fail(HPT_ERR_ARG, "PathTraceBlockKMLT: kmlt_chains exceeds pixelsNum * a_passNum (a chain would have no step)");
     chains = c->kmltChains;
-  } else chains = (uint)std::min<unsigned long long>((unsigned long long)gridBlocks(c, false, true) * 256ull, total);
+  } else {
+    const bool spectral = c->kmltSpectral && c->S.spectralMode != 0u;     // the spectral chain kernel's resident grid is its scope's
+    const int grid = spectral ? spectralGridBlocks(c, spectralScope(c)) : gridBlocks(c, false, true);
+    chains = (uint)std::min<unsigned long long>((unsigned long long)grid * 256ull, total);
+  }
   return HPT_OK;
 }
 
@@ -3157,7 +3197,14 @@ try {
     if (int rc = launchFrame(c, (size_t)blocks * 256, st, [&]() {           // the event pair spans the chains and the normalisation
       kmltNoteLaunch(c, deep);
       job.stackOverflow = c->dStackOvf.p; job.gridLanes = blocks * 256u;
-      kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { kmltChainKernel<dp(), flat(), motion(), sweep()><<<g, b, 0, st>>>(Sq, job); });
+      if (c->S.spectralMode != 0u) {                                        // (kmlt_check let it through: the option is on)
+        c->lastWide = spectralLastWide(c);
+        spectralScopeDispatch(spectralScope(c), [&](auto sc) {
+          constexpr int SC = decltype(sc)::value;
+          kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { kmltChainSpectralKernel<dp(), flat(), sweep(), motion(), SC><<<g, b, 0, st>>>(c->S, job); });
+        });
+      }
+      else kmltDispatch(c, deep, [&](auto dp, auto flat, auto motion, auto sweep) { kmltChainKernel<dp(), flat(), motion(), sweep()><<<g, b, 0, st>>>(Sq, job); });
       normalise();
     })) return rc;
     c->kmltLastChains = chains;
@@ -3596,6 +3643,7 @@ try {
   else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
+  else if (k == "kmlt_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "kmlt_spectral: 0 PathTraceBlockKMLT and the primary-sample-space pass refuse m_spectral_mode, 1 they run the spectral MLT kernels"); c->kmltSpectral = value != 0; }
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels
   else if (k == "dbg_stack_witness") { c->stackWitness = value != 0; c->witnessWords = 0; }   // diagnostic: sentinel fill of the stacks' HBM part before every launch (hpt_get_stack_witness)

@@ -8,34 +8,15 @@
 //     and its proposal in HBM as [slot][chain] (lane-adjacent chains read adjacent addresses), the two contributions of a step go to the film
 //     with no-return float atomics (the idiom of hpt_qmc.hip), every step can be recorded. kmltStatsKernel / kmltScaleKernel are the
 //     brightness normalisation (:448-472).
-// Every BSDF branch and the thin films (shadeVertex<.., FILM>); RGB only (the host refuses m_spectral_mode); megakernel schedule only.
+// Every BSDF branch and the thin films (shadeVertex<.., FILM>); RGB only - m_spectral_mode runs pathTracePssSpectralKernel / kmltChainSpectralKernel
+// (hpt_spectral.hip) when hpt_set_option("kmlt_spectral", 1) asked for it and is refused otherwise; megakernel schedule only.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
+#include "hpt_kmlt_chain.h"
 
 namespace hpt {
 
-static const uint KMLT_BOUNCE_START = 6u, KMLT_LGHT_ID = 0u, KMLT_MATS_ID = 4u, KMLT_BLND_ID = 8u, KMLT_PER_BOUNCE = 10u;   // integrator_kmlt.cpp:33-37
-
-// IntegratorKMLT::GetRandomNumbers* (:87-151): slot i of the lane's vector is x[i * stride]. A blend layer of 2 or more reads into the next
-// bounce's light numbers, as the reference indexes it; a slot past the vector's end reads 0.
-struct PssRands
-{
-  const float* x; size_t stride; uint n;
-  HPT_DEV float at(uint i) const { return i < n ? x[(size_t)i * stride] : 0.0f; }
-  HPT_DEV V4 lights(Rng&, uint bounce, float& rndId) const
-  {
-    const uint b = KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_LGHT_ID;
-    const V4 r = v4(at(b), at(b + 1u), at(b + 2u), at(b + 3u));
-    rndId = r.w;
-    return r;
-  }
-  HPT_DEV V4 mats(Rng&, uint bounce) const
-  {
-    const uint b = KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_MATS_ID;
-    return v4(at(b), at(b + 1u), at(b + 2u), at(b + 3u));
-  }
-  HPT_DEV float blend(Rng&, uint bounce, uint layer) const { return at(KMLT_BOUNCE_START + bounce * KMLT_PER_BOUNCE + KMLT_BLND_ID + layer); }
-};
+// the slots of a vector and the PssRands policy (GetRandomNumbers*) live in hpt_decl.h: pssEvalSpec (hpt_spectral.hip) reads the same vectors
 
 // PathTraceF (:156-228) for the lanes with `active` set; the others only keep the wave's loop company. tid: the reference's thread id (the
 // camera back plate reads m_packedXY[tid]). color = accumColor * m_exposureMult (no m_camRespoceRGB in RGB mode), pixel = y * winWidth + x of
@@ -108,20 +89,7 @@ __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTracePssKernel(const 
   if (active) { job.color[glane] = make_float4(color.x, color.y, color.z, 0.0f); job.pixel[glane] = pixel; }
 }
 
-// :230-233
-HPT_DEV float kmltContribFunc(V3 c) { return smax(0.333334f * (c.x + c.y + c.z), 0.0f); }
-
-// MutateKelemen (:64-85), float32 as written
-HPT_DEV float mutateKelemen(float valueX, float rx, float ry, float p2, float p1)
-{
-  const float s1 = 1.0f / p1, s2 = 1.0f / p2;
-  const float power = -logf(s2 / s1);
-  const float dv = smax(s2 * (expf(power * sqrtf_(rx)) - expf(power)), 0.0f);
-  if (ry < 0.5f) { valueX += dv; if (valueX > 1.0f) valueX -= 1.0f; }
-  else           { valueX -= dv; if (valueX < 0.0f) valueX += 1.0f; }
-  return valueX;
-}
-
+// kmltContribFunc, mutateKelemen and the chain itself (kmltChainBody) live in hpt_kmlt_chain.h, shared with kmltChainSpectralKernel
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) kmltChainKernel(const DevScene S, const KmltJob job)
 {
@@ -130,97 +98,9 @@ __global__ void __launch_bounds__(256, HPT_FILM_WAVES) kmltChainKernel(const Dev
   TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = job.stackOverflow + glane; stk.ovfStride = job.gridLanes;
   TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
   const bool active = glane < job.chains;
-  const uint c = active ? glane : 0u;                                      // (idle lanes form addresses of chain 0 and never use them)
-  const uint n = job.stateSize;
-  const size_t C = job.chains;
-  float* xVec = job.cur + c;                                        // slot i: xVec[i * C]
-  float* xNew = job.prop + c;
-  PssRands rs; rs.x = xNew; rs.stride = C; rs.n = n;
-
-  Rng gen1 = rng_init(c * 7u + 1u), gen2 = rng_init(c);                    // :291-297
-  for (uint i = 0; i < 10u + c % 17u; i++) { rng_next(gen1); rng_next(gen2); }
-
-  V3 yColor = v3(0, 0, 0); float y = 0.0f; uint pixOld = 0u;
-  uint accept = 0u, largeSteps = 0u;
-  double accumBrightness = 0.0;
-  const float MUTATE_COEFF_SCREEN = 128.0f, MUTATE_COEFF_BSDF = 64.0f, plarge = 0.25f;
-
-  // trip 0 evaluates the initial state (:299-312), trip 1 + i is step i of the chain: one place where F is evaluated, one copy of the path code
-  for (uint trip = 0; trip <= job.steps; trip++) {
-    bool isLargeStep = false;
-    if (active) {
-      if (trip == 0u) { for (uint i = 0; i < n; i++) xNew[i * C] = rng_float1(gen2); }
-      else {
-        isLargeStep = rng_float1(gen1) < plarge;
-        if (isLargeStep) {
-          for (uint i = 0; i < n; i += 4u) {
-            const V4 r1 = rng_float4(gen2);
-            xNew[(i + 0u) * C] = r1.x; xNew[(i + 1u) * C] = r1.y; xNew[(i + 2u) * C] = r1.z; xNew[(i + 3u) * C] = r1.w;
-          }
-        } else {
-          const V4 r1 = rng_float4(gen2);
-          const V4 r2 = rng_float4(gen2);
-          xNew[0 * C] = mutateKelemen(xVec[0 * C], r1.x, r1.y, MUTATE_COEFF_SCREEN * 1.0f, 1024.0f);
-          xNew[1 * C] = mutateKelemen(xVec[1 * C], r1.z, r1.w, MUTATE_COEFF_SCREEN * 1.0f, 1024.0f);
-          xNew[2 * C] = mutateKelemen(xVec[2 * C], r2.x, r2.y, MUTATE_COEFF_BSDF, 1024.0f);
-          xNew[3 * C] = mutateKelemen(xVec[3 * C], r2.z, r2.w, MUTATE_COEFF_BSDF, 1024.0f);
-          for (uint i = 4u; i < n; i += 2u) {
-            const V4 r = rng_float4(gen2);
-            xNew[(i + 0u) * C] = mutateKelemen(xVec[(i + 0u) * C], r.x, r.y, MUTATE_COEFF_BSDF, 1024.0f);
-            xNew[(i + 1u) * C] = mutateKelemen(xVec[(i + 1u) * C], r.z, r.w, MUTATE_COEFF_BSDF, 1024.0f);
-          }
-        }
-      }
-    }
-    V3 yNewColor; uint pixNew;
-    pssEval<DEEP, FLAT, MOTION, SWEEP>(S, rs, active, c, job.packedXY, job.packedCount, stk, st, yNewColor, pixNew);
-    if (active) {
-      const float yNew = kmltContribFunc(yNewColor);
-      if (trip == 0u) {
-        for (uint i = 0; i < n; i++) xVec[i * C] = xNew[i * C];
-        y = yNew; yColor = yNewColor; pixOld = pixNew;
-        if (job.recInitColor) job.recInitColor[c] = make_float4(yNewColor.x, yNewColor.y, yNewColor.z, 0.0f);
-        if (job.recInitPixel) job.recInitPixel[c] = pixNew;
-      } else {
-        const size_t rec = (size_t)c * job.steps + (trip - 1u);
-        if (job.recProposals) { float* p = job.recProposals + rec * n; for (uint i = 0; i < n; i++) p[i] = xNew[i * C]; }
-        const float yOld = y;
-        const V3 yOldColor = yColor;
-        const uint pixCompared = pixOld;
-        const float a = (yOld == 0.0f) ? 1.0f : smin(1.0f, yNew / yOld);
-        const float p = rng_float1(gen1);
-        const bool accepted = p <= a;
-        if (accepted) {
-          for (uint i = 0; i < n; i++) xVec[i * C] = xNew[i * C];
-          y = yNew; yColor = yNewColor; pixOld = pixNew;
-          accept++;
-        }
-        if (isLargeStep) { accumBrightness += (double)yNew; largeSteps++; }
-        // (5) contrib to image (:386-433), w1 = 1
-        const float kY = (1.0f / smax(yNew, 1e-6f)), kX = (1.0f / smax(yOld, 1e-6f)), na = 1.0f - a;
-        const V3 contribAtY = v3(1.0f * yNewColor.x * kY * a, 1.0f * yNewColor.y * kY * a, 1.0f * yNewColor.z * kY * a);
-        const V3 contribAtX = v3(1.0f * yOldColor.x * kX * na, 1.0f * yOldColor.y * kX * na, 1.0f * yOldColor.z * kX * na);
-        const bool addX = dot(contribAtX, contribAtX) > 1e-12f, addY = dot(contribAtY, contribAtY) > 1e-12f;
-        if (addX) {
-          float* o = job.outColor + (size_t)pixCompared * 4u;
-          atomicAdd(o + 0, contribAtX.x); atomicAdd(o + 1, contribAtX.y); atomicAdd(o + 2, contribAtX.z);
-        }
-        if (addY) {
-          float* o = job.outColor + (size_t)pixNew * 4u;
-          atomicAdd(o + 0, contribAtY.x); atomicAdd(o + 1, contribAtY.y); atomicAdd(o + 2, contribAtY.z);
-        }
-        if (job.recLarge) job.recLarge[rec] = isLargeStep ? 1 : 0;
-        if (job.recAccepted) job.recAccepted[rec] = accepted ? 1 : 0;
-        if (job.recA) job.recA[rec] = a;
-        if (job.recColor) job.recColor[rec] = make_float4(yNewColor.x, yNewColor.y, yNewColor.z, 0.0f);
-        if (job.recPixel) job.recPixel[rec] = pixNew;
-        if (job.recOldPixel) job.recOldPixel[rec] = pixCompared;
-        if (job.recContribX) job.recContribX[rec] = make_float4(contribAtX.x, contribAtX.y, contribAtX.z, addX ? 1.0f : 0.0f);
-        if (job.recContribY) job.recContribY[rec] = make_float4(contribAtY.x, contribAtY.y, contribAtY.z, addY ? 1.0f : 0.0f);
-      }
-    }
-  }
-  if (active) { job.accumBrightness[c] = accumBrightness; job.largeSteps[c] = largeSteps; job.accept[c] = accept; }
+  kmltChainBody(job, active, glane, [&](const PssRands& rs, V3& color, uint& pixel) {
+    pssEval<DEEP, FLAT, MOTION, SWEEP>(S, rs, active, active ? glane : 0u, job.packedXY, job.packedCount, stk, st, color, pixel);
+  });
 }
 
 // Sums of one block in a fixed order: every thread adds its strided share, the 256 partial sums are folded in LDS.

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 #include "hpt_block_trace.h"
+#include "hpt_kmlt_chain.h"
 #ifndef HPT_SPEC_FILM
 #define HPT_SPEC_FILM 1      // 0: an A/B build without the thin-film branches (what they cost the scenes that have none)
 #endif
@@ -751,6 +752,105 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
 #undef PIXEL
 }
 
+// ---- IntegratorKMLT under m_spectral_mode (mlt/integrator_kmlt.cpp; `hydra --mlt --spectral`) -------------------------------------------------------
+// pssEvalSpec = IntegratorKMLT::PathTraceF with m_spectral_mode on: pssEval (hpt_kmlt.hip) around the path state of the kernels above. Every number
+// is READ from the lane's vector: x[0..3] the film and lens point, x[4] the wavelength sample (kernel_InitEyeRay, :173-174: SampleWavelengths of
+// GetRandomNumbersSpec = slot 4), x[5] the time, the vertices through PssRands; no generator is read or written. The end of a path is step (7) of
+// pathTraceQmcSpectralKernel: the environment by scope, SpectralCamRespoceToRGB, then the exposure (:224-227) - so the chain's contribFunc,
+// acceptance, contributions and normalisation see RGB, as in RGB mode. The loop has pssEval's shape: one closest-hit and one shadow query per
+// trip, the whole wave leaves together. waves / raw: the path's wavelengths and exposure * accumColor[i] before the conversion (records).
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
+HPT_DEV void pssEvalSpec(const DevScene& S, const PssRands rs, const bool active, const uint tid, const uint* __restrict__ packedXY, const uint packedCount,
+                         const TravStack& stk, TravStats& st, V3& color, uint& pixel, V4& waves, V4& raw)
+{
+  bool alive = active;
+  uint bounce = 0, flags = 0;
+  Rng gen; gen.sx = gen.sy = 0;                                            // never drawn from: PssRands ignores it
+  V3 rpos = v3(0, 0, 0), rdir = v3(0, 0, 1);
+  V4 accum = v4s(0.0f), thr = v4s(1.0f);
+  float misPdf = 1.0f, misIor = 1.0f, pathTime = 0.0f;
+  const uint maxBounce = S.traceDepth;
+  color = v3(0, 0, 0); pixel = 0u; waves = v4s(0.0f); raw = v4s(0.0f);
+  if (alive) {                                                             // kernel_InitEyeRay with IntegratorQMC::SampleCameraRay
+    const V4 lens = v4(rs.at(0u), rs.at(1u), rs.at(2u), rs.at(3u));
+    cameraRayAt<(SCOPE >= 2)>(S, lens.x, lens.y, lens, rpos, rdir);
+    uint x = (uint)(lens.x * float(S.winWidth)), y = (uint)(lens.y * float(S.winHeight));
+    if (x >= (uint)(S.winWidth - 1)) x = (uint)(S.winWidth - 1);
+    if (y >= (uint)(S.winHeight - 1)) y = (uint)(S.winHeight - 1);
+    pixel = y * (uint)S.winWidth + x;
+    if (MOTION) pathTime = rs.at(5u);
+    waves = sampleWavelengths(rs.at(4u), LAMBDA_MIN, LAMBDA_MAX);
+    if (maxBounce == 0u) alive = false;                                    // (the depth loop does not run: the colour stays 0, as in pssEval)
+  }
+  while (__any(alive)) {
+    HitRec hit; hit.inst = 0xFFFFFFFFu; hit.prim = 0; hit.t = 0; hit.u = hit.v = 0;
+    if (alive) traceAny<false, false, DEEP, FLAT, MOTION, SWEEP>(S, rpos, rdir, 0.0f, HPT_FLT_MAX, hit, stk, st, pathTime);
+    bool wantShadow = false;
+    V3 shPos = v3(0, 0, 0), shDir = v3(0, 0, 1); float shFar = 0.0f;
+    V4 contrib = v4s(0.0f);
+    if (alive)
+      shadeVertexSpec<SCOPE, MOTION, PssRands>(S, hit, rpos, rdir, waves, accum, thr, misPdf, misIor, flags, bounce, gen, false, wantShadow, shPos, shDir, shFar, contrib, pathTime, rs);
+    if (wantShadow) {
+      HitRec sh;
+      const bool occluded = traceAny<true, false, DEEP, FLAT, MOTION, SWEEP>(S, shPos, shDir, 0.0f, shFar, sh, stk, st, pathTime);
+      if (!occluded) accum = accum + contrib;
+    }
+    if (alive) {
+      bounce++;
+      if ((flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= maxBounce) {        // kernel_HitEnvironment, then the conversion
+        if ((flags & RAY_FLAG_OUT_OF_SCENE) != 0) {
+          V4 env = ld4(S.envColor);
+          if (SCOPE >= 2) {                                                // the back plate reads m_packedXY[tid]; past the vector's end: 0
+            const uint backXY = (S.envCamBackId != 0xFFFFFFFFu && tid < packedCount) ? packedXY[tid] : 0u;
+            env = environmentRadianceSpec(S, rdir, waves, misPdf, flags, backXY);
+          }
+          else if (S.envSpecId != 0xFFFFFFFFu) env = sampleUniformSpectrum(S.specValues, S.specOffsetSz[2u * S.envSpecId], waves) * (S.envSpecMult / 106.856895f);
+          if (S.integratorType == INTEGRATOR_STUPID_PT) accum = thr * env; else accum = accum + thr * env;
+        }
+        const V3 c = spectralCamResponseToRGB(S, accum, waves, flags);
+        color = v3(S.exposureMult * c.x, S.exposureMult * c.y, S.exposureMult * c.z);
+        raw = accum * S.exposureMult;
+        alive = false;
+      }
+    }
+  }
+}
+
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE_>
+__global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTracePssSpectralKernel(const DevScene S, const PssJob job)
+{
+  constexpr int SCOPE = SCOPE_ == 3 ? 2 : SCOPE_;
+  __shared__ uint stackMem[LDS_STACK * 256];
+  const uint glane = blockIdx.x * 256u + threadIdx.x;
+  TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = job.stackOverflow + glane; stk.ovfStride = job.gridLanes;
+  TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
+  const bool active = glane < job.n;
+  PssRands rs; rs.x = job.x + (size_t)(active ? glane : 0u) * job.vecStride; rs.stride = 1u; rs.n = job.stateSize;
+  V3 color; uint pixel; V4 waves, raw;
+  pssEvalSpec<DEEP, FLAT, SWEEP, MOTION, SCOPE>(S, rs, active, glane, job.packedXY, job.packedCount, stk, st, color, pixel, waves, raw);
+  if (active) {
+    job.color[glane] = make_float4(color.x, color.y, color.z, 0.0f); job.pixel[glane] = pixel;
+    if (job.waves != nullptr) job.waves[glane] = make_float4(waves.x, waves.y, waves.z, waves.w);
+    if (job.accum != nullptr) job.accum[glane] = make_float4(raw.x, raw.y, raw.z, raw.w);
+  }
+}
+
+// the chains of kmltChainKernel (hpt_kmlt_chain.h: one copy of the body) around pssEvalSpec
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE_>
+__global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) kmltChainSpectralKernel(const DevScene S, const KmltJob job)
+{
+  constexpr int SCOPE = SCOPE_ == 3 ? 2 : SCOPE_;
+  __shared__ uint stackMem[LDS_STACK * 256];
+  const uint glane = blockIdx.x * 256u + threadIdx.x;
+  TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = job.stackOverflow + glane; stk.ovfStride = job.gridLanes;
+  TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
+  const bool active = glane < job.chains;
+  kmltChainBody(job, active, glane, [&](const PssRands& rs, V3& color, uint& pixel) {
+    V4 waves, raw;
+    pssEvalSpec<DEEP, FLAT, SWEEP, MOTION, SCOPE>(S, rs, active, active ? glane : 0u, job.packedXY, job.packedCount, stk, st, color, pixel, waves, raw);
+  });
+}
+
 // ---- spectral rendering under the block-local schedule (hpt_block.hip's structure on four wavelengths) ------------------------------------------
 // The kernel above is one thread per pixel without a work queue; its lanes keep their ray until the slowest lane of the wave is through. For
 // scenes whose rays walk a real tree - the reference's 16 396-triangle spectral fixture, a 10^6-triangle interior under m_spectral_mode = 1 -
@@ -1017,7 +1117,7 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
 }
 
 // one translation unit per scope (-DHPT_SPEC_INST=1 / 2 / 3 / 4: scope 0 / 1 / 2 / 2 at 4 waves; 5 / 6 / 7 / 8: the QMC kernel of those scopes;
-// 0: all), see __graft_entry__.build
+// 9 / 10 / 11 / 12: the primary-sample-space pass and the MLT chains of those scopes; 0: all), see __graft_entry__.build
 #ifndef HPT_SPEC_INST
 #define HPT_SPEC_INST 0
 #endif
@@ -1048,6 +1148,27 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   template __global__ void pathTraceQmcSpectralKernel<true,  false, false, true,  SCOPE>(const DevScene, const Job, const QmcJob); \
   template __global__ void pathTraceQmcSpectralKernel<false, true,  false, true,  SCOPE>(const DevScene, const Job, const QmcJob); \
   template __global__ void pathTraceQmcSpectralKernel<true,  true,  false, true,  SCOPE>(const DevScene, const Job, const QmcJob);
+#define HPT_SPEC_KMLT_1(DEEP, FLAT, SWEEP, MOTION, SCOPE) \
+  template __global__ void pathTracePssSpectralKernel<DEEP, FLAT, SWEEP, MOTION, SCOPE>(const DevScene, const PssJob); \
+  template __global__ void kmltChainSpectralKernel<DEEP, FLAT, SWEEP, MOTION, SCOPE>(const DevScene, const KmltJob);
+#define HPT_SPEC_KMLT(SCOPE)  /* the same traversal variants */ \
+  HPT_SPEC_KMLT_1(false, false, false, false, SCOPE) HPT_SPEC_KMLT_1(true,  false, false, false, SCOPE) \
+  HPT_SPEC_KMLT_1(false, true,  false, false, SCOPE) HPT_SPEC_KMLT_1(true,  true,  false, false, SCOPE) \
+  HPT_SPEC_KMLT_1(false, false, true,  false, SCOPE) \
+  HPT_SPEC_KMLT_1(false, false, false, true,  SCOPE) HPT_SPEC_KMLT_1(true,  false, false, true,  SCOPE) \
+  HPT_SPEC_KMLT_1(false, true,  false, true,  SCOPE) HPT_SPEC_KMLT_1(true,  true,  false, true,  SCOPE)
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 9
+HPT_SPEC_KMLT(0)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 10
+HPT_SPEC_KMLT(1)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 11
+HPT_SPEC_KMLT(2)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 12
+HPT_SPEC_KMLT(3)
+#endif
 #if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 5
 HPT_SPEC_QMC(0)
 #endif

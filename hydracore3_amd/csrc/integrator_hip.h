@@ -274,10 +274,13 @@ public:
 
 // IntegratorKMLT (mlt/integrator_kmlt.cpp): Kelemen MLT; derives from the QMC integrator as in the reference, whose FB_DIRECT layer it forwards to
 // (the C entry does that itself). out_color: zero-filled, 4 channels; the chain count is hpt_set_option(ctx, "kmlt_chains", n) or the default.
+// m_spectral_mode (`hydra --mlt --spectral`) is refused by the C entry unless EnableSpectralKMLT(true) set the context's "kmlt_spectral" option;
+// the frame stays RGB (SpectralCamRespoceToRGB is applied per path). The FB_DIRECT layer of a spectral context needs EnableSpectralQMC as well.
 class IntegratorKMLTHIP : public IntegratorQMCHIP
 {
 public:
   using IntegratorQMCHIP::IntegratorQMCHIP;
+  void EnableSpectralKMLT(bool a_on) { if (m_ctx) report(hpt_set_option(m_ctx, "kmlt_spectral", a_on ? 1 : 0), "EnableSpectralKMLT"); }
   void PathTraceBlock(uint32_t pixelsNum, uint32_t channels, float* out_color, uint32_t a_passNum) override
   { if (m_ctx) report(hpt_path_trace_kmlt_block(m_ctx, pixelsNum, channels, out_color, a_passNum), "PathTraceBlockKMLT"); }
 };

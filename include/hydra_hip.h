@@ -344,7 +344,8 @@ uint32_t hpt_qmc_sample_count(uint32_t pixelsNum, uint32_t passNum);
 
 /* ---- Kelemen MLT in primary sample space (mlt/integrator_kmlt.cpp; `hydra`'s MLT mode) ---------------------------------- */
 /* m_randsPerThread: floats of one primary-sample-space vector = AlignedSize(10 * traceDepth + 6, 16). Slots 0..3: the lens float4 (0 and 1
- * are the film position in [0,1]); 4: the wavelength sample (unused in RGB); 5: the time; 6 + 10 b + 0..3: bounce b's light float4 (.w selects
+ * are the film position in [0,1]); 4: the wavelength sample (GetRandomNumbersSpec: SampleWavelengths of it gives a spectral path its four
+ * wavelengths; not read in RGB); 5: the time; 6 + 10 b + 0..3: bounce b's light float4 (.w selects
  * the light); 6 + 10 b + 4..7: its material float4; 6 + 10 b + 8 + layer: its blend numbers (layer 2 and up overlaps the next bounce's light
  * numbers, as in the reference; a slot past the vector's end reads 0). Host code; no context, no GPU. */
 uint32_t hpt_kmlt_state_size(uint32_t traceDepth);
@@ -352,9 +353,20 @@ uint32_t hpt_kmlt_state_size(uint32_t traceDepth);
  * from the vector. color4fDev[i] = accumColor * m_exposureMult and a fourth float 0 (no camRespoceRGB: PathTraceF applies none in RGB mode),
  * pixelDev[i] = y * winWidth + x with x = min(uint(x[0] * winWidth), winWidth - 1), y likewise from x[1] (IntegratorQMC::SampleCameraRay).
  * m_randomGens is neither read nor written. Asynchronous on stream. HPT_ERR_ARG for a null pointer or strideFloats below
- * hpt_kmlt_state_size(traceDepth); HPT_ERR_UNSUPPORTED with m_spectral_mode on; HPT_ERR_STATE before CommitDeviceData, UpdateMembersPlainData
- * or PackXYBlock. Megakernel schedule only. */
+ * hpt_kmlt_state_size(traceDepth); HPT_ERR_UNSUPPORTED with m_spectral_mode on unless the option "kmlt_spectral" is set (below);
+ * HPT_ERR_STATE before CommitDeviceData, UpdateMembersPlainData or PackXYBlock. Megakernel schedule only.
+ * Spectral MLT (`hydra --mlt --spectral`) is opt-in: after hpt_set_option(ctx, "kmlt_spectral", 1) (0 is the default, any other value
+ * HPT_ERR_ARG) this entry, hpt_path_trace_kmlt_block and hpt_path_trace_kmlt_block_dev serve a context with m_spectral_mode on instead of
+ * refusing it; with m_spectral_mode off nothing changes. A path then carries the four wavelengths SampleWavelengths(x[4]) and color4fDev[i] =
+ * m_exposureMult * SpectralCamRespoceToRGB(accumColor, wavelengths, rayFlags): the chains' contribFunc, acceptance, contributions and
+ * normalisation work on RGB as before. channels stays 4 (no wavelength layers); thin films whose tables are not of spectral size are
+ * HPT_ERR_ARG, as in PathTraceBlock; the FB_DIRECT layer still forwards to the QMC entry, whose own option "qmc_spectral" decides there. */
 int  hpt_path_trace_pss_dev(hpt_ctx* ctx, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev, void* stream);
+/* The same with two more records of 4 floats per vector, each NULL or n elements long: waves4fDev[i] = the path's four wavelengths,
+ * accum4fDev[i] = m_exposureMult * accumColor[k], the four raw components before SpectralCamRespoceToRGB. They exist in spectral MLT only: on
+ * a context with m_spectral_mode off a non-NULL one is HPT_ERR_ARG. hpt_path_trace_pss_dev forwards here with NULLs. */
+int  hpt_path_trace_pss_dev2(hpt_ctx* ctx, const float* xDev, uint32_t n, uint32_t strideFloats, float* color4fDev, uint32_t* pixelDev,
+                             float* waves4fDev, float* accum4fDev, void* stream);
 /* Records of the chains, all in device memory, each pointer NULL or long enough: per chain c and step i at [c * steps + i] - whether the step
  * was a large one and whether it was accepted (bytes), the acceptance probability a, the proposal's colour (4 floats) and pixel, the pixel of
  * the state it was compared with; per chain the initial state's colour and pixel; every proposal vector, [c][i][state size] floats; and
@@ -380,7 +392,8 @@ typedef struct hpt_kmlt_records {
  * hpt_set_option("kmlt_chains", n), by default one chain per lane of the resident grid, at most pixelsNum * a_passNum (DESIGN.md 7 has this
  * and the other definitions the reference ties to its thread count). m_randomGens is left untouched. m_renderLayer == FB_DIRECT forwards to
  * hpt_path_trace_qmc_block and returns what it returns. HPT_ERR_ARG for a null frame, channels other than 4, pixelsNum above winWidth *
- * winHeight and kmlt_chains above pixelsNum * a_passNum; HPT_ERR_UNSUPPORTED with m_spectral_mode on; HPT_ERR_STATE as hpt_path_trace_pss_dev;
+ * winHeight and kmlt_chains above pixelsNum * a_passNum; HPT_ERR_UNSUPPORTED with m_spectral_mode on unless the option "kmlt_spectral" is
+ * set (hpt_path_trace_pss_dev; the default chain count is then the spectral kernel's resident grid); HPT_ERR_STATE as hpt_path_trace_pss_dev;
  * a_passNum = 0 is HPT_OK and touches nothing. hpt_get_execution_time("PathTraceBlockKMLT") gives its four slots; the kernel slot spans the chains and the normalisation. */
 /* C and steps = (pixelsNum * passNum) / C of a hpt_path_trace_kmlt_block call made now with these arguments (the option kmlt_chains, or the
  * resident grid of the present launch configuration, at most pixelsNum * passNum): what a caller sizes its record arrays by. Both 0 when
