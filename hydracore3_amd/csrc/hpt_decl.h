@@ -28,12 +28,14 @@ struct Job
   // Pass slices (SLICED instantiations of pathTraceKernel, forward calls; hpt_set_option("pass_slice")) share the storage of four fields that
   // only PathTraceDR reads, so that Job - a by-value kernel argument of every kernel family - keeps its size and layout:
   //   passSlice       s > 0: the queue holds tidCount * passSliceCount(passNum, s) items (hpt_types.h: passSliceItem) and a pixel is handed
-  //                   from slice to slice through HBM
-  //   sliceDone       [tid]: slices of the pixel that are finished and published (zeroed before the launch)
+  //                   from slice to slice through sliceMail
+  //   sliceMail       [tid][SLICE_MAIL_WORDS]: the pixel and its generator as tagged 64-bit words (hpt_types.h: sliceWordPack), written by the
+  //                   lane that finished a slice which has a successor and read by the lane that holds that successor; relaxed agent-scope
+  //                   atomics only, no fence on either side (zeroed before the launch)
   //   slicePollLimit  polls after which a lane waiting for its predecessor gives up (a protocol bug ends as an error, not as a hang)
   //   sliceError      set to 1 by a lane that gave up (host-visible; the host reports HPT_ERR_STATE)
   union { float* lossAccum; uint* sliceError; };      // lossAccum: sum over samples of loss / passNum
-  union { float* record; uint* sliceDone; };          // record: per-lane, per-bounce adjoint records: [bounce][field][lane]
+  union { float* record; unsigned long long* sliceMail; };         // record: per-lane, per-bounce adjoint records: [bounce][field][lane]
   union { uint recordLanes; uint passSlice; };        // recordLanes: total lanes of the grid (stride of the record buffer)
   uint   naive;                   // the spectral kernel only: NaivePathTrace (the RGB kernels have their own instantiations)
   uint   drSkipNonFinite;         // hpt_set_option("dr_skip_nonfinite"): samples whose radiance is not finite give neither loss, colour nor gradient

@@ -26,11 +26,24 @@
 #include "bvh_build.h"
 #include "hpt_lbvh.h"
 
-// Pass slices of the forward megakernel when hpt_set_option("pass_slice") was never called: 256 passes per work item in calls with at least two
-// pixels per lane and at least two such slices per pixel, whole pixels otherwise. Every hand-over writes the XCD's L2 back, so short slices
-// lose steeply. profiles/r7_pass_slices.md has what was measured: 16 ... 512 passes per item at four pixels per lane, 16 ... 256 at half a pixel,
-// 256 at one pixel (loses) and at two (gains), and 1024^2 calls of 512 passes with 0 / 128 / 256. Nothing between one and two pixels per lane was measured.
-static const uint PASS_SLICE_AUTO = 256u;
+// Pass slices of the forward megakernel when hpt_set_option("pass_slice") was never called (passSliceAuto below). The hand-over is a mailbox of
+// tagged words with no release and no acquire (hpt_kernels.hip), so slices shorter than the 256 passes of the fenced form pay; what stands
+// behind each constant is measured in profiles/slice_mailbox.md (m = pixels per lane of the grid, Mpaths/s, whole pixels -> best slice):
+//   PASS_SLICE_MIN_M 2    m = 2 gains with every slice tried (5703 -> 6992 at 64); m = 1 and m = 0.5 lose with every slice (9336 -> 9182 at best,
+//                         14615 -> 13184); nothing between one and two was measured, so two is the smallest value known to gain
+//   PASS_SLICE_MAX_M 8    m = 4 gains, m = 16 loses with 64 and with 128 (3782 -> 3574, 3693): sixteen whole pixels per lane already even out the
+//                         end of the call. Nothing between was measured; eight is the middle of the two in ratio
+//   PASS_SLICE_MIN_PASSES 256   the shortest call measured, and it gains (m = 4: 3372 -> 3532 at 64); shorter calls keep whole pixels
+//   64 or 128             m = 4 at 1024 passes: 128 is best (3650 ... 3654; 64: 3603 ... 3609, 256: 3630 ... 3636, 32: 3364 ... 3366, 512: 3550 ... 3556);
+//                         at 512 passes 128 and 64 are close (3590, 3575); at 256 passes 64 (3532; 128: 3490); m = 2 at 1024 passes 64 (6992; 128: 6911).
+//                         In lane-passes, m x passes: 4096 -> 128, 2048 -> either, 1024 -> 64, 2048 -> 64: 128 where it still leaves a lane
+//                         PASS_SLICE_LONG_ITEMS = 32 items, 64 elsewhere. 32 passes per item lose everywhere.
+static const uint PASS_SLICE_MIN_M = 2u, PASS_SLICE_MAX_M = 8u, PASS_SLICE_MIN_PASSES = 256u, PASS_SLICE_SHORT = 64u, PASS_SLICE_LONG = 128u, PASS_SLICE_LONG_ITEMS = 32u;
+static uint passSliceAuto(uint64_t tidCount, uint64_t gridLanes, uint64_t passNum)
+{
+  if (tidCount < PASS_SLICE_MIN_M * gridLanes || tidCount >= PASS_SLICE_MAX_M * gridLanes || passNum < PASS_SLICE_MIN_PASSES) return 0u;
+  return tidCount * passNum >= (uint64_t)PASS_SLICE_LONG_ITEMS * PASS_SLICE_LONG * gridLanes ? PASS_SLICE_LONG : PASS_SLICE_SHORT;
+}
 static const float BLOCK_SAH_VISITS = 8.0f;                     // automatic schedule: from this many expected inner-node visits per ray the megakernel repacks rays block-locally (hpt_block.hip)
 static const uint MAX_STACK = 64;                           // traversal stack entries per lane: LDS_STACK in LDS + the rest in an HBM overflow buffer
 // Static scenes with at most this many INSTANCED triangles get the single-level world-space BVH (48 B + ~32 B of nodes per triangle:
@@ -164,9 +177,9 @@ struct hpt_ctx
   uint gensCount = 0;                                    // m_randomGens.size() as the last InitRandomGens / hpt_set_random_gens left it (the buffer never shrinks)
   DevBuf<uint> dQueue, dStackOvf; DevBuf<Counters> dCounters;
   // pass slices of the forward megakernel (hpt_kernels.hip): hpt_set_option("pass_slice", n), 0 = a work item is a whole pixel
-  int  passSlice = -1;                                   // -1: by the rule at PASS_SLICE_AUTO
+  int  passSlice = -1;                                   // -1: by the rule passSliceAuto
   uint lastPassSlice = 0;
-  DevBuf<uint> dSliceDone;                               // [tid]: finished slices of the pixel, zeroed before every sliced launch
+  DevBuf<unsigned long long> dSliceMail;                 // [tid][SLICE_MAIL_WORDS]: the slices' hand-over mailbox (hpt_types.h), zeroed before every sliced launch
   uint* sliceError = nullptr;                            // pinned, device-visible: a lane gave up waiting for its predecessor (sliceErrorCheck)
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
@@ -2190,7 +2203,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
   const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
   const size_t fullGrid = (size_t)gridBlocks(c, dr, fullMaterials && !mode7) * 256;
-  const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : ((job.tidCount >= 2 * fullGrid && job.passNum >= 2u * PASS_SLICE_AUTO) ? PASS_SLICE_AUTO : 0u);
+  const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : passSliceAuto(job.tidCount, fullGrid, job.passNum);
   uint slice = (dr || inRays || naive || film || stats || blockLocal || streamCall || waveCall) ? 0u : sliceWanted;
   while (slice != 0u && (uint64_t)job.tidCount * passSliceCount(job.passNum, slice) > (1ull << 31)) slice *= 2u;
   if (slice >= job.passNum) slice = 0u;                           // one item per pixel either way: the plain form
@@ -2202,9 +2215,9 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (slice != 0u) {                                           // (the slice fields share storage with PathTraceDR's: hpt_decl.h)
     job.passSlice = slice;
     if (!c->sliceError) { HIPCHK(c, hipHostMalloc((void**)&c->sliceError, sizeof(uint), hipHostMallocMapped)); *c->sliceError = 0u; }
-    HIPCHK(c, c->dSliceDone.alloc(job.tidEnd));
-    HIPCHK(c, hipMemsetAsync(c->dSliceDone.p, 0, (size_t)job.tidEnd * 4, st));
-    job.sliceDone = c->dSliceDone.p; job.sliceError = c->sliceError;
+    HIPCHK(c, c->dSliceMail.alloc((size_t)job.tidEnd * SLICE_MAIL_WORDS));
+    HIPCHK(c, hipMemsetAsync(c->dSliceMail.p, 0, (size_t)job.tidEnd * SLICE_MAIL_WORDS * sizeof(unsigned long long), st));   // tag 0: empty, so no tag of an earlier call is ever taken
+    job.sliceMail = c->dSliceMail.p; job.sliceError = c->sliceError;
     // A waiting lane polls once per trip of its wave, or once per sleep (>= one trip's time) when the whole wave waits. What it waits for is at
     // most the pixel's earlier passes, each at most traceDepth + 2 trips: 64 times that, and never less than 2^20 polls.
     job.slicePollLimit = (uint)std::min<uint64_t>(0x7FFFFFFFull, std::max<uint64_t>(1ull << 20, 64ull * job.passNum * (c->S.traceDepth + 2u)));

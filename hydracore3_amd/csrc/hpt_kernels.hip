@@ -13,7 +13,8 @@
 //     ballot + mbcnt prefix sum, and ONE atomicAdd per wave fetches a contiguous run of tids for them;
 //   * the grid is sized to the chip (blocksPerCU x 256 CUs), not to the image;
 //   * with pass slices (Job::passSlice) a work item is a run of passes of a pixel; the pixel and its generator pass from item to item
-//     through HBM behind an agent-scope release / acquire of sliceDone[tid] (DESIGN.md 2.1 has the protocol and its progress argument).
+//     through a mailbox of tagged 64-bit words, sliceMail[tid], with relaxed atomics and no fence (DESIGN.md 2.1 has the protocol, why it
+//     is correct and its progress argument).
 //
 // Exit condition every wave reaches: the queue counter only grows, a lane that draws an index past the end never asks
 // again, and a wave leaves the loop when none of its lanes holds a live path or a pixel or waits for a slice (a wait is bounded).
@@ -67,16 +68,27 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 
   while (true) {
     // ---- (1) a finished pixel goes back to HBM: one read-modify-write per pixel and call ------------------------------
-    if (!alive && havePixel && PIX_PASSES == 0u) {
+    if constexpr (SLICED) {
+      // hand-over: a slice with a successor leaves the frame and gens alone and posts the pixel and its generator as five tagged words. Each
+      // word is valid on its own (its tag rides in the same 64-bit store), so there is no release and no order among the stores to keep.
+      if (!alive && havePixel && PIX_PASSES == 0u && (PIX_SLICE + 1u) * passSlice < job.passNum) {
+        unsigned long long* mail = job.sliceMail + (size_t)PIX_TID * SLICE_MAIL_WORDS;
+        const uint s = PIX_SLICE;
+        __hip_atomic_store(mail + 0, sliceWordPack(s, __float_as_uint(PIX(0))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mail + 1, sliceWordPack(s, __float_as_uint(PIX(1))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mail + 2, sliceWordPack(s, __float_as_uint(PIX(2))), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mail + 3, sliceWordPack(s, gen.sx), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(mail + 4, sliceWordPack(s, gen.sy), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // the word a taker looks at first
+        havePixel = false;
+      }
+    }
+    if (!alive && havePixel && PIX_PASSES == 0u) {                         // (SLICED: the pixel's last slice)
       const uint XY = PIX_XY;
       const uint pixel = INRAYS ? PIX_TID : ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
       if (job.channels == 1) job.outColor[pixel] = PIX(0);
       else { float* o = job.outColor + (size_t)pixel * job.channels; o[0] = PIX(0); o[1] = PIX(1); o[2] = PIX(2); }
       job.gens[PIX_TID] = gen;                                           // kernel_ContributeToImage: m_randomGens[tid] = *gen (:605)
       havePixel = false;
-      // hand-over: the stores above become visible to every CU before the count of finished slices does (the last slice has no successor)
-      if (SLICED && (PIX_SLICE + 1u) * passSlice < job.passNum)
-        __hip_atomic_store(job.sliceDone + PIX_TID, PIX_SLICE + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
     }
     // ---- (2) work queue: ballot the idle lanes, one atomic per wave, prefix-sum the ranks --------------------------------
     if constexpr (!SLICED) {
@@ -118,27 +130,43 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
           } else drained = true;
         }
       }
-      // A pending lane polls ONCE per trip and never in a loop of its own: its wave-mates may hold the very slice it waits for. The poll is
-      // a relaxed agent-scope load; the acquire is one agent-scope fence, in wave-uniform control flow, once a lane's poll has matched.
+      // A pending lane polls ONCE per trip and never in a loop of its own: its wave-mates may hold the very slice it waits for. A poll is one
+      // relaxed agent-scope load of the word the giver writes last; when that carries this lane's tag the other four are loaded, and the
+      // lane takes the pixel only if all five do (a word whose tag is not yet there is simply looked at again next trip). No fence: the taker
+      // reads nothing but these words.
       bool matched = false;
       if (pending) {
-        matched = __hip_atomic_load(job.sliceDone + PIX_TID, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == PIX_SLICE;
+        const unsigned long long* mail = job.sliceMail + (size_t)PIX_TID * SLICE_MAIL_WORDS;
+        const uint s = PIX_SLICE;
+        const unsigned long long w4 = __hip_atomic_load(mail + 4, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (sliceWordFor(w4, s)) {
+          const unsigned long long w0 = __hip_atomic_load(mail + 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long w1 = __hip_atomic_load(mail + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long w2 = __hip_atomic_load(mail + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          const unsigned long long w3 = __hip_atomic_load(mail + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+          matched = sliceWordFor(w0, s) && sliceWordFor(w1, s) && sliceWordFor(w2, s) && sliceWordFor(w3, s);
+          if (matched) {
+            PIX(0) = __uint_as_float(sliceWordPayload(w0)); PIX(1) = __uint_as_float(sliceWordPayload(w1)); PIX(2) = __uint_as_float(sliceWordPayload(w2));
+            gen.sx = sliceWordPayload(w3); gen.sy = sliceWordPayload(w4);
+          }
+        }
         if (matched) pending = false;
         else if (++PIX_POLLS > job.slicePollLimit) {                        // bounded wait: give up, tell the host, take no more work
           __hip_atomic_store(job.sliceError, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
           pending = false; drained = true;
         }
       }
-      if (__any(matched)) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      ready = ready || matched;
-      if (ready) {
+      if (ready) {                                                          // slice 0: the frame and the generator as the caller left them
         const uint tid = PIX_TID;
         const uint XY = job.packedXY[tid];
         gen = job.gens[tid];
         const uint pixel = ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
         if (job.channels == 1) { PIX(0) = job.outColor[pixel]; PIX(1) = 0.0f; PIX(2) = 0.0f; }
         else { const float* o = job.outColor + (size_t)pixel * job.channels; PIX(0) = o[0]; PIX(1) = o[1]; PIX(2) = o[2]; }
-        PIX_XY = XY; PIX_PASSES = passSlicePasses(PIX_SLICE, job.passNum, passSlice);
+        PIX_XY = XY;
+      } else if (matched) PIX_XY = job.packedXY[PIX_TID];
+      if (ready || matched) {
+        PIX_PASSES = passSlicePasses(PIX_SLICE, job.passNum, passSlice);
         havePixel = true;
       }
     }

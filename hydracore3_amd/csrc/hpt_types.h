@@ -297,6 +297,15 @@ HPT_HD SliceItem passSliceItem(uint k, uint tidCount, uint passNum, uint s)
   it.passes = passSlicePasses(it.slice, passNum, s);
   return it;
 }
+// The hand-over of a pixel from slice to slice: a mailbox of one record per tid, SLICE_MAIL_WORDS 64-bit words (one 64-byte line) of which
+// the first SLICE_MAIL_USED are {tag : 32, payload : 32} for PIX(0), PIX(1), PIX(2), gen.sx, gen.sy, written and read one word at a time
+// with relaxed agent-scope 64-bit atomics. tag = writing slice + 1 and the mailbox is zeroed before the launch, so tag 0 is "empty"; the
+// lane that holds slice s > 0 takes a word only when its tag is s, i.e. written by slice s - 1 (tests/cpp/slice_mailbox_test.cpp).
+#define SLICE_MAIL_WORDS 8
+#define SLICE_MAIL_USED  5
+HPT_HD unsigned long long sliceWordPack(uint slice, uint payload) { return ((unsigned long long)(slice + 1u) << 32) | (unsigned long long)payload; }
+HPT_HD bool sliceWordFor(unsigned long long w, uint slice) { return slice != 0u && (uint)(w >> 32) == slice; }   // is w what slice `slice` waits for?
+HPT_HD uint sliceWordPayload(unsigned long long w) { return (uint)(w & 0xFFFFFFFFull); }
 // pixel index of a launch -> tid (Job::tidBegin / tidChunk / tidStride: every tidStride-th chunk of tidChunk tids, hpt_set_tid_interleave)
 HPT_HD uint tidOfIndex(uint tidBegin, uint tidChunk, uint tidStride, uint index)
 { return tidBegin + (index / tidChunk) * tidChunk * tidStride + (index % tidChunk); }

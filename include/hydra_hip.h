@@ -591,8 +591,8 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               those of n = 0 (a work item is a whole pixel). n >= a_passNum is n = 0. PathTraceDR, PathTraceFromInputRays and the other
  *               schedules ignore it. A waiting lane that exceeds its poll limit makes the call (or, for the device-pointer forms, the next
  *               call or hpt_last_kernel_ms) return HPT_ERR_STATE. The limit counts polls (about 3 us each when a whole wave waits; at least 2^20),
- *               not time: with n set by hand on a heavy scene a healthy call could reach it. Never set: 256 in calls with at least two pixels per lane of the grid and at
- *               least 512 passes, else 0. Environment: HPT_PASS_SLICE.
+ *               not time: with n set by hand on a heavy scene a healthy call could reach it. Never set: in calls with at least two and fewer than eight pixels per lane of the
+ *               grid and at least 256 passes, 128 when that leaves a lane 32 work items or more and 64 when not; else 0. Environment: HPT_PASS_SLICE.
  * A member of the reference that is set in its constructor:
  *   "dr_grad_mode"  IntegratorDR's a_gradMode (integrator_dr.h; default 1). 0: RayTraceDR renders and returns the loss through the ordinary
  *               sampler and writes no gradient (integrator_dr.cpp:99, 432-438). PathTraceDR does not read it.
