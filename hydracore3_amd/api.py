@@ -64,6 +64,7 @@ ABI = {
     "hpt_set_tid_interleave": (_i, [_vp, _u32, _u32]),
     "hpt_put_diff_tex2d": (_i, [_vp, _u32, _u32, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "hpt_reset_diff_tex": (_i, [_vp]),
+    "hpt_put_diff_lights": (_i, [_vp, _u32, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "hpt_path_trace_dr": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, C.POINTER(_f)]),
     "hpt_path_trace_dr_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz, _vp, _vp]),
     "hpt_path_trace_vjp": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp, _vp, _sz]),
@@ -640,6 +641,14 @@ class HipIntegrator:
         if rc != 0 and size.value == 0 and off.value == 0xFFFFFFFFFFFFFFFF:
             return (off.value, 0)          # reference behaviour for a bad id: message + (size_t(-1), 0)
         self._chk(rc)
+        self.grad_size = off.value + size.value
+        return (off.value, size.value)
+
+    def PutDiffLights(self, first, count):
+        """Registers lights [first, first + count) as differentiable (no counterpart in the reference): light first + i owns the RGB gain
+        a_data[offset + 4 i + 0..2] (float 4 i + 3 is padding), a_dataGrad receives d loss / d gain there. Returns (offset, size = 4 * count)."""
+        off, size = _u64(0), _u64(0)
+        self._chk(self.L.hpt_put_diff_lights(self.h, first, count, C.byref(off), C.byref(size)))
         self.grad_size = off.value + size.value
         return (off.value, size.value)
 

@@ -952,9 +952,9 @@ HPT_DEV float lightEvalPDF(const LightRec& L, V3 illuminationPoint, V3 ray_dir, 
   return pdfAtoW(L.pdfA, hitDist, cosVal);
 }
 
-HPT_DEV V3 lightIntensity(const DevScene& S, const LightRec& L, V3 a_rayPos, V3 a_rayDir)   // :109-173 (RGB mode)
+// `lightColor`: what the expression starts from - L.intensity, or L.intensity times a registered light's gain (hpt_shade.h: DrLights)
+HPT_DEV V3 lightIntensityFrom(const DevScene& S, const LightRec& L, V3 lightColor, V3 a_rayPos, V3 a_rayDir)   // :109-173 (RGB mode)
 {
-  V3 lightColor = ld3(L.intensity);
   lightColor = lightColor * L.mult;
   if (L.iesId != 0xFFFFFFFFu) {
     if ((L.flags & LIGHT_FLAG_POINT_AREA) != 0) a_rayDir = normalize(ld3(L.pos) - a_rayPos);
@@ -982,6 +982,7 @@ HPT_DEV V3 lightIntensity(const DevScene& S, const LightRec& L, V3 a_rayPos, V3 
   }
   return lightColor;
 }
+HPT_DEV V3 lightIntensity(const DevScene& S, const LightRec& L, V3 a_rayPos, V3 a_rayDir) { return lightIntensityFrom(S, L, ld3(L.intensity), a_rayPos, a_rayDir); }
 
 // ---- sampled environment map: include/clight.h:128-218, integrator_pt_lgt.cpp:30-55, 175-236, cglobals.h:360-373 -----------------------------
 HPT_DEV int selectIndexPropToOpt(float a_r, const float* a_accum, int N, float& pdf)

@@ -247,6 +247,8 @@ struct hpt_ctx
   uint tidChunk = 0, tidStride = 1;      // hpt_set_tid_interleave
   bool instrument = false;
   uint64_t gradSize = 0;
+  uint32_t diffLightFirst = 0, diffLightCount = 0;  // hpt_put_diff_lights: lights [first, first + count) own RGB gains at a_data[diffLightOff + 4 i]; count 0: none registered
+  uint64_t diffLightOff = 0;
 
   float tSlots[T_SLOT_COUNT][4] = {};   // GetExecutionTime slots: kernel, copy in, copy out, overhead (ms) per TimeSlot
   float lastKernelMs = 0.0f;
@@ -1487,7 +1489,7 @@ try {
     r.data = dp; r.diffOffset = ~0ull; r.diffW = r.diffH = r.diffChannels = 0; r.pad2 = 0;
   }
   HIPCHK(c, c->dTextures.upload(c->hTextures.data(), c->hTextures.size()));
-  c->gradSize = 0;
+  c->gradSize = 0; c->diffLightFirst = c->diffLightCount = 0; c->diffLightOff = 0;
 
   DevScene& S = c->S;
   S.triIndices = c->dTriIndices.p; S.vData8f = c->dVData.p; S.matIdByPrimId = c->dMatIdByPrim.p; S.matVertOffset = c->dMatVertOffset.p;
@@ -1786,16 +1788,16 @@ static int gridBlocks(hpt_ctx* c, bool dr, bool fullMaterials = false)
 
 // DEEP: the scene's BVH can need more than LDS_STACK stack entries, so pushes / pops check for the HBM overflow part
 // FLAT: single-level world-space BVH (static scenes within FLAT_TRI_BUDGET) vs two-level TLAS/BLAS
-template <bool STATS, bool DR, int NAIVE, bool SLICED = false>
+template <bool STATS, bool DR, int NAIVE, bool SLICED = false, bool LGRAD = false>   // LGRAD: PathTraceDR / PathTraceVJP with lights registered (hpt_put_diff_lights)
 static void launchPT(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
-  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   else if (S.flatMode) {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -1923,6 +1925,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
       else if (specScope == 2) wfShadeSpecKernel<2><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else wfShadeSpecKernel<1><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
     }
+    else if (dr && wj.drLightCount != 0u) wfShadeKernel<true, true, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (dr)               wfShadeKernel<true, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (c->hasFilm)       { if (c->S.motion) wfShadeKernel<false, false, true, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj); else wfShadeKernel<false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj); }
     else if (c->S.motion)      wfShadeKernel<false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
@@ -1961,6 +1964,8 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   wj.drSkipNonFinite = job.drSkipNonFinite;
   wj.refImg = job.refImg; wj.data = job.data; wj.grad = job.grad; wj.lossAccum = job.lossAccum; wj.record = nullptr;
   wj.adjImg = job.adjImg; wj.vjp = job.vjp;
+  const bool drLights = dr && c->diffLightCount != 0u;        // (launch_path_trace has checked the registration against the scene)
+  wj.drLightFirst = drLights ? job.drLightFirst : 0u; wj.drLightCount = drLights ? job.drLightCount : 0u; wj.drLightOff = drLights ? job.drLightOff : 0u;
   // every path takes at most traceDepth shade passes after the one that generated it; the pass that ends it (or the next one, when a
   // shadow ray was outstanding) also generates the pixel's next path
   // safety net only (the loop ends when a round queues no ray): pixels whose rays were suspended sit rounds out, so there is no tight bound
@@ -1987,7 +1992,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
     HIPCHK(c, g.u[4].alloc(2 * WF_CTR_WORDS));
     HIPCHK(c, g.u[6].alloc(g.itemCount));
     HIPCHK(c, g.u[7].alloc(suspWords)); HIPCHK(c, g.u[8].alloc(suspWords));
-    if (dr) { HIPCHK(c, g.rec.alloc((size_t)g.itemCount * REC_FIELDS * (c->S.traceDepth + 1))); HIPCHK(c, g.lossSlot.alloc(g.itemCount)); }
+    if (dr) { HIPCHK(c, g.rec.alloc((size_t)g.itemCount * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(g.itemCount, c->S.traceDepth) : 0))); HIPCHK(c, g.lossSlot.alloc(g.itemCount)); }
     if (c->S.motion) HIPCHK(c, g.time.alloc(g.itemCount));
     if (spec) { HIPCHK(c, g.waves.alloc(g.itemCount)); HIPCHK(c, g.fb.alloc(g.itemCount)); }
     WfPool& P = pools[gi];
@@ -2130,6 +2135,13 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (dr && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u || c->S.envCamBackId != 0xFFFFFFFFu))
     return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: environment maps, their sampling and camera back plates are not differentiated (constant m_envColor only)");
   if (dr && !c->leanMaterials) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: gltf and emissive materials without normal maps only (what the reference's replay differentiates, integrator_dr.cpp:461-612)");
+  // light-colour gradients (hpt_put_diff_lights): served by the megakernel and the wavefront schedule
+  const bool drLights = dr && c->diffLightCount != 0u;
+  if (drLights && (uint64_t)c->diffLightFirst + c->diffLightCount > c->S.numLights)
+    return c->fail(HPT_ERR_ARG, "PathTraceDR: the scene has fewer lights than hpt_put_diff_lights registered");
+  if (drLights && c->schedule == 3)
+    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the block-local schedule has no light-gradient variant (its kernel spills at four waves per SIMD as it is); hpt_set_schedule 0, 1 or 2");
+  if (drLights && c->instrument) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the instrumented probe has no light-gradient variant");
   // never more lanes than pixels: with fewer, the hardware's round-robin block placement spreads them evenly over the CUs, whereas a
   // full grid would let whichever waves ask first take all the work (a small multi-GPU share of a frame)
   if (c->S.spectralMode != 0u) {                               // four wavelengths per path: its own (plain) kernel
@@ -2200,7 +2212,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
   // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
   const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
-  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS;
+  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS && !drLights;   // (no block-local kernel with light gradients)
   const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
   const size_t fullGrid = (size_t)gridBlocks(c, dr, fullMaterials && !mode7) * 256;
   const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : passSliceAuto(job.tidCount, fullGrid, job.passNum);
@@ -2225,6 +2237,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
   job.counters = nullptr;
   job.drSkipNonFinite = c->drSkipNonFinite ? 1u : 0u;
+  if (drLights) { job.drLightFirst = c->diffLightFirst; job.drLightCount = c->diffLightCount; job.drLightOff = (uint)c->diffLightOff; job.drLightPad = 0u; }   // (share the input-ray pointers' storage)
   c->lastSchedule = 1;
   c->lastShadeRecords = c->S.shadeTris != nullptr ? 1u : 0u;
   // schedule 4 (experimental, never chosen automatically): the block-owned streaming form of the wavefront schedule - heavy static scenes with gltf / emissive materials
@@ -2241,7 +2254,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (stats) { HIPCHK(c, c->dCounters.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dCounters.p, 0, sizeof(Counters), st)); job.counters = c->dCounters.p; }
   if (dr) {
     job.recordLanes = (uint)blocks * 256u;
-    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1)));
+    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(job.recordLanes, c->S.traceDepth) : 0)));
     job.record = c->dRecord.p;
   }
   c->lastPassSlice = slice;
@@ -2274,7 +2287,8 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
       if (stats) {                                                 // the counting probe follows the walk an uninstrumented call would do (see the forward probe below)
         Sd.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;
         launchPT<true, true, 0>(Sd, job, blocks, st, deep || (Sd.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
-      } else launchPT<false, true, 0>(Sd, job, blocks, st, deep);
+      } else if (drLights) launchPT<false, true, 0, false, true>(Sd, job, blocks, st, deep);
+      else launchPT<false, true, 0>(Sd, job, blocks, st, deep);
     }
     else if (film) {
       if (inRays) launchPT<false, false, 6>(c->S, job, blocks, st, deep); else if (naive) launchPT<false, false, 5>(c->S, job, blocks, st, deep); else launchPT<false, false, 4>(c->S, job, blocks, st, deep);
@@ -3250,7 +3264,7 @@ try {
   if (!c) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
   for (TexRec& t : c->hTextures) { t.diffOffset = ~0ull; t.diffW = t.diffH = t.diffChannels = 0; }
-  c->gradSize = 0;
+  c->gradSize = 0; c->diffLightFirst = c->diffLightCount = 0; c->diffLightOff = 0;
   if (!c->hTextures.empty()) HIPCHK(c, c->dTextures.upload(c->hTextures.data(), c->hTextures.size()));
   return HPT_OK;
 }
@@ -3276,6 +3290,27 @@ try {
   return HPT_OK;
 }
 catch (...) { return hptGuard(c, "hpt_put_diff_tex2d"); }
+
+// Light-colour gradients (no counterpart in the reference): lights [firstLight, firstLight + count) of the uploaded m_lights get an RGB gain each,
+// four floats per light appended to the parameter vector as hpt_put_diff_tex2d appends a texture (the fourth is padding: never read, its gradient
+// stays 0). PathTraceDR / PathTraceVJP then evaluate such a light from intensity * gain and return d loss / d gain in a_dataGrad.
+extern "C" int hpt_put_diff_lights(hpt_ctx* c, uint32_t firstLight, uint32_t count, uint64_t* outOffset, uint64_t* outSize)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (!outOffset || !outSize) return c->fail(HPT_ERR_ARG, "PutDiffLights: null out-pointer");
+  if (count == 0) return c->fail(HPT_ERR_ARG, "PutDiffLights: count is 0");
+  if (!c->sceneUploaded || (uint64_t)firstLight + count > c->S.numLights)
+    return c->fail(HPT_ERR_ARG, "PutDiffLights: lights [" + std::to_string(firstLight) + ", " + std::to_string((uint64_t)firstLight + count) + ") reach past the " + std::to_string(c->sceneUploaded ? c->S.numLights : 0u) + " uploaded lights");
+  if (c->diffLightCount != 0u) return c->fail(HPT_ERR_ARG, "PutDiffLights: lights are already registered on this context (hpt_reset_diff_tex clears the registration)");
+  if ((c->gradSize % 4) != 0) return c->fail(HPT_ERR_ARG, "PutDiffLights: the gains must start at a multiple of 4 floats (as 4-channel textures)");
+  const uint64_t sz = 4ull * count;
+  if (c->gradSize + sz > (uint64_t(1) << 31)) return c->fail(HPT_ERR_UNSUPPORTED, "PutDiffLights: more than 2^31 parameters (the gradient scatter indexes a_dataGrad with 31 bits)");
+  c->diffLightFirst = firstLight; c->diffLightCount = count; c->diffLightOff = c->gradSize;
+  *outOffset = c->gradSize; *outSize = sz;
+  c->gradSize += sz;
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_put_diff_lights"); }
 
 extern "C" int hpt_path_trace_dr_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum,
                                      const float* refDev, const float* dataDev, float* gradDev, size_t gradSize, float* lossDev, void* stream)

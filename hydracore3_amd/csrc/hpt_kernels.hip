@@ -23,9 +23,10 @@
 
 namespace hpt {
 
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED>
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED, bool LGRAD>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job)
 {
+  static_assert(!LGRAD || (DR && !STATS), "light-colour gradients: the uninstrumented DR kernel");
   constexpr bool NAIVE = (MODE == 1 || MODE == 5), INRAYS = (MODE == 2 || MODE == 6), LEAN = (MODE == 3), FILM = (MODE >= 4 && MODE <= 6);   // (MODE 7 = MODE 0 built for one more wave per SIMD)
   __shared__ uint stackMem[LDS_STACK * 256];
   const uint glane = blockIdx.x * 256u + threadIdx.x;                    // slot in the per-lane HBM buffers
@@ -37,6 +38,13 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   __shared__ float coldPix[3 * 256];
   __shared__ uint  coldU[(SLICED ? 5 : 3) * 256];
   __shared__ uint  drStage[DR ? 4 * DR_STAGE_DWORDS : 1];               // PathTraceDR: the waves' staging areas of the cooperative gradient scatter
+  // light-colour gradients (LGRAD): the workgroup's bins and the light plane of the adjoint record (hpt_shade.h). The bounce terms live in the
+  // record, not in registers: they must outlast the path (PathTraceDR's seed is known at its end) and four dwords for each of up to 16 bounces
+  // are not to be had in a kernel that fills its 128 VGPRs at four waves per SIMD.
+  float* lightBins = drLightBins<LGRAD>();
+  const DrLights lightReg = { LGRAD ? job.drLightFirst : 0u, LGRAD ? job.drLightCount : 0u, LGRAD ? job.drLightOff : 0u };
+  float4* lightPlane = LGRAD ? drLightPlane(job.record, job.recordLanes, S.traceDepth) : nullptr;
+  if (LGRAD) drLightBinsClear(lightBins);
 #define PIX(k)      coldPix[(k) * 256 + threadIdx.x]
 #define PIX_XY      coldU[0 * 256 + threadIdx.x]
 #define PIX_TID     coldU[1 * 256 + threadIdx.x]
@@ -218,10 +226,11 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     for (int k = 0; k < 4; k++) { recTaps.off[k] = 0; recTaps.w[k] = 0.0f; }
     recTaps.fx = recTaps.fy = 0.0f; recTaps.base = recTaps.ch = 0u;
 
+    DrLightVtx lv; lv.reg = lightReg; lv.sLight = lv.tLight = 0xFFFFFFFFu; lv.sUnit = lv.tUnit = v3(0, 0, 0);   // (LGRAD only)
     if (alive) {
       if (STATS && hit.inst != 0xFFFFFFFFu) nHits++;
-      didBounce = shadeVertex<DR, NAIVE, LEAN, MOTION, FILM>(S, job.data, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
-                                                 wantShadow, shPos, shDir, shFar, contrib, recA, recS, recdA, recdS, recTaps, recTex, tailR, pathTime);
+      didBounce = shadeVertex<DR, NAIVE, LEAN, MOTION, FILM, PseudoRands, LGRAD>(S, job.data, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
+                                                 wantShadow, shPos, shDir, shFar, contrib, recA, recS, recdA, recdS, recTaps, recTex, tailR, pathTime, PseudoRands(), &lv);
     }
 
     STAMP(2);
@@ -230,7 +239,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       HitRec sh;
       const bool occluded = traceAny<true, STATS, DEEP, FLAT, MOTION, SWEEP>(S, shPos, shDir, 0.0f, shFar, sh, stk, st, pathTime);
       if (STATS) { nRays++; nShadow++; }
-      if (!occluded) accum = accum + contrib; else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); }
+      if (!occluded) accum = accum + contrib; else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); if (LGRAD) lv.sLight = 0xFFFFFFFFu; }
     } else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); }
 
     STAMP(3);
@@ -238,6 +247,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     bool closing = false;                              // DR: this lane's path ended in this trip and its gradient is to be scattered
     V3 sweepSeed = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
     DrRec lastRec = drEmptyRecord(); bool lastInRegs = false;
+    const V3 lightTail = thr * lv.tUnit;                  // (LGRAD) T_n * tail_unit: an emitter hit leaves the throughput as it was
     if (alive) {
       if (didBounce) bounce++;
       const bool ended = (flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= maxBounce;
@@ -249,6 +259,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 #ifndef HPT_DBG_DR_NOSTORE   // diagnostic builds only (profiles/dr_ab.sh): what do the record stores cost?
         if (!ended) drStoreRecord(job.record, job.recordLanes, glane, bounce - 1u, lastRec);
 #endif
+        if (LGRAD) drStoreLightTerm(lightPlane, job.recordLanes, glane, bounce - 1u, lv.sLight, thrBefore * lv.sUnit);   // (also the last bounce's: the sweep reads every level from the plane)
         if (STATS) { nRec++; if (recTex != 0xFFFFFFFFu) nRecTex++; if (!ended) nRecStored++; }
         STAMP(5);
       }
@@ -310,6 +321,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
         drReverseSweep(S, job.record, job.recordLanes, glane, closing, bounce, sweepTail, sweepSeed, job.grad, job.drSkipNonFinite != 0u,
                        drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, lastRec, lastInRegs, STATS ? &nAtomInst : nullptr);
 #endif
+        if (LGRAD) drLightSweep(S, lightPlane, job.recordLanes, glane, closing, bounce, sweepSeed, lv.tLight, lightTail, lightBins, job.grad, lightReg, job.drSkipNonFinite != 0u);
       }
       STAMP(6);
     }
@@ -352,6 +364,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       if ((threadIdx.x & 63) == 0 && x) atomicAdd(&job.counters->v[i], x);
     }
   }
+  if (LGRAD) drLightFlush(lightBins, job.grad, lightReg);
   if (DR && job.vjp == 0u) {
     float x = lossLocal;
     for (int o = 32; o > 0; o >>= 1) x += __shfl_down(x, o);
@@ -375,7 +388,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   template __global__ void pathTraceKernel<false, false, MODE, true,  true,  false, false, true>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<false, false, MODE, false, false, false, true,  true>(const DevScene, const Job);
 #ifndef HPT_INST_GROUP
-#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..19"
+#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..20"
 #endif
 #if HPT_INST_GROUP == 1      // gltf + emissive scenes (every benchmark workload)
 HPT_INST4(false, false, 3)
@@ -389,6 +402,12 @@ HPT_INST4(false, false, 2)
 HPT_INST4(true, false, 0)
 #elif HPT_INST_GROUP == 6    // PathTraceDR
 HPT_INST4(false, true, 0)
+#elif HPT_INST_GROUP == 20   // PathTraceDR / PathTraceVJP with light-colour gradients (hpt_put_diff_lights)
+template __global__ void pathTraceKernel<false, true, 0, false, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, true,  false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, false, true,  false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, true,  true,  false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, false, false, false, true,  false, true>(const DevScene, const Job);
 #elif HPT_INST_GROUP == 15   // PathTraceDR, instrumented (phase stamps, record / sweep / atomic counts: profiles/dr_phases.py)
 HPT_INST4(true, true, 0)
 #elif HPT_INST_GROUP == 9    // scenes with thin films (MODE 4 / 5 / 6 = 0 / 1 / 2 + MAT_TYPE_THIN_FILM)

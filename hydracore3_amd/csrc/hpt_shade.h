@@ -245,6 +245,12 @@ struct PseudoRands
   HPT_DEV float blend(Rng& gen, uint /*bounce*/, uint /*layer*/) const { return rng_float1(gen); }
 };
 
+// Light-colour gradients: lights [first, first + count) own an RGB gain each, a_data[off + 4 i + 0..2] for light first + i.
+// The LGRAD instantiations of shadeVertex start lightIntensity() of such a light from intensity * gain and hand back, per unit gain, what the
+// vertex took from it: the light sample's shade (sLight / sUnit) and the emitter hit's tail (tLight / tUnit); 0xFFFFFFFF: no registered light.
+struct DrLights { uint first, count, off; };
+struct DrLightVtx { DrLights reg; uint sLight; V3 sUnit; uint tLight; V3 tUnit; };
+
 // Shades the vertex a closest-hit query returned for one path.  All path registers are passed by reference and the
 // function is always inlined, so both callers keep them in VGPRs.  Returns true when the path continues (didBounce).
 // A miss only sets the OUT_OF_SCENE flags.  The caller traces the shadow ray (if wantShadow) and adds `contrib`.
@@ -252,12 +258,15 @@ struct PseudoRands
 // LEAN: the scene holds gltf and emissive materials only (the host checked): the conductor / diffuse / glass / dielectric branches are
 // compiled out - fewer live registers and spills in the kernels every benchmark scene runs (the DR variant is lean by definition).
 // FILM: the scene holds thin films (MAT_TYPE_THIN_FILM, hpt_film.h): their branches exist in the FILM variants only.
-template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false, class RANDS = PseudoRands>
+// LGRAD (with DR): light-colour gradients, `lv` is read and filled (DrLightVtx); the other instantiations never look at it.
+template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false, class RANDS = PseudoRands, bool LGRAD = false>
 HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec& hit,
                          V3& rpos, V3& rdir, V3& accum, V3& thr, float& misPdf, float& misIor, uint& flags, const uint bounce, Rng& gen,
                          bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V3& contrib,
-                         V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f, const RANDS rands_ = RANDS())
+                         V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f, const RANDS rands_ = RANDS(),
+                         DrLightVtx* lv = nullptr)
 {
+  static_assert(!LGRAD || DR, "light-colour gradients: the differentiable kernels only");
   // the lean forward kernels (Lambert-heavy benchmark scenes: waves of one lobe) evaluate only what a vertex uses; see gltfSampleAndEvalC
   constexpr bool LEAN_FWD = LEAN && !DR;
   bool didBounce = false;
@@ -370,7 +379,13 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
           else if (L.geomType == LIGHT_GEOM_POINT) misWeight = 1.0f;
           const bool isDirectLight = (flags & RAY_FLAG_HAS_NON_SPEC) == 0;
           if ((S.renderLayer == FB_DIRECT && !isDirectLight) || (S.renderLayer == FB_INDIRECT && isDirectLight)) misWeight = 0.0f;
-          const V3 lightColor = lightIntensity(S, L, shadowRayPos, shadowRayDir);
+          V3 lightColor;
+          if (LGRAD && (uint)lightId - lv->reg.first < lv->reg.count) {  // a registered light: intensity * gain first, then the expression as it is
+            const float* gain = diffData + lv->reg.off + 4u * ((uint)lightId - lv->reg.first);
+            lightColor = lightIntensityFrom(S, L, ld3(L.intensity) * v3(gain[0], gain[1], gain[2]), shadowRayPos, shadowRayDir);
+            const V3 unitColor = lightIntensity(S, L, shadowRayPos, shadowRayDir);
+            lv->sLight = (uint)lightId; lv->sUnit = ((unitColor * bv.val) / lgtPdfW) * cosThetaOut * misWeight;   // d shade / d gain, whatever the gain is
+          } else lightColor = lightIntensity(S, L, shadowRayPos, shadowRayDir);
           shade = ((lightColor * bv.val) / lgtPdfW) * cosThetaOut * misWeight;
           if (DR) dshade = ((lightColor * bv.dval) / lgtPdfW) * cosThetaOut * misWeight;
           wantShadow = true;
@@ -382,7 +397,8 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
     // -- kernel_NextBounce (integrator_pt.cpp:426-548) --
     if (mtype == MAT_TYPE_LIGHT_SOURCE) {
       const uint lightId = (uint)S.remapInst[2 * instId + 1];
-      V3 lightInt = v3(0, 0, 0);
+      V3 lightInt = v3(0, 0, 0), unitInt = v3(0, 0, 0);                  // unitInt (LGRAD): the emission of a registered light per unit gain
+      bool unitSet = false;
       float misWeight = 1.0f;
       if (!LEAN_FWD || lightId == 0xFFFFFFFFu) {                       // (a mesh bound to a light discards this value: the lean forward kernels do not fetch it then)
         const V4 tc = texSample(S.textures, m.texid[0], mulRows2x4(m.row0[0], m.row1[0], uv));
@@ -392,7 +408,11 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
         const LightRec& L = S.lights[lightId];
         const float lightCos = dot(rdir, ld3(L.norm));
         const float atten = (lightCos < 0.0f || L.geomType == LIGHT_GEOM_SPHERE) ? 1.0f : 0.0f;
-        lightInt = lightIntensity(S, L, rpos, rdir) * atten;
+        if (LGRAD && lightId - lv->reg.first < lv->reg.count) {
+          const float* gain = diffData + lv->reg.off + 4u * (lightId - lv->reg.first);
+          lightInt = lightIntensityFrom(S, L, ld3(L.intensity) * v3(gain[0], gain[1], gain[2]), rpos, rdir) * atten;
+          unitInt = lightIntensity(S, L, rpos, rdir) * atten; unitSet = true;
+        } else lightInt = lightIntensity(S, L, rpos, rdir) * atten;
       }
       if (S.integratorType == INTEGRATOR_MIS_PT) {
         if (bounce > 0 && lightId != 0xFFFFFFFFu) {
@@ -406,6 +426,7 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
       if (S.renderLayer == FB_INDIRECT && (isDirectLight || isFirstNonSpec)) misWeight = 0.0f;
       accum = accum + thr * lightInt * misWeight;
       if (DR) tailR = lightInt * misWeight;
+      if (LGRAD && unitSet) { lv->tLight = lightId; lv->tUnit = unitInt * misWeight; }
       flags |= (RAY_FLAG_IS_DEAD | RAY_FLAG_HIT_LIGHT);
     } else {
       // The reference keeps the hit's material id in the low 24 bits of the ray flags (packMatId, integrator_pt.h:340-341, set at
@@ -521,12 +542,97 @@ HPT_DEV void drStoreRecord(float* record, size_t s, size_t idx, uint bounce, con
   if (r.e0 != 0xFFFFFFFFu) *(float*)(q + 4 * s) = r.fy;
 }
 // the light sample of bounce b turned out occluded: its S term and derivative vanish
-HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce)
+HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce, float4* lightPlane = nullptr)
 {
   float* q = (float*)((float4*)record + ((size_t)bounce * REC_PLANES) * s + idx);
   q[3] = 0.0f;                                                              // S.x
   q[4 * s + 0] = 0.0f; q[4 * s + 1] = 0.0f;                                 // S.yz
   q[8 * s + 1] = 0.0f; q[8 * s + 2] = 0.0f; q[8 * s + 3] = 0.0f;            // T*dS
+  if (lightPlane) *(uint*)(lightPlane + (size_t)bounce * s + idx) = 0xFFFFFFFFu;   // ... and so does the light term (light-colour gradients)
+}
+
+// ---- light-colour gradients: the light plane of the adjoint record and the binned reduction ----------------------------------
+// The colour of a sample is linear in the gain of every registered light: C = C_0 + sum_l g_l C_l, so dC/dg_l is what the path took from light l
+// per unit gain: T_b * shade_unit at the bounces whose light sample was light l and came back unoccluded, T_n * tail_unit where the path ended on
+// its mesh. A sixth plane beside the five of DrRec keeps the bounce terms, one float4 per slot and bounce, (light, T_b * shade_unit.xyz), laid out
+// [bounce][slot] behind the records of all bounces (the seed of PathTraceDR is only known at the path's end); light = 0xFFFFFFFF: no term.
+HPT_DEV float4* drLightPlane(float* record, size_t s, uint traceDepth) { return (float4*)record + ((size_t)(traceDepth + 1u) * REC_PLANES) * s; }
+HPT_HD size_t drLightPlaneFloats(size_t s, uint traceDepth) { return 4u * s * traceDepth; }
+HPT_DEV void drStoreLightTerm(float4* plane, size_t s, size_t idx, uint bounce, uint light, V3 term)
+{
+  plane[(size_t)bounce * s + idx] = make_float4(__uint_as_float(light), term.x, term.y, term.z);
+}
+// Texture gradients scatter to millions of addresses; these go to 3 * count words every wave of the chip wants to add to at once - the case
+// MI355X_MICROARCH.md ("Global float atomics") measures at 14 x below the atomic rate. So a workgroup first adds into bins of its own in LDS,
+// [light - first][rgb] for the first DR_LIGHT_BINS registered lights (f32 LDS adds; lanes on one bin are serialised by the LDS, not by a round
+// trip to L2), and sends its non-zero bins out once, at the end of the launch: at most one global atomic per (workgroup, light, channel, launch).
+// 64 bins = 768 bytes: the DR megakernel holds 38 912 bytes of LDS per block, 31 allocation units of 1280 bytes are 39 680, and four blocks of
+// that size share a CU's 160 KB - its residency of four waves per SIMD - so 768 bytes are what the kernel has to spare without touching it.
+// Lights past the bins go straight to memory, but merged first: the wave ballots over the key and every distinct key costs one atomic
+// wave-instruction (three lanes, one per channel), not one request per lane.
+static const uint DR_LIGHT_BINS = 64u;
+template <bool ON> HPT_DEV float* drLightBins()
+{
+  if constexpr (ON) { __shared__ float bins[3u * DR_LIGHT_BINS]; return bins; }
+  else return nullptr;
+}
+HPT_DEV void drLightBinsClear(float* bins)
+{
+  for (uint i = threadIdx.x; i < 3u * DR_LIGHT_BINS; i += 256u) bins[i] = 0.0f;
+  __syncthreads();
+}
+// by ALL lanes of the wave, wave-uniform control flow; `has`: this lane holds g = seed * term for registered light first + k
+HPT_DEV void drLightAdd(float* bins, float* gain0, const bool has, const uint k, const V3 g)
+{
+#ifdef HPT_LGRAD_NAIVE       // diagnostic build only (profiles/light_grad.py): every term straight to a global atomic
+  if (has) { atomicAdd(gain0 + 4u * (size_t)k + 0u, g.x); atomicAdd(gain0 + 4u * (size_t)k + 1u, g.y); atomicAdd(gain0 + 4u * (size_t)k + 2u, g.z); }
+  (void)bins;
+#else
+  if (has && k < DR_LIGHT_BINS) {
+    __hip_atomic_fetch_add(bins + 3u * k + 0u, g.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(bins + 3u * k + 1u, g.y, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    __hip_atomic_fetch_add(bins + 3u * k + 2u, g.z, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  const bool past = has && k >= DR_LIGHT_BINS;
+  unsigned long long todo = __ballot(past);
+  const uint lane = lane_id();
+  while (todo != 0ull) {                                                    // one trip per distinct key among the wave's lanes
+    const uint key = (uint)__shfl((int)k, (int)(__ffsll((long long)todo) - 1));
+    const bool match = past && k == key;
+    V3 x = match ? g : v3(0, 0, 0);
+    for (int o = 32; o > 0; o >>= 1) { x.x += __shfl_xor(x.x, o); x.y += __shfl_xor(x.y, o); x.z += __shfl_xor(x.z, o); }   // every lane ends with the sum
+    if (lane < 3u) atomicAdd(gain0 + 4u * (size_t)key + lane, lane == 0u ? x.x : (lane == 1u ? x.y : x.z));
+    todo &= ~__ballot(match);
+  }
+#endif
+}
+// The light terms of the paths that closed in this trip: called by ALL lanes of the wave in wave-uniform control flow, as drReverseSweep is.
+// Level b < traceDepth: the light sample of bounce b, from the light plane; level traceDepth: the emitter hit, from registers.
+HPT_DEV void drLightSweep(const DevScene& S, const float4* plane, size_t s, size_t idx, const bool closing, const uint bounceIn, const V3 seed,
+                          const uint tailLight, const V3 tailTerm, float* bins, float* grad, const DrLights reg, const bool skipNonFinite)
+{
+  const uint bounce = closing ? bounceIn : 0u;
+  for (uint b = 0; b <= S.traceDepth; b++) {                                // wave-uniform trip count
+    uint light = 0xFFFFFFFFu; V3 t = v3(0, 0, 0);
+    if (b < S.traceDepth) {
+      if (b < bounce) { const float4 q = plane[(size_t)b * s + idx]; light = __float_as_uint(q.x); t = v3(q.y, q.z, q.w); }
+    } else if (closing) { light = tailLight; t = tailTerm; }
+    const bool has = light != 0xFFFFFFFFu;
+    if (__ballot(has) == 0ull) continue;
+    V3 g = v3(seed.x * t.x, seed.y * t.y, seed.z * t.z);
+    if (skipNonFinite && !__builtin_isfinite(g.x + g.y + g.z)) g = v3(0, 0, 0);   // (dr_skip_nonfinite: as the texture terms)
+    drLightAdd(bins, grad + reg.off, has, light - reg.first, g);
+  }
+}
+// end of the launch: the workgroup's non-zero bins, one global atomic each
+HPT_DEV void drLightFlush(const float* bins, float* grad, const DrLights reg)
+{
+  __syncthreads();
+  for (uint i = threadIdx.x; i < 3u * DR_LIGHT_BINS; i += 256u) {
+    const uint k = i / 3u, ch = i - 3u * k;
+    const float v = bins[i];
+    if (k < reg.count && v != 0.0f) atomicAdd(grad + reg.off + 4u * (size_t)k + ch, v);
+  }
 }
 // Hand-derived reverse sweep replacing __enzyme_autodiff (integrator_dr.cpp:1172-1183). With T_0 = 1, T_{b+1} = T_b A_b and
 // C = sum_b T_b S_b + T_n tail:  dC/dtex_b = T_b dS_b + T_b dA_b R_{b+1},  R_b = S_b + A_b R_{b+1},  R_n = tail;  the gradient

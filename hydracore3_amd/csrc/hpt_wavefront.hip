@@ -26,7 +26,7 @@
 
 namespace hpt {
 
-#if !defined(HPT_WF_INST) || HPT_WF_INST != 2      // (small kernels: emitted once, with the shade kernels)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3)      // (small kernels: emitted once, with the shade kernels)
 __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 {
   const uint i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -34,10 +34,17 @@ __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 }
 #endif
 
-template <bool DR, bool LEAN, bool MOTION, bool FILM>
+template <bool DR, bool LEAN, bool MOTION, bool FILM, bool LGRAD>
 __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const WfPool P, const WfJob job)
 {
+  static_assert(!LGRAD || DR, "light-colour gradients: the DR shade kernel");
   __shared__ uint drStage[DR ? 4 * DR_STAGE_DWORDS : 1];                   // the waves' staging areas of the cooperative gradient scatter (drReverseSweep)
+  // light-colour gradients (LGRAD): the workgroup's bins, flushed at the end of this pass, and the light plane of the adjoint record (hpt_shade.h)
+  float* lightBins = drLightBins<LGRAD>();
+  const DrLights lightReg = { LGRAD ? job.drLightFirst : 0u, LGRAD ? job.drLightCount : 0u, LGRAD ? job.drLightOff : 0u };
+  float4* lightPlane = LGRAD ? drLightPlane(job.record, job.itemCount, S.traceDepth) : nullptr;
+  uint tailLight = 0xFFFFFFFFu; V3 tailTerm = v3(0, 0, 0);
+  if (LGRAD) drLightBinsClear(lightBins);
   const uint s = blockIdx.x * 256u + threadIdx.x;
   uint* ctr = P.ctr + WF_CTR_WORDS * (job.iter & 1u);
   if (s <= WF_RANGES) P.ctr[WF_CTR_WORDS * ((job.iter + 1u) & 1u) + 32u * s] = 0u;   // counters of the NEXT round (its trace pass is long done)
@@ -71,7 +78,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
     // (6') the shadow ray traced since the last visit: add the candidate contribution in the megakernel's order
     if (pend) {
       if (ldP(&P.occl[s]) == 0u) { const float4 c = ldP(&P.contrib[s]); accum = accum + v3(c.x, c.y, c.z); }
-      else if (DR && bounce > 0u) drClearShadowTerm(job.record, job.itemCount, s, bounce - 1u);   // the light sample of the last vertex was occluded
+      else if (DR && bounce > 0u) drClearShadowTerm(job.record, job.itemCount, s, bounce - 1u, lightPlane);   // the light sample of the last vertex was occluded
       pend = false;
     }
     bool finalize = ending;                                                // path ended last time, only its shadow ray was outstanding
@@ -89,8 +96,10 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
       for (int k = 0; k < 4; k++) { taps.off[k] = 0; taps.w[k] = 0.0f; }
       taps.fx = taps.fy = 0.0f; taps.base = taps.ch = 0u;
       const V3 thrBefore = thr;
-      const bool didBounce = shadeVertex<DR, false, LEAN, MOTION, FILM>(S, DR ? job.data : nullptr, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
-                                                    wantShadow, shPos, shDir, shFar, contrib, rA, rS, rdA, rdS, taps, recTex, tailR, pathTime);
+      DrLightVtx lv; lv.reg = lightReg; lv.sLight = lv.tLight = 0xFFFFFFFFu; lv.sUnit = lv.tUnit = v3(0, 0, 0);   // (LGRAD only)
+      const bool didBounce = shadeVertex<DR, false, LEAN, MOTION, FILM, PseudoRands, LGRAD>(S, DR ? job.data : nullptr, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
+                                                    wantShadow, shPos, shDir, shFar, contrib, rA, rS, rdA, rdS, taps, recTex, tailR, pathTime, PseudoRands(), &lv);
+      if (LGRAD) { tailLight = lv.tLight; tailTerm = thr * lv.tUnit; }       // T_n * tail_unit: an emitter hit leaves the throughput as it was
       if (didBounce) bounce++;
       const bool ended = (flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= S.traceDepth;
       if (DR && didBounce) {
@@ -99,6 +108,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
         // a path that ends here with no shadow ray outstanding is swept in this pass: its last record never leaves the registers
         lastInRegs = ended && !wantShadow;
         if (!lastInRegs) drStoreRecord(job.record, job.itemCount, s, bounce - 1u, lastRec);
+        if (LGRAD) drStoreLightTerm(lightPlane, job.itemCount, s, bounce - 1u, wantShadow ? lv.sLight : 0xFFFFFFFFu, thrBefore * lv.sUnit);   // (cleared if its shadow ray comes back occluded)
       }
       if (ended) {
         if (!DR && (flags & RAY_FLAG_OUT_OF_SCENE) != 0) {                  // kernel_HitEnvironment (integrator_pt.cpp:550-595)
@@ -165,6 +175,8 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
     drReverseSweep(S, job.record, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepTail, sweepSeed, job.grad, job.drSkipNonFinite != 0u,
                    drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, lastRec, lastInRegs, nullptr, 64u, false);
 #endif
+  if (LGRAD && __any(closing))
+    drLightSweep(S, lightPlane, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepSeed, tailLight, tailTerm, lightBins, job.grad, lightReg, job.drSkipNonFinite != 0u);
   // ray compaction: ballot + prefix sum, one atomic per wave and queue
   const bool qNear = active && alive, qShad = active && wantShadow;
   uint kn, ks;
@@ -172,9 +184,10 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   uint* rayQ = P.rayQ[job.iter & 1u];
   if (qNear) stP(&rayQ[kn], s);
   if (qShad) stP(&rayQ[ks], s | 0x80000000u);
+  if (LGRAD) drLightFlush(lightBins, job.grad, lightReg);
 }
 
-#if !defined(HPT_WF_INST) || HPT_WF_INST != 2
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3)
 // DR: sum of the per-slot losses in double, one atomic per block; wfLossFinishKernel adds the total to the caller's float
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc)
 {
@@ -445,7 +458,7 @@ __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScen
 
 // ---- explicit instantiations (the host launches them through the declarations in hpt_decl.h) -----------------------------------------------
 #ifndef HPT_WF_INST
-#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only
+#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 1
 template __global__ void wfShadeKernel<true, true>(const DevScene, const WfPool, const WfJob);
@@ -454,6 +467,9 @@ template __global__ void wfShadeKernel<false, false>(const DevScene, const WfPoo
 template __global__ void wfShadeKernel<false, false, true>(const DevScene, const WfPool, const WfJob);     // moving instances (every BSDF branch)
 template __global__ void wfShadeKernel<false, false, false, true>(const DevScene, const WfPool, const WfJob);   // thin films
 template __global__ void wfShadeKernel<false, false, true, true>(const DevScene, const WfPool, const WfJob);    // thin films and moving instances
+#endif
+#if HPT_WF_INST == 0 || HPT_WF_INST == 3
+template __global__ void wfShadeKernel<true, true, false, false, true>(const DevScene, const WfPool, const WfJob);   // light-colour gradients (hpt_put_diff_lights)
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 2
 #define HPT_WFT(DEEP, FLAT, STATS) template __global__ void wfTraceKernel<DEEP, FLAT, STATS>(const DevScene, const WfPool, uint, uint, uint, uint*, uint, Counters*);

@@ -6,7 +6,7 @@
 //                                  kernel_slicer-generated Integrator_Generated overrides (main.cpp:221-224) --
 //                                  PathTraceBlock, NaivePathTraceBlock, EvalGBuffer, CastSingleRayBlock, RayTraceBlock, PackXYBlock, CommitDeviceData,
 //                                  UpdateMembersPlainData, GetExecutionTime, Update_m_materials / Update_m_lights
-//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136): PutDiffTex2D, PathTraceDR, PathTraceVJP, RayTraceDR
+//   hydra_hip::IntegratorDRHIP <-> IntegratorDR                      (diff_render/integrator_dr.h:27-136): PutDiffTex2D, PutDiffLights, PathTraceDR, PathTraceVJP, RayTraceDR
 //
 // The reference's headers cannot be included here (they need the absent LiteMath), so this header carries the same
 // member names over plain arrays; INTEGRATION.md shows the dozen lines that derive the real `Integrator` from it.
@@ -294,6 +294,14 @@ public:
   {
     uint64_t off = 0, size = 0;
     if (!m_ctx || hpt_put_diff_tex2d(m_ctx, texId, width, height, channels, &off, &size) != HPT_OK) return std::make_pair(size_t(-1), size_t(0));
+    return std::make_pair(size_t(off), size_t(size));
+  }
+  // PutDiffLights (no counterpart in the reference): lights [first, first + count) get an RGB gain each, a_data[offset + 4 i + 0..2] for light
+  // first + i (float 4 i + 3 is padding), and PathTraceDR / PathTraceVJP return d loss / d gain there. Returns (offset, size); (size_t(-1), 0) on an error.
+  std::pair<size_t, size_t> PutDiffLights(uint32_t first, uint32_t count)
+  {
+    uint64_t off = 0, size = 0;
+    if (!m_ctx || hpt_put_diff_lights(m_ctx, first, count, &off, &size) != HPT_OK) return std::make_pair(size_t(-1), size_t(0));
     return std::make_pair(size_t(off), size_t(size));
   }
   virtual void SetMaxThreadsAndBounces(int /*a_maxThreads*/, int a_maxBounce) { m_traceDepth = uint32_t(a_maxBounce); }   // no per-CPU-thread records on the GPU

@@ -61,7 +61,9 @@ def render(integrator, params, spp):
     """The frame of `integrator` (a HipIntegrator with its differentiable textures registered by PutDiffTex2D) with the parameters `params`:
     a [H, W, 4] float32 tensor on the GPU, the SUM over `spp` samples per pixel (divide by spp for the mean), differentiable with respect to
     `params`. params: a contiguous float32 tensor on the integrator's device with at least the registered number of elements; anything else
-    raises ValueError before any device work. Each call draws new samples (m_randomGens goes on); backward replays forward's."""
+    raises ValueError before any device work. Each call draws new samples (m_randomGens goes on); backward replays forward's.
+    Light colours need no argument of their own: the RGB gains of the lights registered by PutDiffLights are elements of `params` (at the
+    offset PutDiffLights returned, four floats per light, the fourth unused), and `params.grad` receives their gradient there."""
     _check(integrator, params)
     spp = int(spp)
     if spp < 1:

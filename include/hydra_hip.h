@@ -462,7 +462,16 @@ int  hpt_cam_get_execution_time(hpt_cam* cam, const char* funcName, float out[4]
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
-int  hpt_reset_diff_tex(hpt_ctx* ctx);                                                   /* LoadSceneEnd (integrator_dr.cpp:24-31) */
+int  hpt_reset_diff_tex(hpt_ctx* ctx);                                                   /* LoadSceneEnd (integrator_dr.cpp:24-31); also clears hpt_put_diff_lights */
+/* Light-colour gradients (no counterpart in the reference). Registers lights [firstLight, firstLight + count) of the uploaded m_lights as
+ * differentiable and appends 4 * count floats to the parameter vector, as hpt_put_diff_tex2d appends a texture: light firstLight + i owns
+ * a_data[*outOffset + 4 i + 0..2], its RGB gain; float 4 i + 3 is padding (never read, its gradient stays 0). *outSize = 4 * count; the offset
+ * must be a multiple of 4. PathTraceDR / PathTraceVJP (and their _dev forms) then evaluate such a light from intensity * gain - the frame and
+ * m_randomGens are, bit for bit, those of a scene whose intensities were multiplied on the host - and add d loss / d gain to a_dataGrad, taken
+ * per unit gain (exact at gain 0). Served by the megakernel and the wavefront schedule; an explicit block-local request is HPT_ERR_UNSUPPORTED.
+ * HPT_ERR_ARG, nothing changed: count 0, a range past the uploaded lights, a second registration on the context, a misaligned offset, null
+ * out-pointers. The registration survives hpt_update_lights; hpt_reset_diff_tex and a scene upload clear it. RayTraceDR ignores it. */
+int  hpt_put_diff_lights(hpt_ctx* ctx, uint32_t firstLight, uint32_t count, uint64_t* outOffset, uint64_t* outSize);
 /* IntegratorDR::PathTraceDR (integrator_dr.cpp:1135-1218). a_dataGrad is overwritten (zeroed first), out_color accumulated,
  * *outLoss receives the value the reference returns. Host-pointer form. */
 int  hpt_path_trace_dr(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color, uint32_t passNum,
