@@ -50,7 +50,8 @@ struct Job
   // Light-colour gradients (the LGRAD instantiations, hpt_put_diff_lights) share the storage of the input-ray pointers, which no DR kernel reads
   // (launch_path_trace fills them in after it has looked at inRayPos): DrLights' first, count and off.
   union { const float4* inRayPos; struct { uint drLightFirst, drLightCount; }; };   // inRayPos / inRayDir: PathTraceFromInputRays, RayPosAndW[tid] / RayDirAndT[tid] in camera space (MODE 2)
-  union { const float4* inRayDir; struct { uint drLightOff, drLightPad; }; };
+  // Environment maps in DR (the ENV instantiations; mutually exclusive with LGRAD) use the padding word: the env plane of the record exists.
+  union { const float4* inRayDir; struct { uint drLightOff, drLightPad; }; struct { uint drEnvPad, drEnvPlaneOn; }; };
 };
 static_assert(sizeof(Job) == 184, "Job is a by-value argument of every kernel family: its size and layout stay");
 
@@ -76,7 +77,8 @@ static_assert(sizeof(Job) == 184, "Job is a by-value argument of every kernel fa
 #define HPT_PT_BOUNDS(DR, MODE) __launch_bounds__(256, (DR) ? HPT_DR_WAVES : ((MODE) == 3 ? HPT_MIN_WAVES : ((MODE) == 7 ? HPT_FULL_WAVES + 1 : ((MODE) >= 4 ? HPT_FILM_WAVES : HPT_FULL_WAVES))))
 // SLICED: work items are runs of Job::passSlice passes of a pixel (instantiated for PathTrace from the camera: MODE 3, 0, 7 and moving instances)
 // LGRAD (with DR): light-colour gradients (hpt_shade.h: DrLights); the residency is the DR kernel's
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false, bool SLICED = false, bool LGRAD = false>
+// ENV (with DR, without LGRAD): environment maps and their texel gradients (hpt_shade.h: drEnvSweep); the residency is the DR kernel's
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false, bool SLICED = false, bool LGRAD = false, bool ENV = false>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job);
 
 // spectral rendering (hpt_spectral.hip): one thread per pixel, four wavelengths per path
@@ -155,7 +157,8 @@ struct WfJob
   // differentiable rendering (wfShadeKernel<DR = true>): a_refImg, a_data, a_dataGrad, loss accumulator, adjoint records [bounce][field][slot]
   const float* refImg; const float* data; float* grad; float* lossAccum; float* record;
   const float* adjImg; uint vjp;  // PathTraceVJP: as in Job
-  uint drLightFirst, drLightCount, drLightOff;   // light-colour gradients (wfShadeKernel<.., LGRAD>): DrLights; count 0 otherwise
+  union { uint drLightFirst; uint drEnvPlaneOn; };   // (wfShadeKernel<.., ENV>, where no light is registered: the env plane of the record exists)
+  uint drLightCount, drLightOff;                 // light-colour gradients (wfShadeKernel<.., LGRAD>): DrLights; count 0 otherwise
 };
 
 #ifndef HPT_WF_SHADE_FULL_WAVES
@@ -204,7 +207,7 @@ __global__ void __launch_bounds__(256, HPT_STREAM_WAVES) streamKernel(const DevS
                                                                       uint* stackOverflow, uint gridLanes);
 template <int SCOPE>                                                    // spectral rendering under the wavefront schedule (hpt_spectral.hip)
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) wfShadeSpecKernel(const DevScene S, const WfPool P, const WfJob job);
-template <bool DR, bool LEAN, bool MOTION = false, bool FILM = false, bool LGRAD = false>   // FILM: shadeVertex<FILM> (thin films, hpt_film.h); LGRAD (with DR): light-colour gradients
+template <bool DR, bool LEAN, bool MOTION = false, bool FILM = false, bool LGRAD = false, bool ENV = false>   // FILM: shadeVertex<FILM> (thin films, hpt_film.h); LGRAD (with DR): light-colour gradients; ENV (with DR): environment maps
 __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const WfPool P, const WfJob job);
 template <bool DEEP, bool FLAT, bool STATS, bool MOTION = false, bool WIDE = false>   // WIDE: walk DevScene::nodes4 (4-wide compressed nodes) instead of the BVH2
 __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScene S, const WfPool P, uint iter, uint refillBelow, uint grace,

@@ -171,6 +171,7 @@ struct hpt_ctx
   bool anyMotion = false;                                // some instance moves: the MOTION kernel variants (either BVH layout, either schedule; no sweep, no refit)
   std::vector<MaterialRec> hMaterials;                   // host mirror of m_materials: the blend graph is validated as a whole
   std::vector<uint> hLightGeom;                          // geomType of every light, to validate m_envLightId
+  std::vector<uint> hLightTex;                           // ... and its texId (dr_environment: is the map the env light reads registered?)
   std::vector<uint> hTriIndices;                         // host mirror of m_triIndices: Update_m_matIdOffsets re-validates the vertex indices a mesh will read
   bool envLightOk(uint id) const { return id < hLightGeom.size() && hLightGeom[id] == LIGHT_GEOM_ENV; }
   DevBuf<Rng> dGens;
@@ -217,6 +218,7 @@ struct hpt_ctx
   void* rcclLib = nullptr; void* comm = nullptr; int commRanks = 0, commRank = 0;
   bool forceFull = false;                // diagnostic (hpt_set_option "force_full_materials")
   bool drSkipNonFinite = false;          // hpt_set_option "dr_skip_nonfinite": off = PixelLossPT as the reference has it
+  bool drEnvironment = false;            // hpt_set_option "dr_environment": PathTraceDR / PathTraceVJP serve environment maps and their sampling (the ENV kernels)
   bool drGradMode = true;                // hpt_set_option "dr_grad_mode": IntegratorDR's m_gradMode, read by RayTraceDR only
   bool leanMaterials = false;            // every material is gltf or emissive: the kernels without the other BSDF branches are used
   int  schedule = 0;                     // 0 automatic, 1 megakernel, 2 wavefront, 3 megakernel with block-local ray repacking (hpt_set_schedule)
@@ -1603,6 +1605,8 @@ try {
   }
   c->hLightGeom.resize(d->numLights);
   for (uint i = 0; i < d->numLights; i++) c->hLightGeom[i] = ((const LightRec*)d->lights)[i].geomType;
+  c->hLightTex.resize(d->numLights);
+  for (uint i = 0; i < d->numLights; i++) c->hLightTex[i] = ((const LightRec*)d->lights)[i].texId;
   // a new scene invalidates the environment ids of the previous UpdateMembersPlainData until the next one
   S.envTexId = S.envLightId = S.envCamBackId = 0xFFFFFFFFu; S.envEnableSam = 0;
   c->sceneUploaded = true; c->shadeTrisDirty = true;
@@ -1690,7 +1694,7 @@ try {
   if (!c || !lights) return HPT_ERR_ARG;
   if (first + count > c->S.numLights) return c->fail(HPT_ERR_ARG, "Update_m_lights: range out of bounds");
   int rc = check_lights(c, (const LightRec*)lights, count, c->hTextures.size(), c->numArrays1f); if (rc) return rc;
-  for (size_t i = 0; i < count; i++) c->hLightGeom[first + i] = ((const LightRec*)lights)[i].geomType;
+  for (size_t i = 0; i < count; i++) { c->hLightGeom[first + i] = ((const LightRec*)lights)[i].geomType; c->hLightTex[first + i] = ((const LightRec*)lights)[i].texId; }
   (void)hipSetDevice(c->device);
   HIPCHK(c, hipMemcpy(c->dLights.p + first, lights, count * sizeof(LightRec), hipMemcpyHostToDevice));
   return HPT_OK;
@@ -1788,16 +1792,16 @@ static int gridBlocks(hpt_ctx* c, bool dr, bool fullMaterials = false)
 
 // DEEP: the scene's BVH can need more than LDS_STACK stack entries, so pushes / pops check for the HBM overflow part
 // FLAT: single-level world-space BVH (static scenes within FLAT_TRI_BUDGET) vs two-level TLAS/BLAS
-template <bool STATS, bool DR, int NAIVE, bool SLICED = false, bool LGRAD = false>   // LGRAD: PathTraceDR / PathTraceVJP with lights registered (hpt_put_diff_lights)
+template <bool STATS, bool DR, int NAIVE, bool SLICED = false, bool LGRAD = false, bool ENV = false>   // LGRAD: PathTraceDR / PathTraceVJP with lights registered (hpt_put_diff_lights); ENV: over an environment map ("dr_environment")
 static void launchPT(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
-  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   else if (S.flatMode) {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED, LGRAD><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -1914,9 +1918,27 @@ static void launchWfTrace(hpt_ctx* c, const DevScene& S, const WfPool& P, uint i
   }
 }
 
+// Environment maps in DR (hpt_set_option "dr_environment"): a DR call on a scene with a map or with env sampling runs the ENV
+// kernels; the env plane of the adjoint record exists when a map one of the two lookups reads is registered (hpt_put_diff_tex2d).
+static bool drEnvironmentCall(const hpt_ctx* c) { return c->drEnvironment && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u); }
+static bool drEnvMapRegistered(const hpt_ctx* c)
+{
+  const auto reg = [&](uint id) { return id < c->hTextures.size() && c->hTextures[id].diffOffset != ~0ull; };
+  return reg(c->S.envTexId) || (c->S.envLightId < c->hLightTex.size() && reg(c->hLightTex[c->S.envLightId]));
+}
+// the textures an ENV kernel reads through texFetchAD: m_envTexId (the tail) and the texId of every light (the lookup along the shadow ray)
+static bool drEnvReads(const hpt_ctx* c, uint texId)
+{
+  if (texId == 0xFFFFFFFFu) return false;
+  if (texId == c->S.envTexId) return true;
+  for (const uint t : c->hLightTex) if (t == texId) return true;
+  return false;
+}
 static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
 {
   const bool spec = specScope >= 0;
+  const bool drEnv = dr && drEnvironmentCall(c);               // (launch_path_trace has made the refusals)
+  const bool envPlane = drEnv && drEnvMapRegistered(c);
   DevScene Sw = c->S;
   if (spec) Sw.shadeTris = nullptr;                  // the spectral shade kernel fetches its surface through the primitive id: the trace pass must report that
   auto launchShade = [&](const dim3 sg, hipStream_t gs, const WfPool& P, const WfJob& wj) {
@@ -1925,6 +1947,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
       else if (specScope == 2) wfShadeSpecKernel<2><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else wfShadeSpecKernel<1><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
     }
+    else if (drEnv)            wfShadeKernel<true, true, false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (dr && wj.drLightCount != 0u) wfShadeKernel<true, true, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (dr)               wfShadeKernel<true, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (c->hasFilm)       { if (c->S.motion) wfShadeKernel<false, false, true, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj); else wfShadeKernel<false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj); }
@@ -1966,6 +1989,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   wj.adjImg = job.adjImg; wj.vjp = job.vjp;
   const bool drLights = dr && c->diffLightCount != 0u;        // (launch_path_trace has checked the registration against the scene)
   wj.drLightFirst = drLights ? job.drLightFirst : 0u; wj.drLightCount = drLights ? job.drLightCount : 0u; wj.drLightOff = drLights ? job.drLightOff : 0u;
+  if (drEnv) wj.drEnvPlaneOn = envPlane ? 1u : 0u;           // (shares drLightFirst's word: no light is registered then)
   // every path takes at most traceDepth shade passes after the one that generated it; the pass that ends it (or the next one, when a
   // shadow ray was outstanding) also generates the pixel's next path
   // safety net only (the loop ends when a round queues no ray): pixels whose rays were suspended sit rounds out, so there is no tight bound
@@ -1992,7 +2016,8 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
     HIPCHK(c, g.u[4].alloc(2 * WF_CTR_WORDS));
     HIPCHK(c, g.u[6].alloc(g.itemCount));
     HIPCHK(c, g.u[7].alloc(suspWords)); HIPCHK(c, g.u[8].alloc(suspWords));
-    if (dr) { HIPCHK(c, g.rec.alloc((size_t)g.itemCount * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(g.itemCount, c->S.traceDepth) : 0))); HIPCHK(c, g.lossSlot.alloc(g.itemCount)); }
+    if (dr) { HIPCHK(c, g.rec.alloc((size_t)g.itemCount * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(g.itemCount, c->S.traceDepth) : 0) +
+                                        (envPlane ? drEnvPlaneFloats(g.itemCount, c->S.traceDepth) : 0))); HIPCHK(c, g.lossSlot.alloc(g.itemCount)); }
     if (c->S.motion) HIPCHK(c, g.time.alloc(g.itemCount));
     if (spec) { HIPCHK(c, g.waves.alloc(g.itemCount)); HIPCHK(c, g.fb.alloc(g.itemCount)); }
     WfPool& P = pools[gi];
@@ -2132,8 +2157,11 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (dr && c->S.motion) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: motion blur is not differentiated");
   // the DR kernels add the constant m_envColor unweighted; the reference's replay evaluates EnvironmentColor() with the map and the
   // env-sampling MIS weight (integrator_dr.cpp:1077-1098): such scenes are refused rather than differentiated differently
-  if (dr && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u || c->S.envCamBackId != 0xFFFFFFFFu))
+  // hpt_set_option("dr_environment", 1) serves the map and its sampling (the ENV kernels); the replay has no back plate at all
+  if (dr && !c->drEnvironment && (c->S.envTexId != 0xFFFFFFFFu || c->S.envEnableSam != 0u || c->S.envCamBackId != 0xFFFFFFFFu))
     return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: environment maps, their sampling and camera back plates are not differentiated (constant m_envColor only)");
+  if (dr && c->S.envCamBackId != 0xFFFFFFFFu)
+    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: a camera back plate (m_envCamBackId) is not differentiated: the reference's replay has none");
   if (dr && !c->leanMaterials) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: gltf and emissive materials without normal maps only (what the reference's replay differentiates, integrator_dr.cpp:461-612)");
   // light-colour gradients (hpt_put_diff_lights): served by the megakernel and the wavefront schedule
   const bool drLights = dr && c->diffLightCount != 0u;
@@ -2142,6 +2170,18 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (drLights && c->schedule == 3)
     return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the block-local schedule has no light-gradient variant (its kernel spills at four waves per SIMD as it is); hpt_set_schedule 0, 1 or 2");
   if (drLights && c->instrument) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the instrumented probe has no light-gradient variant");
+  // environment maps: served by the megakernel and the wavefront schedule, and not together with registered lights (one more kernel cross product)
+  const bool drEnv = dr && drEnvironmentCall(c);
+  if (drEnv && drLights)
+    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the light-gradient variant has no environment-map form (hpt_put_diff_lights and an environment scene under dr_environment on one context)");
+  if (drEnv && c->schedule == 3)
+    return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the block-local schedule has no environment-map variant; hpt_set_schedule 0, 1 or 2");
+  if (drEnv && c->instrument) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceDR: the instrumented probe has no environment-map variant");
+  if (drEnv)                                                   // (the env sweep scatters rgb: a one-channel registration of a map it reads has no meaning)
+    for (uint t = 0; t < (uint)c->hTextures.size(); t++)
+      if (c->hTextures[t].diffOffset != ~0ull && c->hTextures[t].diffChannels != 4u && drEnvReads(c, t))
+        return c->fail(HPT_ERR_ARG, "PathTraceDR: the environment map is registered with one channel (hpt_put_diff_tex2d: an environment map takes 4)");
+  const bool drEnvPlane = drEnv && drEnvMapRegistered(c);
   // never more lanes than pixels: with fewer, the hardware's round-robin block placement spreads them evenly over the CUs, whereas a
   // full grid would let whichever waves ask first take all the work (a small multi-GPU share of a frame)
   if (c->S.spectralMode != 0u) {                               // four wavelengths per path: its own (plain) kernel
@@ -2212,7 +2252,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
   // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
   const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
-  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS && !drLights;   // (no block-local kernel with light gradients)
+  const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS && !drLights && !drEnv;   // (no block-local kernel with light gradients or environment maps)
   const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
   const size_t fullGrid = (size_t)gridBlocks(c, dr, fullMaterials && !mode7) * 256;
   const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : passSliceAuto(job.tidCount, fullGrid, job.passNum);
@@ -2238,6 +2278,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   job.counters = nullptr;
   job.drSkipNonFinite = c->drSkipNonFinite ? 1u : 0u;
   if (drLights) { job.drLightFirst = c->diffLightFirst; job.drLightCount = c->diffLightCount; job.drLightOff = (uint)c->diffLightOff; job.drLightPad = 0u; }   // (share the input-ray pointers' storage)
+  if (drEnv) { job.drEnvPad = 0u; job.drEnvPlaneOn = drEnvPlane ? 1u : 0u; }
   c->lastSchedule = 1;
   c->lastShadeRecords = c->S.shadeTris != nullptr ? 1u : 0u;
   // schedule 4 (experimental, never chosen automatically): the block-owned streaming form of the wavefront schedule - heavy static scenes with gltf / emissive materials
@@ -2254,7 +2295,8 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   if (stats) { HIPCHK(c, c->dCounters.alloc(1)); HIPCHK(c, hipMemsetAsync(c->dCounters.p, 0, sizeof(Counters), st)); job.counters = c->dCounters.p; }
   if (dr) {
     job.recordLanes = (uint)blocks * 256u;
-    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(job.recordLanes, c->S.traceDepth) : 0)));
+    HIPCHK(c, c->dRecord.alloc((size_t)job.recordLanes * REC_FIELDS * (c->S.traceDepth + 1) + (drLights ? drLightPlaneFloats(job.recordLanes, c->S.traceDepth) : 0) +
+                                (drEnvPlane ? drEnvPlaneFloats(job.recordLanes, c->S.traceDepth) : 0)));
     job.record = c->dRecord.p;
   }
   c->lastPassSlice = slice;
@@ -2288,6 +2330,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
         Sd.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;
         launchPT<true, true, 0>(Sd, job, blocks, st, deep || (Sd.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
       } else if (drLights) launchPT<false, true, 0, false, true>(Sd, job, blocks, st, deep);
+      else if (drEnv) launchPT<false, true, 0, false, false, true>(Sd, job, blocks, st, deep);
       else launchPT<false, true, 0>(Sd, job, blocks, st, deep);
     }
     else if (film) {
@@ -3279,6 +3322,8 @@ try {
   }
   if (channels != 1 && channels != 4) return c->fail(HPT_ERR_ARG, "PutDiffTex2D: channels must be 1 or 4");
   if (channels == 4 && (c->gradSize % 4) != 0) return c->fail(HPT_ERR_ARG, "PutDiffTex2D: 4-channel textures must start at a multiple of 4 floats");
+  if (channels != 4 && c->drEnvironment && ((c->paramsSet && texId == c->S.envTexId) || (c->S.envLightId < c->hLightTex.size() && texId == c->hLightTex[c->S.envLightId])))
+    return c->fail(HPT_ERR_ARG, "PutDiffTex2D: the environment map takes 4 channels (dr_environment reads its rgb)");
   (void)hipSetDevice(c->device);
   TexRec& t = c->hTextures[texId];
   t.diffOffset = c->gradSize; t.diffW = w; t.diffH = h; t.diffChannels = channels;
@@ -3691,6 +3736,7 @@ try {
   else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
+  else if (k == "dr_environment") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_environment: 0 PathTraceDR / PathTraceVJP refuse scenes with an environment map or its sampling, 1 they render and differentiate them"); c->drEnvironment = value != 0; }
   else if (k == "kmlt_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "kmlt_spectral: 0 PathTraceBlockKMLT and the primary-sample-space pass refuse m_spectral_mode, 1 they run the spectral MLT kernels"); c->kmltSpectral = value != 0; }
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels

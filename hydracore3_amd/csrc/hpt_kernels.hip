@@ -23,10 +23,11 @@
 
 namespace hpt {
 
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED, bool LGRAD>
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED, bool LGRAD, bool ENV>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job)
 {
   static_assert(!LGRAD || (DR && !STATS), "light-colour gradients: the uninstrumented DR kernel");
+  static_assert(!ENV || (DR && !STATS && !LGRAD), "environment maps in DR: the uninstrumented DR kernel, without light-colour gradients");
   constexpr bool NAIVE = (MODE == 1 || MODE == 5), INRAYS = (MODE == 2 || MODE == 6), LEAN = (MODE == 3), FILM = (MODE >= 4 && MODE <= 6);   // (MODE 7 = MODE 0 built for one more wave per SIMD)
   __shared__ uint stackMem[LDS_STACK * 256];
   const uint glane = blockIdx.x * 256u + threadIdx.x;                    // slot in the per-lane HBM buffers
@@ -45,6 +46,8 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   const DrLights lightReg = { LGRAD ? job.drLightFirst : 0u, LGRAD ? job.drLightCount : 0u, LGRAD ? job.drLightOff : 0u };
   float4* lightPlane = LGRAD ? drLightPlane(job.record, job.recordLanes, S.traceDepth) : nullptr;
   if (LGRAD) drLightBinsClear(lightBins);
+  // environment maps (ENV): the env plane of the adjoint record, where the light plane would sit; null unless the map is registered (hpt_shade.h)
+  float4* envPlane = (ENV && job.drEnvPlaneOn != 0u) ? drEnvPlane(job.record, job.recordLanes, S.traceDepth) : nullptr;
 #define PIX(k)      coldPix[(k) * 256 + threadIdx.x]
 #define PIX_XY      coldU[0 * 256 + threadIdx.x]
 #define PIX_TID     coldU[1 * 256 + threadIdx.x]
@@ -227,10 +230,11 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     recTaps.fx = recTaps.fy = 0.0f; recTaps.base = recTaps.ch = 0u;
 
     DrLightVtx lv; lv.reg = lightReg; lv.sLight = lv.tLight = 0xFFFFFFFFu; lv.sUnit = lv.tUnit = v3(0, 0, 0);   // (LGRAD only)
+    DrEnvVtx ev; ev.s = drNoTap(); ev.sUnit = v3(0, 0, 0);                                                      // (ENV only)
     if (alive) {
       if (STATS && hit.inst != 0xFFFFFFFFu) nHits++;
-      didBounce = shadeVertex<DR, NAIVE, LEAN, MOTION, FILM, PseudoRands, LGRAD>(S, job.data, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
-                                                 wantShadow, shPos, shDir, shFar, contrib, recA, recS, recdA, recdS, recTaps, recTex, tailR, pathTime, PseudoRands(), &lv);
+      didBounce = shadeVertex<DR, NAIVE, LEAN, MOTION, FILM, PseudoRands, LGRAD, ENV>(S, job.data, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
+                                                 wantShadow, shPos, shDir, shFar, contrib, recA, recS, recdA, recdS, recTaps, recTex, tailR, pathTime, PseudoRands(), &lv, &ev);
     }
 
     STAMP(2);
@@ -239,7 +243,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       HitRec sh;
       const bool occluded = traceAny<true, STATS, DEEP, FLAT, MOTION, SWEEP>(S, shPos, shDir, 0.0f, shFar, sh, stk, st, pathTime);
       if (STATS) { nRays++; nShadow++; }
-      if (!occluded) accum = accum + contrib; else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); if (LGRAD) lv.sLight = 0xFFFFFFFFu; }
+      if (!occluded) accum = accum + contrib; else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); if (LGRAD) lv.sLight = 0xFFFFFFFFu; if (ENV) ev.s.e0 = 0xFFFFFFFFu; }
     } else if (DR) { recS = v3(0, 0, 0); recdS = v3(0, 0, 0); }
 
     STAMP(3);
@@ -248,6 +252,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
     V3 sweepSeed = v3(0, 0, 0), sweepTail = v3(0, 0, 0);
     DrRec lastRec = drEmptyRecord(); bool lastInRegs = false;
     const V3 lightTail = thr * lv.tUnit;                  // (LGRAD) T_n * tail_unit: an emitter hit leaves the throughput as it was
+    DrTapRef envTap = drNoTap(); V3 envTail = v3(0, 0, 0);  // (ENV) the tail's lookup and T_n * tail_unit
     if (alive) {
       if (didBounce) bounce++;
       const bool ended = (flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= maxBounce;
@@ -260,13 +265,17 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
         if (!ended) drStoreRecord(job.record, job.recordLanes, glane, bounce - 1u, lastRec);
 #endif
         if (LGRAD) drStoreLightTerm(lightPlane, job.recordLanes, glane, bounce - 1u, lv.sLight, thrBefore * lv.sUnit);   // (also the last bounce's: the sweep reads every level from the plane)
+        if (ENV && envPlane) drStoreEnvTerm(envPlane, job.recordLanes, glane, bounce - 1u, ev.s, thrBefore * ev.sUnit);   // (the shadow ray is back: an occluded sample has no term)
         if (STATS) { nRec++; if (recTex != 0xFFFFFFFFu) nRecTex++; if (!ended) nRecStored++; }
         STAMP(5);
       }
       if (ended) {
         // kernel_HitEnvironment (integrator_pt.cpp:550-595), constant environment colour.
         // The DR replay adds the environment term unconditionally (diff_render/integrator_dr.cpp:1077-1098).
-        const V3 env = DR ? ld3(S.envColor) : environmentRadiance(S, rdir, misPdf, flags, INRAYS ? (PIX_TID < job.packedCount ? job.packedXY[PIX_TID] : 0u) : PIX_XY);
+        V3 env;
+        if constexpr (ENV) {                                               // the replay's EnvironmentColor() over the map, along the path's final direction
+          V3 envUnit; env = drEnvironmentTail(S, job.data, rdir, misPdf, flags, envTap, envUnit); envTail = thr * envUnit;
+        } else env = DR ? ld3(S.envColor) : environmentRadiance(S, rdir, misPdf, flags, INRAYS ? (PIX_TID < job.packedCount ? job.packedXY[PIX_TID] : 0u) : PIX_XY);
         if (DR) accum = accum + thr * env;
         else if ((flags & RAY_FLAG_OUT_OF_SCENE) != 0) {
           if (S.integratorType == INTEGRATOR_STUPID_PT) accum = thr * env; else accum = accum + thr * env;
@@ -322,6 +331,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
                        drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, lastRec, lastInRegs, STATS ? &nAtomInst : nullptr);
 #endif
         if (LGRAD) drLightSweep(S, lightPlane, job.recordLanes, glane, closing, bounce, sweepSeed, lv.tLight, lightTail, lightBins, job.grad, lightReg, job.drSkipNonFinite != 0u);
+        if (ENV) drEnvSweep(S, envPlane, job.recordLanes, glane, closing, bounce, sweepSeed, envTap, envTail, job.grad, job.drSkipNonFinite != 0u, drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS);
       }
       STAMP(6);
     }
@@ -388,7 +398,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   template __global__ void pathTraceKernel<false, false, MODE, true,  true,  false, false, true>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<false, false, MODE, false, false, false, true,  true>(const DevScene, const Job);
 #ifndef HPT_INST_GROUP
-#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..20"
+#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..21"
 #endif
 #if HPT_INST_GROUP == 1      // gltf + emissive scenes (every benchmark workload)
 HPT_INST4(false, false, 3)
@@ -408,6 +418,12 @@ template __global__ void pathTraceKernel<false, true, 0, true,  false, false, fa
 template __global__ void pathTraceKernel<false, true, 0, false, true,  false, false, false, true>(const DevScene, const Job);
 template __global__ void pathTraceKernel<false, true, 0, true,  true,  false, false, false, true>(const DevScene, const Job);
 template __global__ void pathTraceKernel<false, true, 0, false, false, false, true,  false, true>(const DevScene, const Job);
+#elif HPT_INST_GROUP == 21   // PathTraceDR / PathTraceVJP over environment maps (hpt_set_option "dr_environment")
+template __global__ void pathTraceKernel<false, true, 0, false, false, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, true,  false, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, false, true,  false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, true,  true,  false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, true, 0, false, false, false, true,  false, false, true>(const DevScene, const Job);
 #elif HPT_INST_GROUP == 15   // PathTraceDR, instrumented (phase stamps, record / sweep / atomic counts: profiles/dr_phases.py)
 HPT_INST4(true, true, 0)
 #elif HPT_INST_GROUP == 9    // scenes with thin films (MODE 4 / 5 / 6 = 0 / 1 / 2 + MAT_TYPE_THIN_FILM)

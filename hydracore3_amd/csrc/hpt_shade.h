@@ -251,6 +251,21 @@ struct PseudoRands
 struct DrLights { uint first, count, off; };
 struct DrLightVtx { DrLights reg; uint sLight; V3 sUnit; uint tLight; V3 tUnit; };
 
+// Environment maps in DR (hpt_set_option "dr_environment"): the ENV instantiations serve the LIGHT_GEOM_ENV light sample and read
+// the map through texFetchAD, so a registered map comes from a_data. A lookup of a registered map hands back its four taps in DrRec's encoding
+// (e0 = 0xFFFFFFFF: none) and the expression with the texel colour replaced by 1 - the colour is affine in the texels, nothing is divided by one.
+struct DrTapRef { uint e0; int dx, dy; float fx, fy; };
+HPT_DEV DrTapRef drNoTap() { DrTapRef r; r.e0 = 0xFFFFFFFFu; r.dx = r.dy = 0; r.fx = r.fy = 0.0f; return r; }
+HPT_DEV DrTapRef drTapRef(const Taps& t)
+{
+  DrTapRef r; const int ch = (int)t.ch;
+  r.e0 = (t.base + (uint)t.off[0] * t.ch) | (t.ch == 4u ? 0u : 0x80000000u);
+  r.dx = (t.off[1] - t.off[0]) * ch; r.dy = (t.off[2] - t.off[0]) * ch;
+  r.fx = t.fx; r.fy = t.fy;
+  return r;
+}
+struct DrEnvVtx { DrTapRef s; V3 sUnit; };     // the light sample's lookup along the shadow ray and shade_unit
+
 // Shades the vertex a closest-hit query returned for one path.  All path registers are passed by reference and the
 // function is always inlined, so both callers keep them in VGPRs.  Returns true when the path continues (didBounce).
 // A miss only sets the OUT_OF_SCENE flags.  The caller traces the shadow ray (if wantShadow) and adds `contrib`.
@@ -259,14 +274,16 @@ struct DrLightVtx { DrLights reg; uint sLight; V3 sUnit; uint tLight; V3 tUnit; 
 // compiled out - fewer live registers and spills in the kernels every benchmark scene runs (the DR variant is lean by definition).
 // FILM: the scene holds thin films (MAT_TYPE_THIN_FILM, hpt_film.h): their branches exist in the FILM variants only.
 // LGRAD (with DR): light-colour gradients, `lv` is read and filled (DrLightVtx); the other instantiations never look at it.
-template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false, class RANDS = PseudoRands, bool LGRAD = false>
+// ENV (with DR): the environment light's map goes through texFetchAD and `ev` is filled (DrEnvVtx); the other instantiations never look at it.
+template <bool DR, bool NAIVE, bool LEAN = false, bool MOTION = false, bool FILM = false, class RANDS = PseudoRands, bool LGRAD = false, bool ENV = false>
 HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec& hit,
                          V3& rpos, V3& rdir, V3& accum, V3& thr, float& misPdf, float& misIor, uint& flags, const uint bounce, Rng& gen,
                          bool& wantShadow, V3& shPos, V3& shDir, float& shFar, V3& contrib,
                          V3& recA, V3& recS, V3& recdA, V3& recdS, Taps& recTaps, uint& recTex, V3& tailR, const float time = 0.0f, const RANDS rands_ = RANDS(),
-                         DrLightVtx* lv = nullptr)
+                         DrLightVtx* lv = nullptr, DrEnvVtx* ev = nullptr)
 {
   static_assert(!LGRAD || DR, "light-colour gradients: the differentiable kernels only");
+  static_assert(!ENV || (DR && !LGRAD), "environment maps in DR: the differentiable kernels only, and not with light-colour gradients");
   // the lean forward kernels (Lambert-heavy benchmark scenes: waves of one lobe) evaluate only what a vertex uses; see gltfSampleAndEvalC
   constexpr bool LEAN_FWD = LEAN && !DR;
   bool didBounce = false;
@@ -385,6 +402,13 @@ HPT_DEV bool shadeVertex(const DevScene& S, const float* diffData, const HitRec&
             lightColor = lightIntensityFrom(S, L, ld3(L.intensity) * v3(gain[0], gain[1], gain[2]), shadowRayPos, shadowRayDir);
             const V3 unitColor = lightIntensity(S, L, shadowRayPos, shadowRayDir);
             lv->sLight = (uint)lightId; lv->sUnit = ((unitColor * bv.val) / lgtPdfW) * cosThetaOut * misWeight;   // d shade / d gain, whatever the gain is
+          } else if (ENV && L.iesId == 0xFFFFFFFFu && L.distType != LIGHT_DIST_SPOT && L.texId != 0xFFFFFFFFu) {
+            // lightIntensityFrom's map lookup along the shadow ray (hpt_device.h), the texel through texFetchAD: the same products in the same order
+            const V3 unitColor = ld3(L.intensity) * L.mult;
+            Taps et; bool envParam = false;
+            const V4 ec = texFetchAD(S, diffData, L.texId, mulRows2x4(L.samplerRow0, L.samplerRow1, sphereMapTo2DTexCoord(shadowRayDir)), et, envParam);
+            lightColor = unitColor * v3(ec.x, ec.y, ec.z);
+            if (envParam) { ev->s = drTapRef(et); ev->sUnit = ((unitColor * bv.val) / lgtPdfW) * cosThetaOut * misWeight; }   // d shade / d texel colour, whatever the texel is
           } else lightColor = lightIntensity(S, L, shadowRayPos, shadowRayDir);
           shade = ((lightColor * bv.val) / lgtPdfW) * cosThetaOut * misWeight;
           if (DR) dshade = ((lightColor * bv.dval) / lgtPdfW) * cosThetaOut * misWeight;
@@ -542,13 +566,14 @@ HPT_DEV void drStoreRecord(float* record, size_t s, size_t idx, uint bounce, con
   if (r.e0 != 0xFFFFFFFFu) *(float*)(q + 4 * s) = r.fy;
 }
 // the light sample of bounce b turned out occluded: its S term and derivative vanish
-HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce, float4* lightPlane = nullptr)
+HPT_DEV void drClearShadowTerm(float* record, size_t s, size_t idx, uint bounce, float4* lightPlane = nullptr, float4* envPlane = nullptr)
 {
   float* q = (float*)((float4*)record + ((size_t)bounce * REC_PLANES) * s + idx);
   q[3] = 0.0f;                                                              // S.x
   q[4 * s + 0] = 0.0f; q[4 * s + 1] = 0.0f;                                 // S.yz
   q[8 * s + 1] = 0.0f; q[8 * s + 2] = 0.0f; q[8 * s + 3] = 0.0f;            // T*dS
   if (lightPlane) *(uint*)(lightPlane + (size_t)bounce * s + idx) = 0xFFFFFFFFu;   // ... and so does the light term (light-colour gradients)
+  if (envPlane) *(uint*)(envPlane + (size_t)(2u * bounce) * s + idx) = 0xFFFFFFFFu;   // ... or the env term (environment maps)
 }
 
 // ---- light-colour gradients: the light plane of the adjoint record and the binned reduction ----------------------------------
@@ -650,6 +675,34 @@ HPT_DEV void drLightFlush(const float* bins, float* grad, const DrLights reg)
 // instructions per wave-trip; 360 -> see profiles/r3_measurements.md.) `last`: the record of the closing lane's last bounce when it is
 // still in registers (lastInRegs; it was never stored). `stage`: the wave's 1024-dword LDS area. Same sums, another order.
 static const uint DR_STAGE_DWORDS = 16u * 64u;
+// The staged, cooperative scatter of drReverseSweep and drEnvSweep (see drReverseSweep): `cnt` columns of the wave's staging area - rows 0..11 the
+// values of (tap, channel), rows 12..14 tap 0's element index and the two steps - go out with the atomics of all 64 lanes; cnt is 0 afterwards.
+// One copy of the text, expanded as the body of a lambda in either sweep: as a function of its own it moved the spills of every DR megakernel
+// that inlines drReverseSweep (profiles/env_grad.md), as the lambda it always was it leaves their code as it is. It reads the enclosing
+// function's stage, ss, grad, lane, cnt and STAT (a pointer to the instrumented build's counter, or nullptr).
+#define HPT_DR_STAGE_FLUSH(STAT) \
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); \
+    __builtin_amdgcn_wave_barrier(); \
+    if ((STAT) && lane == 0u) *(STAT) += (12u * cnt + 63u) / 64u;       /* (instrumented build: atomic wave-instructions of this sweep) */ \
+    for (uint p = lane; p < 12u * cnt; p += 64u) { \
+      const uint src = (p * 0xAAABu) >> 19;                               /* p / 12 (p < 768) */ \
+      const uint e = p - 12u * src, tap = (e * 11u) >> 5, ch = e - 3u * tap;   /* e / 3, e % 3 (e < 12) */ \
+      const uint ix0 = stage[12 * ss + src]; \
+      const uint ix = (ix0 & 0x7FFFFFFFu) + ((tap & 1u) ? stage[13 * ss + src] : 0u) + ((tap & 2u) ? stage[14 * ss + src] : 0u);   /* (two's complement: negative steps wrap back) */ \
+      const float val = ((const float*)stage)[e * ss + src]; \
+      HPT_DR_STAGE_ATOMICS \
+    } \
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); \
+    __builtin_amdgcn_wave_barrier(); \
+    cnt = 0;
+#ifndef HPT_DR_NO_ATOMICS    // diagnostic build only: how much of PathTraceDR is the gradient scatter?
+#define HPT_DR_STAGE_ATOMICS \
+      if ((ix0 & 0x80000000u) == 0u) atomicAdd(grad + (size_t)ix + ch, val); \
+      else if (ch == 0u) atomicAdd(grad + (size_t)ix, val);
+#else
+#define HPT_DR_STAGE_ATOMICS \
+      if (ix == 0x7FFFFFFFu) grad[0] = val;
+#endif
 HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, size_t idx, const bool closing, const uint bounceIn, V3 Rn, const V3 seed,
                             float* grad, const bool skipNonFinite, uint* stage, const DrRec& last, const bool lastInRegs,
                             unsigned long long* statAtomics = nullptr, const uint ss = 64u, const bool defer = true)      // ss: dwords between the staging area's rows (64: an area of its own; 256: the wave's columns of a [16][256] array)
@@ -663,25 +716,7 @@ HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, si
   // with its many short sweeps in flight the bunched atomics stall the issue instead (256 -> 249, 1 M triangles 229 -> 224 when deferred).
   uint cnt = 0;                                                             // columns staged so far (wave-uniform)
   auto flush = [&]() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    if (statAtomics && lane == 0u) *statAtomics += (12u * cnt + 63u) / 64u;       // (instrumented build: atomic wave-instructions of this sweep)
-    for (uint p = lane; p < 12u * cnt; p += 64u) {
-      const uint src = (p * 0xAAABu) >> 19;                               // p / 12 (p < 768)
-      const uint e = p - 12u * src, tap = (e * 11u) >> 5, ch = e - 3u * tap;   // e / 3, e % 3 (e < 12)
-      const uint ix0 = stage[12 * ss + src];
-      const uint ix = (ix0 & 0x7FFFFFFFu) + ((tap & 1u) ? stage[13 * ss + src] : 0u) + ((tap & 2u) ? stage[14 * ss + src] : 0u);   // (two's complement: negative steps wrap back)
-      const float val = ((const float*)stage)[e * ss + src];
-#ifndef HPT_DR_NO_ATOMICS    // diagnostic build only: how much of PathTraceDR is the gradient scatter?
-      if ((ix0 & 0x80000000u) == 0u) atomicAdd(grad + (size_t)ix + ch, val);
-      else if (ch == 0u) atomicAdd(grad + (size_t)ix, val);
-#else
-      if (ix == 0x7FFFFFFFu) grad[0] = val;
-#endif
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    cnt = 0;
+    HPT_DR_STAGE_FLUSH(statAtomics)
   };
   for (int b = (int)S.traceDepth - 1; b >= 0; b--) {                      // wave-uniform trip count; a lane joins at its own last bounce
     const bool mine = (uint)b < bounce;
@@ -722,6 +757,126 @@ HPT_DEV void drReverseSweep(const DevScene& S, const float* record, size_t s, si
       if (!defer) flush();
     }
     if (mine) Rn = Sb + A * Rn;
+  }
+  if (cnt != 0u) flush();
+}
+
+// ---- environment maps in DR: the tail, the env plane of the adjoint record and its sweep ---------------------------------------
+// The replay's EnvironmentColor() at the path's end (integrator_dr.cpp:1077-1098): environmentRadiance() (hpt_device.h) without the back plate,
+// the texel through texFetchAD. `unit`: the same expression with the texel colour replaced by 1; `tap`: the lookup's taps when the map is registered.
+HPT_DEV V3 drEnvironmentTail(const DevScene& S, const float* data, V3 rdir, float misPdf, uint flags, DrTapRef& tap, V3& unit)
+{
+  V3 color = ld3(S.envColor);
+  tap = drNoTap(); unit = v3(0, 0, 0);
+  if (S.envTexId == 0xFFFFFFFFu) return color;
+  float envPdf = 1.0f;
+  const float sinTheta = sqrtf_(1.0f - rdir.y * rdir.y);
+  const V2 tcT = mulRows2x4(S.envSamRow0, S.envSamRow1, sphereMapTo2DTexCoord(rdir));
+  if (sinTheta != 0.f && S.envEnableSam != 0 && S.integratorType == INTEGRATOR_MIS_PT && S.envLightId != 0xFFFFFFFFu) {
+    const LightRec& L = S.lights[S.envLightId];
+    const float mapPdf = evalMap2DPdf(tcT, S.arrays1f + L.pdfTableOffset, (int)L.pdfTableSizeX, (int)L.pdfTableSizeY);
+    envPdf = (mapPdf * 1.0f) / (2.f * HPT_PI * HPT_PI * smax(absf(sinTheta), 1e-20f));
+  }
+  Taps t; bool isParam = false;
+  const V4 tx = texFetchAD(S, data, S.envTexId, tcT, t, isParam);
+  unit = color;
+  color = color * v3(tx.x, tx.y, tx.z);
+  const bool isSpec = misPdf < 0.0f, exitZero = (flags & RAY_FLAG_PRIME_RAY_MISS) != 0;
+  if (S.integratorType == INTEGRATOR_MIS_PT && S.envEnableSam != 0 && !isSpec && !exitZero) {
+    const float w = misWeightHeuristic(misPdf, (1.0f / float(S.numLights)) * envPdf);
+    color = color * w; unit = unit * w;
+  }
+  else if (S.integratorType == INTEGRATOR_SHADOW_PT && S.envEnableSam != 0) { color = v3(0, 0, 0); isParam = false; }
+  if (isParam) tap = drTapRef(t);
+  return color;
+}
+// The env plane sits where the light plane does (the two are mutually exclusive): two float4 per slot and bounce, (e0, dx, dy, fx) and
+// (fy, T_b * shade_unit.xyz), laid out [bounce][2][slot]; e0 = 0xFFFFFFFF: no term (the second float4 is then not written). It exists only when
+// the map is registered. The tail's taps and T_n * tail_unit never leave the registers: the path ends there.
+HPT_DEV float4* drEnvPlane(float* record, size_t s, uint traceDepth) { return drLightPlane(record, s, traceDepth); }
+HPT_HD size_t drEnvPlaneFloats(size_t s, uint traceDepth) { return 8u * s * traceDepth; }
+HPT_DEV void drStoreEnvTerm(float4* plane, size_t s, size_t idx, uint bounce, const DrTapRef& t, V3 term)
+{
+  float4* q = plane + (size_t)(2u * bounce) * s + idx;
+  q[0] = make_float4(__uint_as_float(t.e0), __int_as_float(t.dx), __int_as_float(t.dy), t.fx);
+  if (t.e0 != 0xFFFFFFFFu) q[s] = make_float4(t.fy, term.x, term.y, term.z);
+}
+// Maps of up to this many texels get the equal-address merge of drEnvSweep: 64 lanes over 64 x 64 texels still meet now and then, past that a
+// trip per distinct key is all cost (measured at 16 x 8 and 1024 x 512 only: profiles/env_grad.md).
+static const uint DR_ENV_MERGE_TEXELS = 4096u;
+// The env terms of the paths that closed in this trip: called by ALL lanes of the wave in wave-uniform control flow, next to drReverseSweep, whose
+// staging area and flush it shares (the area is empty between the two). dC/d texel[tap k, c] = w_k * term_c; level b < traceDepth: the light sample
+// of bounce b, from the plane (null: the map is not registered where a light sample reads it); level traceDepth: the tail, from registers.
+HPT_DEV void drEnvSweep(const DevScene& S, const float4* plane, size_t s, size_t idx, const bool closing, const uint bounceIn, const V3 seed,
+                        const DrTapRef tailTap, const V3 tailTerm, float* grad, const bool skipNonFinite, uint* stage, const uint ss = 64u, const bool defer = true)
+{
+  const uint bounce = closing ? bounceIn : 0u;
+  const uint lane = lane_id();
+  // merge equal taps within the wave when the registered map is small enough for lanes to meet on a texel (wave-uniform; DR_ENV_MERGE_TEXELS)
+  bool merge = false;
+  if (S.envTexId != 0xFFFFFFFFu) { const TexRec& et = S.textures[S.envTexId]; merge = et.diffOffset != ~0ull && et.diffW * et.diffH <= DR_ENV_MERGE_TEXELS; }
+  uint cnt = 0;
+  auto flush = [&]() {
+    HPT_DR_STAGE_FLUSH((unsigned long long*)nullptr)
+  };
+  for (uint b = 0; b <= S.traceDepth; b++) {                                // wave-uniform trip count
+    DrTapRef tp = drNoTap(); V3 t = v3(0, 0, 0);
+    if (b < S.traceDepth) {
+      if (plane != nullptr && b < bounce) {
+        const float4* q = plane + (size_t)(2u * b) * s + idx;
+        const float4 q0 = q[0];
+        tp.e0 = __float_as_uint(q0.x);
+        if (tp.e0 != 0xFFFFFFFFu) {
+          const float4 q1 = q[s];
+          tp.dx = __float_as_int(q0.y); tp.dy = __float_as_int(q0.z); tp.fx = q0.w; tp.fy = q1.x; t = v3(q1.y, q1.z, q1.w);
+        }
+      }
+    } else if (closing) { tp = tailTap; t = tailTerm; }
+    const bool has = tp.e0 != 0xFFFFFFFFu;
+    const unsigned long long hm0 = __ballot(has);
+    if (hm0 == 0ull) continue;
+    float v[12];                                                            // seed * term * w_k, four taps x rgb
+    {
+      V3 g = v3(seed.x * t.x, seed.y * t.y, seed.z * t.z);
+      if (skipNonFinite && !__builtin_isfinite(g.x + g.y + g.z)) g = v3(0, 0, 0);   // (dr_skip_nonfinite: as the texture terms)
+      const float fx1 = 1.0f - tp.fx, fy1 = 1.0f - tp.fy;
+      const float w[4] = { fx1 * fy1, tp.fx * fy1, fx1 * tp.fy, tp.fx * tp.fy };  // bilinearTaps' weights, the same products
+#pragma unroll
+      for (int k = 0; k < 4; k++) { v[3 * k + 0] = has ? g.x * w[k] : 0.0f; v[3 * k + 1] = has ? g.y * w[k] : 0.0f; v[3 * k + 2] = has ? g.z * w[k] : 0.0f; }
+    }
+    // A small map: many lanes of the wave hold the same four texels, and their atomics would queue on the same few lines - PathTraceVJP under
+    // a 16 x 8 map spent 92 % of its time there (profiles/env_grad.md). So lanes with equal taps (tap 0's element and both steps) are merged
+    // first, as drLightAdd merges equal lights: one trip per distinct key, a butterfly sum of the 12 values, the key's first lane stages them.
+    bool stageMe = has;
+    if (merge) {
+      stageMe = false;
+      unsigned long long todo = hm0;
+      while (todo != 0ull) {
+        const int leader = (int)(__ffsll((long long)todo) - 1);
+        const uint k0 = (uint)__shfl((int)tp.e0, leader); const int kx = __shfl(tp.dx, leader), ky = __shfl(tp.dy, leader);
+        const bool match = has && tp.e0 == k0 && tp.dx == kx && tp.dy == ky;
+#pragma unroll
+        for (int i = 0; i < 12; i++) {
+          float x = match ? v[i] : 0.0f;
+          for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+          if ((int)lane == leader) v[i] = x;
+        }
+        if ((int)lane == leader) stageMe = true;
+        todo &= ~__ballot(match);
+      }
+    }
+    const unsigned long long hm = __ballot(stageMe);
+    const uint n = (uint)__popcll(hm);
+    if (cnt + n > 64u) flush();
+    const uint col = cnt + mbcnt64(hm);
+    if (stageMe) {
+      float* sv = (float*)stage;
+#pragma unroll
+      for (int i = 0; i < 12; i++) sv[i * ss + col] = v[i];
+      stage[12 * ss + col] = tp.e0; stage[13 * ss + col] = (uint)tp.dx; stage[14 * ss + col] = (uint)tp.dy;
+    }
+    cnt += n;
+    if (!defer) flush();
   }
   if (cnt != 0u) flush();
 }

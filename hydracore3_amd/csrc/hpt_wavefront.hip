@@ -26,7 +26,7 @@
 
 namespace hpt {
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3)      // (small kernels: emitted once, with the shade kernels)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4)      // (small kernels: emitted once, with the shade kernels)
 __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 {
   const uint i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -34,10 +34,11 @@ __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 }
 #endif
 
-template <bool DR, bool LEAN, bool MOTION, bool FILM, bool LGRAD>
+template <bool DR, bool LEAN, bool MOTION, bool FILM, bool LGRAD, bool ENV>
 __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const WfPool P, const WfJob job)
 {
   static_assert(!LGRAD || DR, "light-colour gradients: the DR shade kernel");
+  static_assert(!ENV || (DR && !LGRAD), "environment maps in DR: the DR shade kernel, without light-colour gradients");
   __shared__ uint drStage[DR ? 4 * DR_STAGE_DWORDS : 1];                   // the waves' staging areas of the cooperative gradient scatter (drReverseSweep)
   // light-colour gradients (LGRAD): the workgroup's bins, flushed at the end of this pass, and the light plane of the adjoint record (hpt_shade.h)
   float* lightBins = drLightBins<LGRAD>();
@@ -45,6 +46,9 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   float4* lightPlane = LGRAD ? drLightPlane(job.record, job.itemCount, S.traceDepth) : nullptr;
   uint tailLight = 0xFFFFFFFFu; V3 tailTerm = v3(0, 0, 0);
   if (LGRAD) drLightBinsClear(lightBins);
+  // environment maps (ENV): the env plane of the adjoint record, null unless the map is registered; the tail's lookup and T_n * tail_unit (hpt_shade.h)
+  float4* envPlane = (ENV && job.drEnvPlaneOn != 0u) ? drEnvPlane(job.record, job.itemCount, S.traceDepth) : nullptr;
+  DrTapRef envTap = drNoTap(); V3 envTail = v3(0, 0, 0);
   const uint s = blockIdx.x * 256u + threadIdx.x;
   uint* ctr = P.ctr + WF_CTR_WORDS * (job.iter & 1u);
   if (s <= WF_RANGES) P.ctr[WF_CTR_WORDS * ((job.iter + 1u) & 1u) + 32u * s] = 0u;   // counters of the NEXT round (its trace pass is long done)
@@ -74,11 +78,17 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
     float pathTime = 0.0f;
     if (MOTION && alive) pathTime = ldP(&P.time[s]);
     if (alive || ending) { const float4 a = ldP(&P.acc[s]); accum = v3(a.x, a.y, a.z); bounce = __float_as_uint(a.w); }
-    if (DR && ending) { const float4 t4 = ldP(&P.thr[s]); thr = v3(t4.x, t4.y, t4.z); }     // the environment term of the finished path needs its throughput
+    if (DR && ending) {                                                      // the environment term of the finished path needs its throughput
+      const float4 t4 = ldP(&P.thr[s]); thr = v3(t4.x, t4.y, t4.z);
+      if (ENV) {                                                             // ... and over a map its final direction, pdf and flags
+        const float4 ro = ldP(&P.rayO[s]), rd = ldP(&P.rayD[s]);
+        misPdf = ro.w; rdir = v3(rd.x, rd.y, rd.z); flags = __float_as_uint(t4.w);
+      }
+    }
     // (6') the shadow ray traced since the last visit: add the candidate contribution in the megakernel's order
     if (pend) {
       if (ldP(&P.occl[s]) == 0u) { const float4 c = ldP(&P.contrib[s]); accum = accum + v3(c.x, c.y, c.z); }
-      else if (DR && bounce > 0u) drClearShadowTerm(job.record, job.itemCount, s, bounce - 1u, lightPlane);   // the light sample of the last vertex was occluded
+      else if (DR && bounce > 0u) drClearShadowTerm(job.record, job.itemCount, s, bounce - 1u, lightPlane, envPlane);   // the light sample of the last vertex was occluded
       pend = false;
     }
     bool finalize = ending;                                                // path ended last time, only its shadow ray was outstanding
@@ -97,8 +107,9 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
       taps.fx = taps.fy = 0.0f; taps.base = taps.ch = 0u;
       const V3 thrBefore = thr;
       DrLightVtx lv; lv.reg = lightReg; lv.sLight = lv.tLight = 0xFFFFFFFFu; lv.sUnit = lv.tUnit = v3(0, 0, 0);   // (LGRAD only)
-      const bool didBounce = shadeVertex<DR, false, LEAN, MOTION, FILM, PseudoRands, LGRAD>(S, DR ? job.data : nullptr, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
-                                                    wantShadow, shPos, shDir, shFar, contrib, rA, rS, rdA, rdS, taps, recTex, tailR, pathTime, PseudoRands(), &lv);
+      DrEnvVtx ev; ev.s = drNoTap(); ev.sUnit = v3(0, 0, 0);                                                      // (ENV only)
+      const bool didBounce = shadeVertex<DR, false, LEAN, MOTION, FILM, PseudoRands, LGRAD, ENV>(S, DR ? job.data : nullptr, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
+                                                    wantShadow, shPos, shDir, shFar, contrib, rA, rS, rdA, rdS, taps, recTex, tailR, pathTime, PseudoRands(), &lv, &ev);
       if (LGRAD) { tailLight = lv.tLight; tailTerm = thr * lv.tUnit; }       // T_n * tail_unit: an emitter hit leaves the throughput as it was
       if (didBounce) bounce++;
       const bool ended = (flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= S.traceDepth;
@@ -109,6 +120,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
         lastInRegs = ended && !wantShadow;
         if (!lastInRegs) drStoreRecord(job.record, job.itemCount, s, bounce - 1u, lastRec);
         if (LGRAD) drStoreLightTerm(lightPlane, job.itemCount, s, bounce - 1u, wantShadow ? lv.sLight : 0xFFFFFFFFu, thrBefore * lv.sUnit);   // (cleared if its shadow ray comes back occluded)
+        if (ENV && envPlane) drStoreEnvTerm(envPlane, job.itemCount, s, bounce - 1u, ev.s, thrBefore * ev.sUnit);   // (set only with a shadow ray; cleared likewise)
       }
       if (ended) {
         if (!DR && (flags & RAY_FLAG_OUT_OF_SCENE) != 0) {                  // kernel_HitEnvironment (integrator_pt.cpp:550-595)
@@ -122,7 +134,10 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
     if (finalize && DR) {
       // PixelLossPT (integrator_dr.cpp:1103-1132): the replay adds the environment term unconditionally (:1077-1098), after the last
       // shadow contribution as in the megakernel; per-sample loss against the y-flipped reference; out_color += colorRend; reverse sweep
-      const V3 env = ld3(S.envColor);
+      V3 env = ld3(S.envColor);
+      if constexpr (ENV) {                                                   // the replay's EnvironmentColor() over the map, along the path's final direction
+        V3 envUnit; env = drEnvironmentTail(S, job.data, rdir, misPdf, flags, envTap, envUnit); envTail = thr * envUnit;
+      }
       accum = accum + thr * env;
       const uint x = XY & 0x0000FFFFu, y = (XY & 0xFFFF0000u) >> 16;
       bool sane, seeded = true; V3 seed = v3(0, 0, 0);                      // seed: dL/d(colour of this sample), see the megakernel
@@ -157,7 +172,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
       alive = true;
     }
     stP(&job.gens[tid], gen);
-    if (alive) {
+    if (alive || (ENV && ending)) {                                          // (ENV: the tail of a path that waits for its last shadow ray reads the direction and the pdf)
       stP(&P.rayO[s], make_float4(rpos.x, rpos.y, rpos.z, misPdf));
       stP(&P.rayD[s], make_float4(rdir.x, rdir.y, rdir.z, misIor));
     }
@@ -177,6 +192,9 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
 #endif
   if (LGRAD && __any(closing))
     drLightSweep(S, lightPlane, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepSeed, tailLight, tailTerm, lightBins, job.grad, lightReg, job.drSkipNonFinite != 0u);
+  if (ENV && __any(closing))
+    drEnvSweep(S, envPlane, job.itemCount, s < job.itemCount ? s : 0u, closing, sweepBounce, sweepSeed, envTap, envTail, job.grad, job.drSkipNonFinite != 0u,
+               drStage + (threadIdx.x >> 6) * DR_STAGE_DWORDS, 64u, false);
   // ray compaction: ballot + prefix sum, one atomic per wave and queue
   const bool qNear = active && alive, qShad = active && wantShadow;
   uint kn, ks;
@@ -187,7 +205,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   if (LGRAD) drLightFlush(lightBins, job.grad, lightReg);
 }
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4)
 // DR: sum of the per-slot losses in double, one atomic per block; wfLossFinishKernel adds the total to the caller's float
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc)
 {
@@ -458,7 +476,7 @@ __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScen
 
 // ---- explicit instantiations (the host launches them through the declarations in hpt_decl.h) -----------------------------------------------
 #ifndef HPT_WF_INST
-#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients
+#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients; 4: the shade kernel over environment maps
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 1
 template __global__ void wfShadeKernel<true, true>(const DevScene, const WfPool, const WfJob);
@@ -470,6 +488,9 @@ template __global__ void wfShadeKernel<false, false, true, true>(const DevScene,
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 3
 template __global__ void wfShadeKernel<true, true, false, false, true>(const DevScene, const WfPool, const WfJob);   // light-colour gradients (hpt_put_diff_lights)
+#endif
+#if HPT_WF_INST == 0 || HPT_WF_INST == 4
+template __global__ void wfShadeKernel<true, true, false, false, false, true>(const DevScene, const WfPool, const WfJob);   // environment maps in DR (hpt_set_option "dr_environment")
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 2
 #define HPT_WFT(DEEP, FLAT, STATS) template __global__ void wfTraceKernel<DEEP, FLAT, STATS>(const DevScene, const WfPool, uint, uint, uint, uint*, uint, Counters*);

@@ -63,7 +63,8 @@ def render(integrator, params, spp):
     `params`. params: a contiguous float32 tensor on the integrator's device with at least the registered number of elements; anything else
     raises ValueError before any device work. Each call draws new samples (m_randomGens goes on); backward replays forward's.
     Light colours need no argument of their own: the RGB gains of the lights registered by PutDiffLights are elements of `params` (at the
-    offset PutDiffLights returned, four floats per light, the fourth unused), and `params.grad` receives their gradient there."""
+    offset PutDiffLights returned, four floats per light, the fourth unused), and `params.grad` receives their gradient there.
+    Nor does an environment map: with set_option("dr_environment", 1) a map registered by PutDiffTex2D is a slice of `params` like any texture."""
     _check(integrator, params)
     spp = int(spp)
     if spp < 1:

@@ -462,6 +462,10 @@ int  hpt_cam_get_execution_time(hpt_cam* cam, const char* funcName, float out[4]
 /* ---- differentiable rendering (diff_render/integrator_dr.h:42-47, 103) ------------------------------------------ */
 int  hpt_put_diff_tex2d(hpt_ctx* ctx, uint32_t texId, uint32_t width, uint32_t height, uint32_t channels,
                         uint64_t* outOffset, uint64_t* outSize);                         /* PutDiffTex2D (integrator_dr.cpp:33-53) */
+/* The environment map is registered like any texture: with hpt_set_option(ctx, "dr_environment", 1), hpt_put_diff_tex2d(ctx, m_envTexId, w, h, 4)
+ * makes PathTraceDR / PathTraceVJP read the map from a_data - at the path's end and along the shadow ray of an env light sample whose texId
+ * is the registered texture - and add d loss / d texel to a_dataGrad, taken per unit texel (exact at a black map; channel 3 is never read, its
+ * gradient stays 0). w, h are the sizes the fetch uses. A one-channel registration of the environment map is HPT_ERR_ARG. */
 int  hpt_reset_diff_tex(hpt_ctx* ctx);                                                   /* LoadSceneEnd (integrator_dr.cpp:24-31); also clears hpt_put_diff_lights */
 /* Light-colour gradients (no counterpart in the reference). Registers lights [firstLight, firstLight + count) of the uploaded m_lights as
  * differentiable and appends 4 * count floats to the parameter vector, as hpt_put_diff_tex2d appends a texture: light firstLight + i owns
@@ -605,6 +609,14 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  * A member of the reference that is set in its constructor:
  *   "dr_grad_mode"  IntegratorDR's a_gradMode (integrator_dr.h; default 1). 0: RayTraceDR renders and returns the loss through the ordinary
  *               sampler and writes no gradient (integrator_dr.cpp:99, 432-438). PathTraceDR does not read it.
+ *   "dr_environment"  0 (default): PathTraceDR / PathTraceVJP refuse a scene with an environment map, its sampling or a camera back plate
+ *               (HPT_ERR_UNSUPPORTED). 1: scenes with m_envTexId and / or m_envEnableSam are served, as the reference's replay renders them
+ *               (diff_render/integrator_dr.cpp:744-787, 1077-1098): every path end adds m_envColor * map along its final direction - times the
+ *               env-sampling MIS weight under MIS with m_envEnableSam after a non-specular vertex (not on a primary miss), 0 under the shadow
+ *               integrator with m_envEnableSam - and the LIGHT_GEOM_ENV light is sampled at every bounce. A registered map's texel gradient
+ *               comes back in a_dataGrad (hpt_put_diff_tex2d). Still HPT_ERR_UNSUPPORTED: a camera back plate (the replay has none),
+ *               hpt_put_diff_lights on the same context, an explicit block-local schedule (the automatic choice avoids it), the instrumented
+ *               probe, spectral, lens and motion scenes. Scenes without a map run the kernels they always ran. Any other value: HPT_ERR_ARG.
  * Diagnostic switches (these DO change which kernels run or what they compute; never set in production):
  *   "dr_skip_nonfinite"     PathTraceDR: 1 = a sample whose radiance is not finite contributes neither colour, loss nor gradient (what an
  *                           optimisation loop wants: one NaN poisons Adam's moments for good); 0 (default) = PixelLossPT as the reference
