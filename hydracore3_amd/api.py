@@ -130,7 +130,32 @@ ABI = {
     "hpt_cam_read_state": (_i, [_vp, _vp, _vp, _vp, _u32]),
     "hpt_cam_render_dev": (_i, [_vp, _vp, _vp, _u32, _vp]),
     "hpt_cam_get_execution_time": (_i, [_vp, C.c_char_p, C.POINTER(_f)]),
+    "hpt_path_trace_block_counts": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _vp, _vp]),
+    "hpt_path_trace_block_counts_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _u32, _i, _vp, _vp, _vp]),
+    "hpt_adaptive_plan": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hpt_adaptive_plan_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "hpt_adaptive_resolve": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
+    "hpt_adaptive_resolve_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hpt_path_trace_block_adaptive": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
+    "hpt_path_trace_block_adaptive_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
 }
+
+# adaptive sampling: hpt_pixel_moments, one 16-byte record per tid; hpt_adaptive_info, the planner's and the loop's 32-byte report
+MOMENTS_DTYPE = np.dtype([("sumY", np.float32), ("sumY2", np.float32), ("passes", np.uint32), ("reserved", np.uint32)])
+ADAPTIVE_INFO_DTYPE = np.dtype([("passes", np.uint64), ("pixels", np.uint32), ("maxPasses", np.uint32), ("nonfinite", np.uint32), ("rounds", np.uint32),
+                                ("deviceMs", np.float32), ("reserved", np.uint32)])
+assert MOMENTS_DTYPE.itemsize == 16 and ADAPTIVE_INFO_DTYPE.itemsize == 32
+
+
+# passes a pixel may be given per round when the caller names no `step`: the sweep of profiles/adaptive.md (c) has its shortest wall time there (16 / 64 /
+# 256 / 1024 / 4096 -> 633 / 487 / 462 / 506 / 832 ms). It rests on ONE scene (the Cornell box at 1024 x 1024, one tolerance). The C ABI has no default:
+# hpt_adaptive_params.step below 1 is HPT_ERR_ARG.
+ADAPTIVE_STEP_DEFAULT = 256
+
+
+class ADAPTIVE_PARAMS(C.Structure):
+    """hpt_adaptive_params (include/hydra_hip.h): 6 dwords. tol and the pass limits are the caller's; step defaults to ADAPTIVE_STEP_DEFAULT."""
+    _fields_ = [("tol", _f), ("lumFloor", _f), ("minPasses", _u32), ("maxPasses", _u32), ("step", _u32), ("dilate", _u32)]
 
 # hpt_gbuffer_pixel = Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords
 GBUFFER_SAMPLES = 16
@@ -339,6 +364,72 @@ class HipIntegrator:
     def path_trace_block_dev(self, dev_ptr, pass_num, tid_begin=0, tid_count=None, channels=4, naive=False, stream=None):
         tid_count = self.N - tid_begin if tid_count is None else tid_count
         self._chk(self.L.hpt_path_trace_block_dev(self.h, tid_begin, tid_count, channels, dev_ptr, pass_num, int(naive), stream))
+
+    # ---- adaptive sampling (no counterpart in the reference) ---------------------------------------------
+    @staticmethod
+    def _adaptive_params(params=None, **kw):
+        return params if params is not None else ADAPTIVE_PARAMS(float(kw["tol"]), float(kw["lum_floor"]), int(kw["min_passes"]), int(kw["max_passes"]),
+                                                                 int(kw.get("step", ADAPTIVE_STEP_DEFAULT)), int(kw.get("dilate", 0)))
+
+    @staticmethod
+    def _info(rec):
+        return {k: (float(rec[k]) if k == "deviceMs" else int(rec[k])) for k in ("passes", "pixels", "maxPasses", "nonfinite", "rounds", "deviceMs")}
+
+    def PathTraceBlockCounts(self, tid, channels, out_color, a_passNum, pass_counts=None, moments=None, tid_begin=0):
+        """PathTraceBlock with pass_counts[tid] passes for pixel tid (uint32 [winWidth * winHeight], absolute tid; None: a_passNum everywhere) and,
+        with moments (MOMENTS_DTYPE [winWidth * winHeight]), every sample's luminance added to the pixel's record. Both arrays are updated in place."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"]
+        assert pass_counts is None or (pass_counts.dtype == np.uint32 and pass_counts.flags["C_CONTIGUOUS"] and pass_counts.size == self.N)
+        assert moments is None or (moments.dtype == MOMENTS_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.size == self.N)
+        self._chk(self.L.hpt_path_trace_block_counts(self.h, tid_begin, tid, channels, out_color.ctypes.data, a_passNum,
+                                                     None if pass_counts is None else pass_counts.ctypes.data, None if moments is None else moments.ctypes.data))
+
+    def PathTraceBlockCounts_dev(self, dev_ptr, pass_num, counts_ptr=None, moments_ptr=None, tid_begin=0, tid_count=None, channels=4, naive=False, stream=None):
+        tid_count = self.N - tid_begin if tid_count is None else tid_count
+        self._chk(self.L.hpt_path_trace_block_counts_dev(self.h, tid_begin, tid_count, channels, dev_ptr, pass_num, int(naive), counts_ptr, moments_ptr, stream))
+
+    def AdaptivePlan(self, moments, tid=None, tid_begin=0, params=None, **kw):
+        """The planner: (pass counts uint32 [winWidth * winHeight] with the window filled in, totals as a dict). kw: tol, lum_floor, min_passes,
+        max_passes, step (default ADAPTIVE_STEP_DEFAULT), dilate (default 0)."""
+        assert moments.dtype == MOMENTS_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.size == self.N
+        p = self._adaptive_params(params, **kw)
+        counts, info = np.zeros(self.N, np.uint32), np.zeros(1, ADAPTIVE_INFO_DTYPE)
+        self._chk(self.L.hpt_adaptive_plan(self.h, tid_begin, self.N - tid_begin if tid is None else tid, C.byref(p), moments.ctypes.data, counts.ctypes.data, info.ctypes.data))
+        return counts, self._info(info[0])
+
+    def AdaptivePlan_dev(self, moments_ptr, counts_ptr, info_ptr, tid=None, tid_begin=0, params=None, stream=None, **kw):
+        p = self._adaptive_params(params, **kw)
+        self._chk(self.L.hpt_adaptive_plan_dev(self.h, tid_begin, self.N - tid_begin if tid is None else tid, C.byref(p), moments_ptr, counts_ptr, info_ptr, stream))
+
+    def AdaptiveResolve(self, frame, moments, out=None, tid=None, tid_begin=0):
+        """frame / passes per pixel for the first three channels (a pixel without passes: 0; a fourth channel: copied). out None: in place."""
+        assert frame.dtype == np.float32 and frame.flags["C_CONTIGUOUS"] and frame.size % self.N == 0
+        assert moments.dtype == MOMENTS_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.size == self.N
+        out = frame if out is None else out
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.size == frame.size
+        self._chk(self.L.hpt_adaptive_resolve(self.h, tid_begin, self.N - tid_begin if tid is None else tid, frame.size // self.N, frame.ctypes.data, moments.ctypes.data, out.ctypes.data))
+        return out
+
+    def AdaptiveResolve_dev(self, frame_ptr, moments_ptr, out_ptr, channels=4, tid=None, tid_begin=0, stream=None):
+        self._chk(self.L.hpt_adaptive_resolve_dev(self.h, tid_begin, self.N - tid_begin if tid is None else tid, channels, frame_ptr, moments_ptr, out_ptr, stream))
+
+    def PathTraceBlockAdaptive(self, tid, channels, out_color, max_rounds, moments=None, tid_begin=0, params=None, **kw):
+        """The adaptive loop: min_passes everywhere, then up to max_rounds rounds of plan + render. out_color is accumulated into (un-normalised);
+        moments, when given, receives the window's records (zeroed first). Returns the loop's report as a dict."""
+        assert out_color.dtype == np.float32 and out_color.flags["C_CONTIGUOUS"] and out_color.size == self.N * channels
+        assert moments is None or (moments.dtype == MOMENTS_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.size == self.N)
+        p = self._adaptive_params(params, **kw)
+        info = np.zeros(1, ADAPTIVE_INFO_DTYPE)
+        self._chk(self.L.hpt_path_trace_block_adaptive(self.h, tid_begin, tid, channels, out_color.ctypes.data, C.byref(p), max_rounds,
+                                                       None if moments is None else moments.ctypes.data, info.ctypes.data))
+        return self._info(info[0])
+
+    def PathTraceBlockAdaptive_dev(self, dev_ptr, max_rounds, moments_ptr=None, tid_begin=0, tid_count=None, channels=4, params=None, stream=None, **kw):
+        p = self._adaptive_params(params, **kw)
+        info = np.zeros(1, ADAPTIVE_INFO_DTYPE)
+        self._chk(self.L.hpt_path_trace_block_adaptive_dev(self.h, tid_begin, self.N - tid_begin if tid_count is None else tid_count, channels, dev_ptr, C.byref(p),
+                                                           max_rounds, moments_ptr, info.ctypes.data, stream))
+        return self._info(info[0])
 
     def PathTraceFromInputRaysBlock(self, tid, channels, in_rayPosAndNear, in_rayDirAndFar, out_color, a_passNum):
         """Integrator::PathTraceFromInputRaysBlock; rays: float32 [tid, 4] (RayPosAndW / RayDirAndT), camera space."""

@@ -21,10 +21,11 @@ struct Job
   uint  packedCount;              // entries in packedXY (the input-ray mode reads it only for the camera back plate)
   uint*  queue;                   // work-queue head (zeroed before launch)
   Counters* counters;             // instrumentation (STATS builds)
-  // differentiable rendering
-  const float* refImg;            // a_refImg
+  // differentiable rendering; the adaptive forward call (the ADAPT instantiations, which no DR call runs) keeps its two arrays in the storage of two of
+  // these pointers, both indexed by absolute tid like gens: passCounts (null: passNum for every pixel) and moments (null: no statistics)
+  union { const float* refImg; const uint* passCounts; };          // refImg: a_refImg
   const float* data;              // a_data
-  float* grad;                    // a_dataGrad (atomically accumulated)
+  union { float* grad; PixelMoments* moments; };                   // grad: a_dataGrad (atomically accumulated)
   // Pass slices (SLICED instantiations of pathTraceKernel, forward calls; hpt_set_option("pass_slice")) share the storage of four fields that
   // only PathTraceDR reads, so that Job - a by-value kernel argument of every kernel family - keeps its size and layout:
   //   passSlice       s > 0: the queue holds tidCount * passSliceCount(passNum, s) items (hpt_types.h: passSliceItem) and a pixel is handed
@@ -78,7 +79,8 @@ static_assert(sizeof(Job) == 184, "Job is a by-value argument of every kernel fa
 // SLICED: work items are runs of Job::passSlice passes of a pixel (instantiated for PathTrace from the camera: MODE 3, 0, 7 and moving instances)
 // LGRAD (with DR): light-colour gradients (hpt_shade.h: DrLights); the residency is the DR kernel's
 // ENV (with DR, without LGRAD): environment maps and their texel gradients (hpt_shade.h: drEnvSweep); the residency is the DR kernel's
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false, bool SLICED = false, bool LGRAD = false, bool ENV = false>
+// ADAPT: per-pixel pass counts (Job::passCounts) and luminance moments (Job::moments); whole pixels, forward calls from the camera (MODE 3, 0, 7 and moving instances)
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION = false, bool SWEEP = false, bool SLICED = false, bool LGRAD = false, bool ENV = false, bool ADAPT = false>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job);
 
 // spectral rendering (hpt_spectral.hip): one thread per pixel, four wavelengths per path
@@ -394,6 +396,19 @@ __global__ void __launch_bounds__(256) camInitGensKernel(Rng* gens, uint n);   /
 
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc);
 __global__ void wfLossFinishKernel(const double* acc, float* loss);
+
+// ---- adaptive sampling: planner and resolve (hpt_adaptive.hip) ---------------------------------------------------------------
+struct AdaptiveParams { float tol, lumFloor; uint minPasses, maxPasses, step, dilate; };                       // = hpt_adaptive_params
+struct AdaptiveInfo { unsigned long long passes; uint pixels, maxPasses, nonfinite, rounds; float deviceMs; uint reserved; };   // = hpt_adaptive_info
+static_assert(sizeof(AdaptiveParams) == 24 && sizeof(AdaptiveInfo) == 32, "the planner's records are 6 and 8 dwords");
+// one lane per tid of [tidBegin, tidBegin + tidCount): need[y * winWidth + x] = passes the pixel's moments ask for beyond those it has
+__global__ void __launch_bounds__(256) adaptiveNeedKernel(const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth, AdaptiveParams p, uint* need);
+// ... counts[tid] = the (dilated) need, clipped to maxPasses and to step; the totals are added to *info: one integer atomic per block and field
+__global__ void __launch_bounds__(256) adaptivePlanKernel(const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth, uint winHeight,
+                                                          AdaptiveParams p, const uint* need, uint* counts, AdaptiveInfo* info);
+// ... out[pixel] = frame[pixel] / passes for the first three channels (0 for a pixel without passes), the fourth copied; out may be frame
+__global__ void __launch_bounds__(256) adaptiveResolveKernel(const float* frame, const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth,
+                                                             uint channels, float* out);
 
 // ---- helper kernels (hpt_helpers.hip) ---------------------------------------------------------------------------------------------------
 __global__ void packXYKernel(uint* out, int W, int H, uint ts);

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <cmath>
 #include <string>
 #include <new>
 #include <stdexcept>
@@ -182,6 +183,9 @@ struct hpt_ctx
   uint lastPassSlice = 0;
   DevBuf<unsigned long long> dSliceMail;                 // [tid][SLICE_MAIL_WORDS]: the slices' hand-over mailbox (hpt_types.h), zeroed before every sliced launch
   uint* sliceError = nullptr;                            // pinned, device-visible: a lane gave up waiting for its predecessor (sliceErrorCheck)
+  // adaptive sampling (hpt_adaptive.hip): the loop's pass counts [tid], the planner's need image [pixel] and totals, the records of a
+  // loop whose caller keeps none, the host forms' copies of the caller's arrays; all grown on first use, none allocated per round
+  DevBuf<uint> dAdCounts, dAdNeed, dAdCountsIn; DevBuf<AdaptiveInfo> dAdInfo; DevBuf<PixelMoments> dAdMoments, dAdMomentsIn;
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
@@ -1792,16 +1796,16 @@ static int gridBlocks(hpt_ctx* c, bool dr, bool fullMaterials = false)
 
 // DEEP: the scene's BVH can need more than LDS_STACK stack entries, so pushes / pops check for the HBM overflow part
 // FLAT: single-level world-space BVH (static scenes within FLAT_TRI_BUDGET) vs two-level TLAS/BLAS
-template <bool STATS, bool DR, int NAIVE, bool SLICED = false, bool LGRAD = false, bool ENV = false>   // LGRAD: PathTraceDR / PathTraceVJP with lights registered (hpt_put_diff_lights); ENV: over an environment map ("dr_environment")
+template <bool STATS, bool DR, int NAIVE, bool SLICED = false, bool LGRAD = false, bool ENV = false, bool ADAPT = false>   // ADAPT: per-pixel pass counts and moments; LGRAD: PathTraceDR / PathTraceVJP with lights registered (hpt_put_diff_lights); ENV: over an environment map ("dr_environment")
 static void launchPT(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
-  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+  if (S.sweep) pathTraceKernel<STATS, DR, NAIVE, false, false, false, true, SLICED, LGRAD, ENV, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   else if (S.flatMode) {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, true, false, false, SLICED, LGRAD, ENV, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, true, false, false, SLICED, LGRAD, ENV, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED, LGRAD, ENV><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<STATS, DR, NAIVE, true, false, false, false, SLICED, LGRAD, ENV, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<STATS, DR, NAIVE, false, false, false, false, SLICED, LGRAD, ENV, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -1837,15 +1841,15 @@ static void launchSpectralBlock(const DevScene& S, const Job& job, int blocks, h
 }
 
 // the MOTION variants: moving instances (two-level layout only), every BSDF branch
-template <int MODE, bool SLICED = false>
+template <int MODE, bool SLICED = false, bool ADAPT = false>
 static void launchPTMotion(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
   if (S.flatMode) {
-    if (deep) pathTraceKernel<false, false, MODE, true, true, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<false, false, MODE, false, true, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<false, false, MODE, true, true, true, false, SLICED, false, false, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<false, false, MODE, false, true, true, false, SLICED, false, false, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   } else {
-    if (deep) pathTraceKernel<false, false, MODE, true, false, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
-    else      pathTraceKernel<false, false, MODE, false, false, true, false, SLICED><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    if (deep) pathTraceKernel<false, false, MODE, true, false, true, false, SLICED, false, false, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
+    else      pathTraceKernel<false, false, MODE, false, false, true, false, SLICED, false, false, ADAPT><<<dim3(blocks), dim3(256), 0, st>>>(S, job);
   }
 }
 
@@ -2135,11 +2139,22 @@ static int sliceErrorCheck(hpt_ctx* c)
   return c->fail(HPT_ERR_STATE, "PathTraceBlock with pass slices: a lane waited for the slice before its own beyond the poll limit; the frame of that call is incomplete");
 }
 
-static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st)
+// Adaptive sampling serves forward RGB calls from the camera on the megakernel's ADAPT instantiations. What has none is refused by this one check:
+// launch_path_trace makes it for every adaptive call, and the loop makes it once more before it touches the caller's records.
+static int adaptiveRefusal(hpt_ctx* c, bool naive, bool inRays)
+{
+  const char* why = c->S.spectralMode != 0u ? "m_spectral_mode" : (c->hasFilm ? "scenes with thin films" : (naive ? "the naive integrator" :
+                    (inRays ? "input rays" : (c->instrument ? "the instrumented probe" : nullptr))));
+  if (why) return c->fail(HPT_ERR_UNSUPPORTED, std::string("adaptive sampling (per-pixel pass counts): not served for ") + why + " (DESIGN.md 2.13)");
+  return HPT_OK;
+}
+
+static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st, bool adapt = false)   // adapt: Job::passCounts / moments are set (the ADAPT kernels)
 {
   const bool inRays = job.inRayPos != nullptr;
   c->lastPassSlice = 0u;
   if (int rc = sliceErrorCheck(c)) return rc;
+  if (adapt) { if (int rc = adaptiveRefusal(c, naive, inRays)) return rc; }
   if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before CommitDeviceData / UpdateMembersPlainData");
   if (!inRays && c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlock before PackXYBlock");
   job.tidStride = c->tidStride > 1 ? c->tidStride : 1u;
@@ -2245,18 +2260,18 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   // one item per ray), and not its instrumented probe nor the block-local schedule, which have their own loops. The slice doubles until the
   // item count fits the queue's 32-bit head with room for every lane's last draw.
   const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
-  const bool streamCall = c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u;
-  const bool waveCall = !streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount);
+  const bool streamCall = !adapt && c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u;
+  const bool waveCall = !adapt && !streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount);
   // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
   // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
   // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
   // the light fixtures with every BSDF branch stay on the plain megakernel (typed_materials, estimate 4.8: 1186 vs 1133) - profiles/bw_check.py, bw_heavy.py
   const bool bwLean = dr || (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u);
   const bool bwAuto = c->schedule == 0 && bwLean && c->sahVisits >= BLOCK_SAH_VISITS && !drLights && !drEnv;   // (no block-local kernel with light gradients or environment maps)
-  const bool blockLocal = (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
+  const bool blockLocal = !adapt && (c->schedule == 3 || bwAuto) && !naive && !inRays && !motion && !film && !stats && c->S.sweep == 0u;
   const size_t fullGrid = (size_t)gridBlocks(c, dr, fullMaterials && !mode7) * 256;
   const uint sliceWanted = c->passSlice >= 0 ? (uint)c->passSlice : passSliceAuto(job.tidCount, fullGrid, job.passNum);
-  uint slice = (dr || inRays || naive || film || stats || blockLocal || streamCall || waveCall) ? 0u : sliceWanted;
+  uint slice = (adapt || dr || inRays || naive || film || stats || blockLocal || streamCall || waveCall) ? 0u : sliceWanted;   // (adaptive calls: whole pixels)
   while (slice != 0u && (uint64_t)job.tidCount * passSliceCount(job.passNum, slice) > (1ull << 31)) slice *= 2u;
   if (slice >= job.passNum) slice = 0u;                           // one item per pixel either way: the plain form
   const size_t items = (size_t)job.tidCount * passSliceCount(job.passNum, slice);
@@ -2319,6 +2334,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     }
     else if (motion) {
       if (inRays) launchPTMotion<2>(c->S, job, blocks, st, deep); else if (naive) launchPTMotion<1>(c->S, job, blocks, st, deep);
+      else if (adapt) launchPTMotion<0, false, true>(c->S, job, blocks, st, deep);
       else if (slice != 0u) launchPTMotion<0, true>(c->S, job, blocks, st, deep); else launchPTMotion<0>(c->S, job, blocks, st, deep);
     }
     else if (dr) {
@@ -2344,6 +2360,11 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
       DevScene Sp = c->S;
       Sp.statsWide = (wfWide(c) && (c->statsWide || useWavefront(c, naive, dr, false, job.tidCount))) ? 1u : 0u;   // "stats_wide": the caller says the measured call ran there
       launchPT<true, false, 0>(Sp, job, blocks, st, deep || (Sp.statsWide && c->stackNeeded4 > (uint)LDS_STACK));
+    }
+    else if (adapt) {
+      if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) launchPT<false, false, 3, false, false, false, true>(c->S, job, blocks, st, deep);
+      else if (mode7) launchPT<false, false, 7, false, false, false, true>(c->S, job, blocks, st, deep);
+      else launchPT<false, false, 0, false, false, false, true>(c->S, job, blocks, st, deep);
     }
     else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) { if (slice != 0u) launchPT<false, false, 3, true>(c->S, job, blocks, st, deep); else launchPT<false, false, 3>(c->S, job, blocks, st, deep); }
     else if (mode7)  { if (slice != 0u) launchPT<false, false, 7, true>(c->S, job, blocks, st, deep); else launchPT<false, false, 7>(c->S, job, blocks, st, deep); }
@@ -2442,6 +2463,215 @@ catch (...) { return hptGuard(c, "hpt_path_trace_block"); }
 extern "C" int hpt_naive_path_trace_block(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, uint32_t passNum)
 try { return path_trace_host(c, tidBegin, tidCount, channels, out, passNum, 1); }
 catch (...) { return hptGuard(c, "hpt_naive_path_trace_block"); }
+
+// ---- adaptive sampling (hpt_adaptive.hip, the ADAPT instantiations of pathTraceKernel) ----------------------------------------
+static_assert(sizeof(hpt_pixel_moments) == sizeof(PixelMoments) && sizeof(hpt_adaptive_params) == sizeof(AdaptiveParams) && sizeof(hpt_adaptive_info) == sizeof(AdaptiveInfo),
+              "the public records of adaptive sampling are the kernels' records");
+extern "C" int hpt_path_trace_block_counts_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum, int naive,
+                                               const uint32_t* passCountsDev, hpt_pixel_moments* momentsDev, void* stream)
+try {
+  if (!c || !outDev) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (tidCount == 0 || (passNum == 0 && !passCountsDev)) return HPT_OK;
+  Job job; std::memset(&job, 0, sizeof(job));
+  job.tidBegin = tidBegin; job.tidCount = tidCount; job.passNum = passNum; job.channels = channels; job.outColor = outDev;
+  job.passCounts = passCountsDev; job.moments = (PixelMoments*)momentsDev;
+  return launch_path_trace(c, job, naive != 0, false, (hipStream_t)stream, true);
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_block_counts_dev"); }
+
+// the planner's and the resolve's window: tids [tidBegin, tidBegin + tidCount) of the packed viewport
+static int adaptiveWindowCheck(hpt_ctx* c, const char* what, uint32_t tidBegin, uint32_t tidCount)
+{
+  const std::string w(what);
+  if (!c->paramsSet) return c->fail(HPT_ERR_STATE, w + " before UpdateMembersPlainData");
+  if (c->packedCount == 0u || c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, w + " before PackXYBlock");
+  if ((uint64_t)tidBegin + tidCount > c->packedCount) return c->fail(HPT_ERR_ARG, w + ": tid range exceeds the viewport");
+  return HPT_OK;
+}
+static int adaptiveParamsCheck(hpt_ctx* c, const char* what, const hpt_adaptive_params* p)
+{
+  const std::string w(what);
+  if (!p) return c->fail(HPT_ERR_ARG, w + ": params is null");
+  if (!std::isfinite(p->tol) || !(p->tol > 0.0f)) return c->fail(HPT_ERR_ARG, w + ": tol must be finite and above 0");
+  if (!std::isfinite(p->lumFloor) || !(p->lumFloor > 0.0f)) return c->fail(HPT_ERR_ARG, w + ": lumFloor must be finite and above 0");
+  if (p->minPasses < 1u || p->minPasses > p->maxPasses) return c->fail(HPT_ERR_ARG, w + ": 1 <= minPasses <= maxPasses is required");
+  if (p->step < 1u) return c->fail(HPT_ERR_ARG, w + ": step must be at least 1");
+  if (p->dilate > 1u) return c->fail(HPT_ERR_ARG, w + ": dilate is 0 or 1");
+  return HPT_OK;
+}
+// one planning step on st: zero the need image and *infoDev, every pixel's own need, then the counts and the totals (checks made by the callers)
+static int adaptivePlanLaunch(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const AdaptiveParams& p, const PixelMoments* momentsDev, uint* countsDev, AdaptiveInfo* infoDev, hipStream_t st)
+{
+  const size_t pixels = (size_t)c->packedCount;
+  HIPCHK(c, c->dAdNeed.alloc(pixels));
+  HIPCHK(c, hipMemsetAsync(c->dAdNeed.p, 0, pixels * sizeof(uint), st));
+  HIPCHK(c, hipMemsetAsync(infoDev, 0, sizeof(AdaptiveInfo), st));
+  const dim3 g((tidCount + 255u) / 256u), b(256);
+  adaptiveNeedKernel<<<g, b, 0, st>>>(momentsDev, c->dPackedXY.p, tidBegin, tidCount, (uint)c->S.winWidth, p, c->dAdNeed.p);
+  adaptivePlanKernel<<<g, b, 0, st>>>(momentsDev, c->dPackedXY.p, tidBegin, tidCount, (uint)c->S.winWidth, (uint)c->S.winHeight, p, c->dAdNeed.p, countsDev, infoDev);
+  HIPCHK(c, hipGetLastError());
+  return HPT_OK;
+}
+// What the loop refuses before it touches anything: the loop zeroes, plans and counts the contiguous window [tidBegin, tidBegin + tidCount), while a
+// render under hpt_set_tid_interleave with stride > 1 visits every stride-th chunk, far outside it - its counts would be read from words no planner wrote.
+static int adaptiveLoopCheck(hpt_ctx* c, uint32_t channels)
+{
+  if (c->tidStride > 1) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockAdaptive: the loop plans one contiguous tid window; under hpt_set_tid_interleave with stride > 1 drive "
+                                                            "hpt_path_trace_block_counts_dev and hpt_adaptive_plan_dev yourself, or reset the interleave");
+  if (int rc = adaptiveRefusal(c, false, false)) return rc;
+  if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "PathTraceBlockAdaptive before CommitDeviceData");
+  if (c->dGens.n < (size_t)c->packedCount) return c->fail(HPT_ERR_STATE, "PathTraceBlockAdaptive: m_randomGens smaller than the thread range (InitRandomGens)");
+  if (channels != 1u && channels != 3u && channels != 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockAdaptive: 1, 3 or 4 channels");
+  return HPT_OK;
+}
+static AdaptiveParams adaptiveParamsOf(const hpt_adaptive_params* p) { AdaptiveParams q; std::memcpy(&q, p, sizeof(q)); return q; }
+
+extern "C" int hpt_adaptive_plan_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const hpt_adaptive_params* params, const hpt_pixel_moments* momentsDev,
+                                     uint32_t* passCountsDev, hpt_adaptive_info* infoDev, void* stream)
+try {
+  if (!c || !momentsDev || !passCountsDev || !infoDev) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveParamsCheck(c, "AdaptivePlan", params)) return rc;
+  if (int rc = adaptiveWindowCheck(c, "AdaptivePlan", tidBegin, tidCount)) return rc;
+  if (tidCount == 0) { HIPCHK(c, hipMemsetAsync(infoDev, 0, sizeof(AdaptiveInfo), (hipStream_t)stream)); return HPT_OK; }
+  return adaptivePlanLaunch(c, tidBegin, tidCount, adaptiveParamsOf(params), (const PixelMoments*)momentsDev, passCountsDev, (AdaptiveInfo*)infoDev, (hipStream_t)stream);
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_plan_dev"); }
+
+extern "C" int hpt_adaptive_resolve_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frameDev, const hpt_pixel_moments* momentsDev,
+                                        float* outDev, void* stream)
+try {
+  if (!c || !frameDev || !momentsDev || !outDev) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (channels != 1u && channels != 3u && channels != 4u) return c->fail(HPT_ERR_ARG, "AdaptiveResolve: channels must be 1, 3 or 4");
+  if (int rc = adaptiveWindowCheck(c, "AdaptiveResolve", tidBegin, tidCount)) return rc;
+  if (tidCount == 0) return HPT_OK;
+  adaptiveResolveKernel<<<dim3((tidCount + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>(frameDev, (const PixelMoments*)momentsDev, c->dPackedXY.p, tidBegin, tidCount,
+                                                                                                (uint)c->S.winWidth, channels, outDev);
+  HIPCHK(c, hipGetLastError());
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_resolve_dev"); }
+
+extern "C" int hpt_path_trace_block_adaptive_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, const hpt_adaptive_params* params,
+                                                 uint32_t maxRounds, hpt_pixel_moments* momentsDev, hpt_adaptive_info* info, void* stream)
+try {
+  if (!c || !outDev || !info) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveParamsCheck(c, "PathTraceBlockAdaptive", params)) return rc;
+  if (int rc = adaptiveWindowCheck(c, "PathTraceBlockAdaptive", tidBegin, tidCount)) return rc;
+  if (int rc = adaptiveLoopCheck(c, channels)) return rc;
+  hipStream_t st = (hipStream_t)stream;
+  AdaptiveInfo res; std::memset(&res, 0, sizeof(res));
+  if (tidCount == 0) { std::memcpy(info, &res, sizeof(res)); return HPT_OK; }
+  const AdaptiveParams p = adaptiveParamsOf(params);
+  if (!momentsDev) { HIPCHK(c, c->dAdMoments.alloc(c->packedCount)); momentsDev = (hpt_pixel_moments*)c->dAdMoments.p; }
+  HIPCHK(c, c->dAdCounts.alloc(c->packedCount));
+  HIPCHK(c, c->dAdInfo.alloc(1));
+  HIPCHK(c, hipMemsetAsync(momentsDev + tidBegin, 0, (size_t)tidCount * sizeof(PixelMoments), st));
+  float ms = 0.0f, kms = 0.0f;
+  // round 0: minPasses everywhere
+  if (int rc = hpt_path_trace_block_counts_dev(c, tidBegin, tidCount, channels, outDev, p.minPasses, 0, nullptr, momentsDev, stream)) return rc;
+  res.rounds = 1u; res.passes = (unsigned long long)p.minPasses * tidCount;
+  AdaptiveInfo plan; std::memset(&plan, 0, sizeof(plan));
+  for (uint32_t round = 0; ; round++) {
+    if (int rc = adaptivePlanLaunch(c, tidBegin, tidCount, p, (const PixelMoments*)momentsDev, c->dAdCounts.p, c->dAdInfo.p, st)) return rc;
+    HIPCHK(c, hipMemcpyAsync(&plan, c->dAdInfo.p, sizeof(plan), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));                         // (the render launch before this plan has finished: its event pair can be read)
+    if (int rc = sliceErrorCheck(c)) return rc;
+    (void)hipEventElapsedTime(&kms, c->ev0, c->ev1); ms += kms;
+    if (plan.passes == 0ull || round >= maxRounds) break;
+    if (int rc = hpt_path_trace_block_counts_dev(c, tidBegin, tidCount, channels, outDev, 0u, 0, c->dAdCounts.p, momentsDev, stream)) return rc;
+    res.rounds++; res.passes += plan.passes;
+  }
+  res.pixels = plan.pixels; res.maxPasses = plan.maxPasses; res.nonfinite = plan.nonfinite; res.deviceMs = ms;
+  c->lastKernelMs = ms;
+  std::memcpy(info, &res, sizeof(res));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_block_adaptive_dev"); }
+
+// the host-pointer forms: the caller's arrays are indexed by absolute tid; their window goes to context-owned device arrays at the same offsets
+static int adaptiveUploadWindow(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const uint32_t* counts, const hpt_pixel_moments* moments)
+{
+  if (counts) { HIPCHK(c, c->dAdCountsIn.alloc(c->packedCount)); HIPCHK(c, hipMemcpy(c->dAdCountsIn.p + tidBegin, counts + tidBegin, (size_t)tidCount * sizeof(uint), hipMemcpyHostToDevice)); }
+  if (moments) { HIPCHK(c, c->dAdMomentsIn.alloc(c->packedCount)); HIPCHK(c, hipMemcpy(c->dAdMomentsIn.p + tidBegin, moments + tidBegin, (size_t)tidCount * sizeof(PixelMoments), hipMemcpyHostToDevice)); }
+  return HPT_OK;
+}
+extern "C" int hpt_path_trace_block_counts(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, uint32_t passNum,
+                                           const uint32_t* passCounts, hpt_pixel_moments* moments)
+try {
+  if (!c || !out) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveWindowCheck(c, "PathTraceBlockCounts", tidBegin, tidCount)) return rc;
+  if (c->tidStride > 1) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockCounts: the host-pointer form copies one contiguous tid window (use the device form with hpt_set_tid_interleave)");
+  const size_t n = (size_t)c->S.winWidth * c->S.winHeight * channels;
+  const bool runs = tidCount != 0 && (passNum != 0 || passCounts);
+  return roundTrip(c, c->tSlots[T_PATH_TRACE], runs ? KERNEL_EVENTS : KERNEL_NONE,
+                   [&]() -> int { HIPCHK(c, c->dFrame.alloc(n)); HIPCHK(c, hipMemcpy(c->dFrame.p, out, n * 4, hipMemcpyHostToDevice)); return adaptiveUploadWindow(c, tidBegin, tidCount, passCounts, moments); },
+                   [&]() -> int { return hpt_path_trace_block_counts_dev(c, tidBegin, tidCount, channels, c->dFrame.p, passNum, 0, passCounts ? c->dAdCountsIn.p : nullptr,
+                                                                         moments ? (hpt_pixel_moments*)c->dAdMomentsIn.p : nullptr, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * 4, hipMemcpyDeviceToHost));
+                                  if (moments && runs) HIPCHK(c, hipMemcpy(moments + tidBegin, c->dAdMomentsIn.p + tidBegin, (size_t)tidCount * sizeof(PixelMoments), hipMemcpyDeviceToHost));
+                                  return HPT_OK; });
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_block_counts"); }
+
+extern "C" int hpt_adaptive_plan(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const hpt_adaptive_params* params, const hpt_pixel_moments* moments,
+                                 uint32_t* passCounts, hpt_adaptive_info* info)
+try {
+  if (!c || !moments || !passCounts || !info) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveParamsCheck(c, "AdaptivePlan", params)) return rc;
+  if (int rc = adaptiveWindowCheck(c, "AdaptivePlan", tidBegin, tidCount)) return rc;
+  if (int rc = adaptiveUploadWindow(c, tidBegin, tidCount, nullptr, moments)) return rc;
+  HIPCHK(c, c->dAdCountsIn.alloc(c->packedCount));
+  HIPCHK(c, c->dAdInfo.alloc(1));
+  if (int rc = hpt_adaptive_plan_dev(c, tidBegin, tidCount, params, (const hpt_pixel_moments*)c->dAdMomentsIn.p, c->dAdCountsIn.p, (hpt_adaptive_info*)c->dAdInfo.p, nullptr)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(passCounts + tidBegin, c->dAdCountsIn.p + tidBegin, (size_t)tidCount * sizeof(uint), hipMemcpyDeviceToHost));
+  HIPCHK(c, hipMemcpy(info, c->dAdInfo.p, sizeof(AdaptiveInfo), hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_plan"); }
+
+extern "C" int hpt_adaptive_resolve(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frame, const hpt_pixel_moments* moments, float* out)
+try {
+  if (!c || !frame || !moments || !out) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (channels != 1u && channels != 3u && channels != 4u) return c->fail(HPT_ERR_ARG, "AdaptiveResolve: channels must be 1, 3 or 4");
+  if (int rc = adaptiveWindowCheck(c, "AdaptiveResolve", tidBegin, tidCount)) return rc;
+  const size_t n = (size_t)c->packedCount * channels;
+  DevBuf<float> dOut;                                            // (out may be frame: the caller's out is uploaded first so that pixels outside the window keep their contents)
+  HIPCHK(c, dOut.upload(out, n));
+  HIPCHK(c, c->dFrame.upload(frame, n));
+  if (int rc = adaptiveUploadWindow(c, tidBegin, tidCount, nullptr, moments)) return rc;
+  if (int rc = hpt_adaptive_resolve_dev(c, tidBegin, tidCount, channels, c->dFrame.p, (const hpt_pixel_moments*)c->dAdMomentsIn.p, dOut.p, nullptr)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(out, dOut.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_resolve"); }
+
+extern "C" int hpt_path_trace_block_adaptive(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, const hpt_adaptive_params* params,
+                                             uint32_t maxRounds, hpt_pixel_moments* moments, hpt_adaptive_info* info)
+try {
+  if (!c || !out || !info) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveParamsCheck(c, "PathTraceBlockAdaptive", params)) return rc;
+  if (int rc = adaptiveWindowCheck(c, "PathTraceBlockAdaptive", tidBegin, tidCount)) return rc;
+  if (int rc = adaptiveLoopCheck(c, channels)) return rc;
+  const size_t n = (size_t)c->packedCount * channels;
+  HIPCHK(c, c->dFrame.upload(out, n));
+  if (moments) HIPCHK(c, c->dAdMomentsIn.alloc(c->packedCount));
+  if (int rc = hpt_path_trace_block_adaptive_dev(c, tidBegin, tidCount, channels, c->dFrame.p, params, maxRounds, moments ? (hpt_pixel_moments*)c->dAdMomentsIn.p : nullptr, info, nullptr)) return rc;
+  HIPCHK(c, hipDeviceSynchronize());
+  HIPCHK(c, hipMemcpy(out, c->dFrame.p, n * sizeof(float), hipMemcpyDeviceToHost));
+  if (moments && tidCount) HIPCHK(c, hipMemcpy(moments + tidBegin, c->dAdMomentsIn.p + tidBegin, (size_t)tidCount * sizeof(PixelMoments), hipMemcpyDeviceToHost));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_path_trace_block_adaptive"); }
 
 // ---- EvalGBuffer (integrator_pt.h:251, integrator_gbuffer.cpp:264-267) ------------------------------------------------------------------------
 static_assert(sizeof(hpt_gbuffer_pixel) == 60 && sizeof(hpt_gbuffer_pixel) == sizeof(GBufferPixel), "GBufferPixel is 15 dwords (integrator_pt.h:187-198)");

@@ -23,9 +23,10 @@
 
 namespace hpt {
 
-template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED, bool LGRAD, bool ENV>
+template <bool STATS, bool DR, int MODE, bool DEEP, bool FLAT, bool MOTION, bool SWEEP, bool SLICED, bool LGRAD, bool ENV, bool ADAPT>
 __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const Job job)
 {
+  static_assert(!ADAPT || (!DR && !STATS && !SLICED && MODE != 2 && MODE != 6), "adaptive sampling: forward calls from the camera, whole pixels");
   static_assert(!LGRAD || (DR && !STATS), "light-colour gradients: the uninstrumented DR kernel");
   static_assert(!ENV || (DR && !STATS && !LGRAD), "environment maps in DR: the uninstrumented DR kernel, without light-colour gradients");
   constexpr bool NAIVE = (MODE == 1 || MODE == 5), INRAYS = (MODE == 2 || MODE == 6), LEAN = (MODE == 3), FILM = (MODE >= 4 && MODE <= 6);   // (MODE 7 = MODE 0 built for one more wave per SIMD)
@@ -37,7 +38,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   // Cold per-PIXEL state (touched once per path, not per bounce) is parked in LDS so that it does not occupy VGPRs
   // across the two traversals and the shading code: running framebuffer value, packed (x,y), tid, passes left.
   __shared__ float coldPix[3 * 256];
-  __shared__ uint  coldU[(SLICED ? 5 : 3) * 256];
+  __shared__ uint  coldU[(SLICED ? 5 : (ADAPT ? 6 : 3)) * 256];
   __shared__ uint  drStage[DR ? 4 * DR_STAGE_DWORDS : 1];               // PathTraceDR: the waves' staging areas of the cooperative gradient scatter
   // light-colour gradients (LGRAD): the workgroup's bins and the light plane of the adjoint record (hpt_shade.h). The bounce terms live in the
   // record, not in registers: they must outlast the path (PathTraceDR's seed is known at its end) and four dwords for each of up to 16 bounces
@@ -54,6 +55,10 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 #define PIX_PASSES  coldU[2 * 256 + threadIdx.x]
 #define PIX_SLICE   coldU[3 * 256 + threadIdx.x]      // SLICED: the slice of the pixel this lane holds or waits for
 #define PIX_POLLS   coldU[4 * 256 + threadIdx.x]      // ... and how often it has polled for it
+#define PIX_MOM(k)  coldU[(3 + (k)) * 256 + threadIdx.x]   // ADAPT: the pixel's moments record while the lane holds it: bits of sumY, bits of sumY2, passes
+  // Adaptive sampling (the ADAPT instantiations): a pixel's pass count comes from Job::passCounts[tid], a pixel with count 0 is
+  // neither loaded nor stored, and every sample's luminance is added to the pixel's moments. The other instantiations hold none of this.
+  const bool momentsOn = ADAPT && job.moments != nullptr;
   // Pass slices (the SLICED instantiations, Job::passSlice > 0): an item is `passSlice` passes of a pixel, and a lane that drew a later slice is
   // `pending` until the lane that holds the slice before it has published the pixel and its generator. The other
   // instantiations hold none of this: their code is the whole-pixel loop as it was.
@@ -99,30 +104,46 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
       if (job.channels == 1) job.outColor[pixel] = PIX(0);
       else { float* o = job.outColor + (size_t)pixel * job.channels; o[0] = PIX(0); o[1] = PIX(1); o[2] = PIX(2); }
       job.gens[PIX_TID] = gen;                                           // kernel_ContributeToImage: m_randomGens[tid] = *gen (:605)
+      if constexpr (ADAPT) {
+        if (momentsOn) { PixelMoments m; m.sumY = __uint_as_float(PIX_MOM(0)); m.sumY2 = __uint_as_float(PIX_MOM(1)); m.passes = PIX_MOM(2); m.reserved = 0u; job.moments[PIX_TID] = m; }
+      }
       havePixel = false;
     }
     // ---- (2) work queue: ballot the idle lanes, one atomic per wave, prefix-sum the ranks --------------------------------
     if constexpr (!SLICED) {
-      const bool need = !alive && !havePixel && !drained;
-      const unsigned long long mask = __ballot(need);
-      if (mask != 0ull) {
-        uint base = 0;
-        if (need && mbcnt64(mask) == 0u) base = atomicAdd(job.queue, (uint)__popcll(mask));
-        base = __shfl(base, (int)(__ffsll((long long)mask) - 1));
-        if (need) {
-          const uint k = base + mbcnt64(mask);
-          const uint tid = tidOfIndex(job.tidBegin, job.tidChunk, job.tidStride, k);
-          if (k < job.tidCount && tid < job.tidEnd) {
-            const uint XY = INRAYS ? 0u : job.packedXY[tid];
-            gen = job.gens[tid];
-            const uint pixel = INRAYS ? tid : ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
-            if (job.channels == 1) { PIX(0) = job.outColor[pixel]; PIX(1) = 0.0f; PIX(2) = 0.0f; }
-            else { const float* o = job.outColor + (size_t)pixel * job.channels; PIX(0) = o[0]; PIX(1) = o[1]; PIX(2) = o[2]; }
-            PIX_XY = XY; PIX_TID = tid; PIX_PASSES = job.passNum;
-            havePixel = true;
-          } else drained = true;
+      // (ADAPT: a lane that drew a pixel with count 0 leaves the pixel, its generator and its moments alone and asks again in the same trip.
+      // Every turn of the loop moves the queue head, which ends at tidCount.)
+      bool again;
+      do {
+        again = false;
+        const bool need = !alive && !havePixel && !drained;
+        const unsigned long long mask = __ballot(need);
+        if (mask != 0ull) {
+          uint base = 0;
+          if (need && mbcnt64(mask) == 0u) base = atomicAdd(job.queue, (uint)__popcll(mask));
+          base = __shfl(base, (int)(__ffsll((long long)mask) - 1));
+          if (need) {
+            const uint k = base + mbcnt64(mask);
+            const uint tid = tidOfIndex(job.tidBegin, job.tidChunk, job.tidStride, k);
+            if (k < job.tidCount && tid < job.tidEnd) {
+              uint passes = job.passNum;
+              if constexpr (ADAPT) { if (job.passCounts != nullptr) passes = job.passCounts[tid]; }
+              if (!ADAPT || passes != 0u) {
+                const uint XY = INRAYS ? 0u : job.packedXY[tid];
+                gen = job.gens[tid];
+                const uint pixel = INRAYS ? tid : ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
+                if (job.channels == 1) { PIX(0) = job.outColor[pixel]; PIX(1) = 0.0f; PIX(2) = 0.0f; }
+                else { const float* o = job.outColor + (size_t)pixel * job.channels; PIX(0) = o[0]; PIX(1) = o[1]; PIX(2) = o[2]; }
+                PIX_XY = XY; PIX_TID = tid; PIX_PASSES = passes;
+                if constexpr (ADAPT) {
+                  if (momentsOn) { const PixelMoments m = job.moments[tid]; PIX_MOM(0) = __float_as_uint(m.sumY); PIX_MOM(1) = __float_as_uint(m.sumY2); PIX_MOM(2) = m.passes; }
+                }
+                havePixel = true;
+              } else again = true;
+            } else drained = true;
+          }
         }
-      }
+      } while (ADAPT && __any(again));
     } else {
       const bool need = !alive && !havePixel && !drained && !pending;
       bool ready = false;                                                   // this lane may load its pixel now
@@ -317,6 +338,18 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
           if (INRAYS) { PIX(0) += accum.x; PIX(1) += accum.y; PIX(2) += accum.z; }        // kernel_CopyColorToOutput: raw accumColor
           else if (job.channels == 1) PIX(0) += accum.x * S.exposureMult;
           else { PIX(0) += S.exposureMult * c.x; PIX(1) += S.exposureMult * c.y; PIX(2) += S.exposureMult * c.z; }
+          if constexpr (ADAPT) {
+            // the sample's luminance from the very values added above (Rec. 709 weights; the one value of a one-channel frame), in f32 and in
+            // this order; a non-finite sample is added as it is, as the frame adds it
+            if (momentsOn) {
+              float y;
+              if (job.channels == 1) y = accum.x * S.exposureMult;
+              else { const float r = S.exposureMult * c.x, g = S.exposureMult * c.y, b = S.exposureMult * c.z; y = (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+              PIX_MOM(0) = __float_as_uint(__uint_as_float(PIX_MOM(0)) + y);
+              PIX_MOM(1) = __float_as_uint(__uint_as_float(PIX_MOM(1)) + y * y);
+              PIX_MOM(2) = PIX_MOM(2) + 1u;
+            }
+          }
         }
         alive = false;
       }
@@ -345,6 +378,7 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 #undef PIX_PASSES
 #undef PIX_SLICE
 #undef PIX_POLLS
+#undef PIX_MOM
   if (STATS) {
     // wave-reduce, one atomic per counter per wave
     unsigned long long v[8] = { nRays, st.nodes, st.tris, nHits, nShadow, nPaths, st.insts, 0ull };
@@ -397,8 +431,15 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
   template __global__ void pathTraceKernel<false, false, MODE, false, true,  false, false, true>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<false, false, MODE, true,  true,  false, false, true>(const DevScene, const Job); \
   template __global__ void pathTraceKernel<false, false, MODE, false, false, false, true,  true>(const DevScene, const Job);
+// ... and the five with per-pixel pass counts and moments (adaptive sampling: what the pass slices serve)
+#define HPT_INST4_ADAPT(MODE) \
+  template __global__ void pathTraceKernel<false, false, MODE, false, false, false, false, false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, true,  false, false, false, false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, false, true,  false, false, false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, true,  true,  false, false, false, false, false, true>(const DevScene, const Job); \
+  template __global__ void pathTraceKernel<false, false, MODE, false, false, false, true,  false, false, false, true>(const DevScene, const Job);
 #ifndef HPT_INST_GROUP
-#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..21"
+#error "compile hpt_kernels.hip with -DHPT_INST_GROUP=1..25"
 #endif
 #if HPT_INST_GROUP == 1      // gltf + emissive scenes (every benchmark workload)
 HPT_INST4(false, false, 3)
@@ -473,6 +514,17 @@ template __global__ void pathTraceKernel<false, false, 1, false, true, true>(con
 template __global__ void pathTraceKernel<false, false, 1, true,  true, true>(const DevScene, const Job);
 template __global__ void pathTraceKernel<false, false, 2, false, true, true>(const DevScene, const Job);
 template __global__ void pathTraceKernel<false, false, 2, true,  true, true>(const DevScene, const Job);
+#elif HPT_INST_GROUP == 22   // adaptive sampling: gltf + emissive scenes
+HPT_INST4_ADAPT(3)
+#elif HPT_INST_GROUP == 23   // adaptive sampling: every BSDF branch
+HPT_INST4_ADAPT(0)
+#elif HPT_INST_GROUP == 24   // adaptive sampling: every BSDF branch at 4 waves per SIMD
+HPT_INST4_ADAPT(7)
+#elif HPT_INST_GROUP == 25   // adaptive sampling: moving instances (PathTrace only), both layouts
+template __global__ void pathTraceKernel<false, false, 0, false, false, true, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, true,  false, true, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, false, true,  true, false, false, false, false, true>(const DevScene, const Job);
+template __global__ void pathTraceKernel<false, false, 0, true,  true,  true, false, false, false, false, true>(const DevScene, const Job);
 #endif
 
 } // namespace hpt

@@ -306,6 +306,11 @@ HPT_HD SliceItem passSliceItem(uint k, uint tidCount, uint passNum, uint s)
 HPT_HD unsigned long long sliceWordPack(uint slice, uint payload) { return ((unsigned long long)(slice + 1u) << 32) | (unsigned long long)payload; }
 HPT_HD bool sliceWordFor(unsigned long long w, uint slice) { return slice != 0u && (uint)(w >> 32) == slice; }   // is w what slice `slice` waits for?
 HPT_HD uint sliceWordPayload(unsigned long long w) { return (uint)(w & 0xFFFFFFFFull); }
+// Adaptive sampling (the ADAPT instantiations of pathTraceKernel, hpt_adaptive.hip): one record per tid = hpt_pixel_moments.
+// sumY / sumY2: the sums of the samples' luminance and of its square, in pass order; passes: samples added. Read when a lane loads the
+// pixel, written back when it flushes it.
+struct PixelMoments { float sumY, sumY2; uint passes, reserved; };
+static_assert(sizeof(PixelMoments) == 16, "PixelMoments is one 16-byte record per tid");
 // pixel index of a launch -> tid (Job::tidBegin / tidChunk / tidStride: every tidStride-th chunk of tidChunk tids, hpt_set_tid_interleave)
 HPT_HD uint tidOfIndex(uint tidBegin, uint tidChunk, uint tidStride, uint index)
 { return tidBegin + (index / tidChunk) * tidChunk * tidStride + (index % tidChunk); }

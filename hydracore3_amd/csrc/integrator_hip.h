@@ -201,6 +201,18 @@ public:
     report(rc, "DenoiseFrame");
     return rc == HPT_OK;
   }
+  // PathTraceBlockAdaptive (no counterpart in the reference; include/hydra_hip.h): PathTraceBlock with the passes placed where the
+  // pixels' luminance statistics ask for them. out_color receives the un-normalised sums; moments (winWidth * winHeight entries, or null) the per-pixel records, whose
+  // `passes` hpt_adaptive_resolve divides by. Returns false on an error.
+  bool PathTraceBlockAdaptive(uint32_t tid, uint32_t channels, float* out_color, const hpt_adaptive_params& params, uint32_t maxRounds,
+                              hpt_pixel_moments* moments, hpt_adaptive_info* info)
+  {
+    if (!m_ctx) return false;
+    hpt_adaptive_info local;
+    const int rc = hpt_path_trace_block_adaptive(m_ctx, 0, tid, channels, out_color, &params, maxRounds, moments, info ? info : &local);
+    report(rc, "PathTraceBlockAdaptive");
+    return rc == HPT_OK;
+  }
   // cam_plugin/CamPluginAPI.h:27-37: both structs are 16 bytes (origin + wavelength, direction + time), camera space
   struct RayPosAndW { float origin[3]; float wave; };
   struct RayDirAndT { float direction[3]; float time; };

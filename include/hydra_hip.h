@@ -238,6 +238,56 @@ int  hpt_path_trace_block_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount
 int  hpt_path_trace_from_input_rays_block(hpt_ctx* ctx, uint32_t tid, uint32_t channels, const float* rayPosAndW, const float* rayDirAndT, float* out_color, uint32_t passNum);
 int  hpt_path_trace_from_input_rays_block_dev(hpt_ctx* ctx, uint32_t tid, uint32_t channels, const float* rayPosAndWDev, const float* rayDirAndTDev, float* outDev, uint32_t passNum, void* stream);
 
+/* ---- adaptive sampling (no counterpart in the reference) ---------------------------------------------------------------- */
+/* One record per tid: the sums of the samples' luminance and of its square, in pass order, and the number of samples. The luminance of a sample
+ * is y = (0.2126f * r + 0.7152f * g) + 0.0722f * b in f32 over the three values the sample adds to the frame (the one value when channels == 1).
+ * Records accumulate across calls; a caller who wants fresh statistics zeroes the array. reserved is written as 0. */
+typedef struct hpt_pixel_moments { float sumY; float sumY2; uint32_t passes; uint32_t reserved; } hpt_pixel_moments;
+/* The planner's parameters. A pixel with n passes, mean m and variance v of its luminance asks for ceil(v / (tol * (|m| + lumFloor))^2) passes in
+ * all, at least minPasses; a call gives it at most `step` more and never more than maxPasses in all. dilate = 1: a pixel asks for what the
+ * neediest pixel of its 3 x 3 neighbourhood asks for (clipped to the frame; the neighbourhood stops at the edge of the tid window).
+ * HPT_ERR_ARG unless tol and lumFloor are finite and > 0, 1 <= minPasses <= maxPasses, 1 <= step and dilate is 0 or 1. */
+typedef struct hpt_adaptive_params { float tol; float lumFloor; uint32_t minPasses; uint32_t maxPasses; uint32_t step; uint32_t dilate; } hpt_adaptive_params;
+/* What the planner and the loop report (32 bytes). The planner: passes = the sum of the counts it wrote, pixels = counts above 0, maxPasses = the
+ * largest record's passes, nonfinite = records with passes whose sums are not finite (they are given no more), rounds = 0, deviceMs = 0.
+ * The loop: passes = passes spent, pixels = pixels still short at the end, maxPasses and nonfinite of the final records, rounds = render
+ * launches (the first included), deviceMs = the sum of their kernel times. */
+typedef struct hpt_adaptive_info { uint64_t passes; uint32_t pixels; uint32_t maxPasses; uint32_t nonfinite; uint32_t rounds; float deviceMs; uint32_t reserved; } hpt_adaptive_info;
+/* PathTraceBlock with a pass count per pixel. passCounts and moments are arrays of winWidth * winHeight entries indexed by absolute tid, like
+ * m_randomGens; the window [tidBegin, tidBegin + tidCount) of them is read (and, of moments, written). passCounts NULL: passNum passes for every
+ * pixel; otherwise passNum is not read. A pixel with count k ends, bit for bit, as a PathTraceBlock call with k passes leaves it (frame and
+ * generator); a pixel with count 0 is neither read nor written. moments NULL: no statistics. Always the persistent megakernel with whole pixels:
+ * hpt_set_schedule and the option "pass_slice" are ignored and hpt_get_last_launch reports schedule 1 (heavy scenes included).
+ * HPT_ERR_UNSUPPORTED with a message, nothing touched: m_spectral_mode, scenes with thin films, naive != 0, the instrumented probe.
+ * The device form is asynchronous on stream and honours hpt_set_tid_interleave (the arrays are indexed by the tids the items map to); the host
+ * form copies the frame and the contiguous window of both arrays in, and the frame and moments out, and refuses a stride above 1 with
+ * HPT_ERR_UNSUPPORTED. */
+int  hpt_path_trace_block_counts(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color, uint32_t passNum,
+                                 const uint32_t* passCounts, hpt_pixel_moments* moments);
+int  hpt_path_trace_block_counts_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color_dev, uint32_t passNum, int naive,
+                                     const uint32_t* passCountsDev, hpt_pixel_moments* momentsDev, void* stream);
+/* The planner: counts[tid] for the window from moments[tid] (both indexed by absolute tid), the totals in *info. Needs UpdateMembersPlainData and
+ * PackXYBlock. The device form is asynchronous on stream; infoDev is device memory and is overwritten. */
+int  hpt_adaptive_plan(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, const hpt_adaptive_params* params, const hpt_pixel_moments* moments,
+                       uint32_t* passCounts, hpt_adaptive_info* info);
+int  hpt_adaptive_plan_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, const hpt_adaptive_params* params, const hpt_pixel_moments* momentsDev,
+                           uint32_t* passCountsDev, hpt_adaptive_info* infoDev, void* stream);
+/* out[pixel * channels + c] = frame[pixel * channels + c] / float(passes of the pixel's record) for c < min(channels, 3) over the window; a pixel
+ * without passes is written as 0, a fourth channel is copied. Frames of winWidth * winHeight * channels floats (1, 3 or 4); out may be frame. */
+int  hpt_adaptive_resolve(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frame, const hpt_pixel_moments* moments, float* out);
+int  hpt_adaptive_resolve_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frameDev, const hpt_pixel_moments* momentsDev,
+                              float* outDev, void* stream);
+/* The loop, everything resident on the device: the window's records are zeroed, round 0 renders minPasses everywhere; then, up to maxRounds times:
+ * plan, read the totals back, stop when nothing is asked for, render with the counts. out_color receives the un-normalised sums, as from
+ * PathTraceBlock (hpt_adaptive_resolve divides them). moments may be NULL: the records then live in an array the context owns. Synchronous
+ * (the totals are read between rounds); stream carries the launches. Refusals as hpt_path_trace_block_counts and the planner's, and
+ * HPT_ERR_UNSUPPORTED under hpt_set_tid_interleave with a stride above 1 (the loop zeroes, plans and counts one contiguous window; a strided render
+ * visits tids outside it). Every refusal is made before anything is written: frame, generators and the caller's records keep their contents. */
+int  hpt_path_trace_block_adaptive(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color, const hpt_adaptive_params* params,
+                                   uint32_t maxRounds, hpt_pixel_moments* moments, hpt_adaptive_info* info);
+int  hpt_path_trace_block_adaptive_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out_color_dev, const hpt_adaptive_params* params,
+                                       uint32_t maxRounds, hpt_pixel_moments* momentsDev, hpt_adaptive_info* info, void* stream);
+
 /* ---- G-buffer (integrator_gbuffer.cpp) ------------------------------------------------------------------------------- */
 /* Integrator::GBufferPixel (integrator_pt.h:187-198): 15 dwords. A miss: depth 0, norm (0, 0, 1), ids -1, coverage 0. rgba[3] of a hit is
  * DEFINED as 1 (the reference reads color[3] of a float3 there, integrator_gbuffer.cpp:190: undefined); shadow is 0 (not implemented there). */
