@@ -102,6 +102,8 @@ ABI = {
     "hpt_eval_gbuffer_dev": (_i, [_vp, _u32, _vp, _vp, _vp]),
     "hpt_denoise_frame": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp]),
     "hpt_denoise_frame_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
+    "hpt_denoise_frame_var": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "hpt_denoise_frame_var_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "hpt_cast_single_ray_block": (_i, [_vp, _u32, _vp, _u32]),
     "hpt_cast_single_ray_block_dev": (_i, [_vp, _u32, _vp, _u32, _vp]),
     "hpt_ray_trace_block": (_i, [_vp, _u32, _u32, _vp, _u32]),
@@ -136,6 +138,8 @@ ABI = {
     "hpt_adaptive_plan_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp, _vp, _vp]),
     "hpt_adaptive_resolve": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp]),
     "hpt_adaptive_resolve_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _vp, _vp]),
+    "hpt_adaptive_variance": (_i, [_vp, _u32, _u32, _vp, _vp]),
+    "hpt_adaptive_variance_dev": (_i, [_vp, _u32, _u32, _vp, _vp, _vp]),
     "hpt_path_trace_block_adaptive": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp]),
     "hpt_path_trace_block_adaptive_dev": (_i, [_vp, _u32, _u32, _u32, _vp, _vp, _u32, _vp, _vp, _vp]),
 }
@@ -182,6 +186,15 @@ class DENOISE_PARAMS(C.Structure):
 DENOISE_DEMODULATE = 1
 # the defaults of HipIntegrator.denoise, as the header states them (chosen on the quality check of profiles/denoise.md)
 DENOISE_DEFAULTS = {"iterations": 5, "normal_squarings": 7, "sigma_color": 0.6, "sigma_depth": 0.05, "sigma_albedo": 0.1, "demodulate": True}
+
+
+class DENOISE_VAR_PARAMS(C.Structure):
+    """hpt_denoise_var_params (include/hydra_hip.h): 4 dwords."""
+    _fields_ = [("sigmaLum", _f), ("varFloor", _f), ("prefilter", _u32), ("reserved", _u32)]
+
+
+# the defaults of HipIntegrator.denoise_var (chosen on the quality check of profiles/denoise_var.md); the other parameters: DENOISE_DEFAULTS, sigma_color 0
+DENOISE_VAR_DEFAULTS = {"sigma_lum": 2.0, "var_floor": 1e-4, "prefilter": True}
 
 _LIB = None
 
@@ -412,6 +425,18 @@ class HipIntegrator:
 
     def AdaptiveResolve_dev(self, frame_ptr, moments_ptr, out_ptr, channels=4, tid=None, tid_begin=0, stream=None):
         self._chk(self.L.hpt_adaptive_resolve_dev(self.h, tid_begin, self.N - tid_begin if tid is None else tid, channels, frame_ptr, moments_ptr, out_ptr, stream))
+
+    def AdaptiveVariance(self, moments, tid=None, tid_begin=0, out=None):
+        """The variance plane denoise_var reads: float32 [winHeight, winWidth], the estimated variance of each window pixel's mean luminance
+        (DESIGN.md 2.12b). out None: a plane of zeros is written into; pixels outside the window keep their contents."""
+        assert moments.dtype == MOMENTS_DTYPE and moments.flags["C_CONTIGUOUS"] and moments.size == self.N
+        out = np.zeros((self.H, self.W), np.float32) if out is None else out
+        assert out.dtype == np.float32 and out.flags["C_CONTIGUOUS"] and out.size == self.N
+        self._chk(self.L.hpt_adaptive_variance(self.h, tid_begin, self.N - tid_begin if tid is None else tid, moments.ctypes.data, out.ctypes.data))
+        return out
+
+    def AdaptiveVariance_dev(self, moments_ptr, out_ptr, tid=None, tid_begin=0, stream=None):
+        self._chk(self.L.hpt_adaptive_variance_dev(self.h, tid_begin, self.N - tid_begin if tid is None else tid, moments_ptr, out_ptr, stream))
 
     def PathTraceBlockAdaptive(self, tid, channels, out_color, max_rounds, moments=None, tid_begin=0, params=None, **kw):
         """The adaptive loop: min_passes everywhere, then up to max_rounds rounds of plan + render. out_color is accumulated into (un-normalised);
@@ -685,6 +710,42 @@ class HipIntegrator:
         p = params if params is not None else self.denoise_params(**kw)
         self._chk(self.L.hpt_denoise_frame_dev(self.h, self.W if width is None else width, self.H if height is None else height,
                                                color_ptr, gbuffer_ptr, C.byref(p), out_ptr, stream))
+
+    @staticmethod
+    def denoise_var_params(sigma_lum=None, var_floor=None, prefilter=None):
+        """A DENOISE_VAR_PARAMS; None takes the default of DENOISE_VAR_DEFAULTS."""
+        d = DENOISE_VAR_DEFAULTS
+        pick = lambda v, k: d[k] if v is None else v
+        return DENOISE_VAR_PARAMS(float(pick(sigma_lum, "sigma_lum")), float(pick(var_floor, "var_floor")), 1 if pick(prefilter, "prefilter") else 0, 0)
+
+    def denoise_var(self, frame, variance, gbuffer=None, norm_const=1.0, iterations=None, normal_squarings=None, sigma_depth=None, sigma_albedo=None,
+                    demodulate=None, sigma_lum=None, var_floor=None, prefilter=True, return_variance=False):
+        """DenoiseFrameVar (DESIGN.md 2.12b): denoise() with a luminance stop scaled by `variance`, float32 [height, width] (AdaptiveVariance's plane;
+        scaled by norm_const ** 2 inside). Returns a new float32 [height, width, 4], with return_variance also the filtered variance [height, width]."""
+        frame = np.ascontiguousarray(frame, np.float32)
+        assert frame.ndim == 3 and frame.shape[2] == 4
+        variance = np.ascontiguousarray(variance, np.float32)
+        assert variance.shape == frame.shape[:2]
+        if gbuffer is None:
+            gbuffer = self.EvalGBuffer()
+        gbuffer = np.ascontiguousarray(gbuffer)
+        assert gbuffer.dtype == GBUFFER_DTYPE and gbuffer.shape == frame.shape[:2]
+        p = self.denoise_params(norm_const, iterations, normal_squarings, 0.0, sigma_depth, sigma_albedo, demodulate)
+        vp = self.denoise_var_params(sigma_lum, var_floor, prefilter)
+        out = np.zeros_like(frame)
+        out_var = np.zeros_like(variance) if return_variance else None
+        self._chk(self.L.hpt_denoise_frame_var(self.h, frame.shape[1], frame.shape[0], frame.ctypes.data, gbuffer.ctypes.data, variance.ctypes.data, C.byref(p), C.byref(vp),
+                                               out.ctypes.data, None if out_var is None else out_var.ctypes.data))
+        return (out, out_var) if return_variance else out
+
+    def denoise_var_dev(self, color_ptr, gbuffer_ptr, variance_ptr, out_ptr, out_var_ptr=None, width=None, height=None, params=None, var_params=None, stream=None,
+                        sigma_lum=None, var_floor=None, prefilter=None, **kw):
+        """DenoiseFrameVar on device pointers; asynchronous on `stream`. params / var_params: the two records, or the keyword arguments of
+        denoise_params (sigma_color is 0 here) and of denoise_var_params."""
+        p = params if params is not None else self.denoise_params(**dict(kw, sigma_color=0.0))
+        vp = var_params if var_params is not None else self.denoise_var_params(sigma_lum, var_floor, prefilter)
+        self._chk(self.L.hpt_denoise_frame_var_dev(self.h, self.W if width is None else width, self.H if height is None else height,
+                                                   color_ptr, gbuffer_ptr, variance_ptr, C.byref(p), C.byref(vp), out_ptr, out_var_ptr, stream))
 
     def GetExecutionTime(self, name):
         out = (C.c_float * 4)(0, 0, 0, 0)

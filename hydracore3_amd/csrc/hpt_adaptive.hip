@@ -101,4 +101,29 @@ __global__ void __launch_bounds__(256) adaptiveResolveKernel(const float* frame,
   if (channels > 3u) out[at + 3] = frame[at + 3];
 }
 
+// The variance plane DenoiseFrameVar reads: the estimated variance of the pixel's mean luminance, var / (n - 1) with the planner's
+// var. One sample gives no spread and counts as 100 % relative error; a record without passes or with non-finite sums gives 0 (the colour of
+// such a pixel is non-finite too and the filter rebuilds it from its neighbours).
+__global__ void __launch_bounds__(256) adaptiveVarianceKernel(const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth, float* outVar)
+{
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  if (i >= tidCount) return;
+  const uint tid = tidBegin + i;
+  const PixelMoments m = moments[tid];
+  const uint n = m.passes;
+  float v = 0.0f;
+  if (n != 0u && __builtin_isfinite(m.sumY) && __builtin_isfinite(m.sumY2)) {
+    if (n == 1u) v = m.sumY * m.sumY;
+    else {
+      const float fn = (float)n;
+      const float mean = m.sumY / fn;
+      const float d = m.sumY2 / fn - mean * mean;
+      const float var = d > 0.0f ? d : 0.0f;
+      v = var / (fn - 1.0f);
+    }
+  }
+  const uint XY = packedXY[tid];
+  outVar[(size_t)((XY & 0xFFFF0000u) >> 16) * winWidth + (XY & 0x0000FFFFu)] = v;
+}
+
 } // namespace hpt

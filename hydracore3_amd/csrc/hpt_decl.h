@@ -244,6 +244,23 @@ __global__ void __launch_bounds__(256) denoisePackKernel(const DenoiseJob job); 
 #define HPT_DENOISE_LDS 1
 #endif
 template <bool LAST, int TILE = 0> __global__ void __launch_bounds__(256) denoisePassKernel(const DenoiseJob job);
+// ---- DenoiseFrameVar (hpt_denoise.hip): the same filter with a variance-scaled luminance stop and a fourth plane V ---------------
+// A job of its own and kernels of their own: DenoiseJob and the instantiations of DenoiseFrame stay as they are. d.sigmaColor2 and bit 1 of d.terms
+// are not used. V: one float per pixel, the variance of the (prepared) pixel, two buffers that ping-pong with the colours.
+struct DenoiseVarJob
+{
+  DenoiseJob d;
+  const float* variance;          // the caller's plane (pack kernel)
+  float* vin; float* vout;
+  float* outVar;                  // the caller's filtered variance (last pass) or null
+  float sigmaLum2;                // sigmaLum * sigmaLum
+  float varFloor;
+  uint  prefilter;                // not 0: the stop reads the 3 x 3 binomial mean of V at unit spacing
+  uint  useLum;                   // sigmaLum is not 0
+};
+__global__ void __launch_bounds__(256) denoiseVarPackKernel(const DenoiseVarJob job);            // one lane per pixel, blocks of 256
+// mapping and tiles as denoisePassKernel; the tile gains TW * TH floats of V (22 464 / 33 280 B at TILE 1 / 2)
+template <bool LAST, int TILE = 0> __global__ void __launch_bounds__(256) denoiseVarPassKernel(const DenoiseVarJob job);
 // ---- CastSingleRayBlock / RayTraceBlock (hpt_raytrace.hip) -----------------------------------------------------------------------------
 // one lane per pixel of packedXY[0 .. tidCount); outColor: winWidth * winHeight pixels of 4 floats (assigned) / of `channels` = 3 or 4 floats (added to)
 template <bool FLAT, bool MOTION, bool SWEEP>
@@ -409,6 +426,8 @@ __global__ void __launch_bounds__(256) adaptivePlanKernel(const PixelMoments* mo
 // ... out[pixel] = frame[pixel] / passes for the first three channels (0 for a pixel without passes), the fourth copied; out may be frame
 __global__ void __launch_bounds__(256) adaptiveResolveKernel(const float* frame, const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth,
                                                              uint channels, float* out);
+// one lane per tid of the window: outVar[y * winWidth + x] = the estimated variance of the pixel's mean luminance; other pixels are not written
+__global__ void __launch_bounds__(256) adaptiveVarianceKernel(const PixelMoments* moments, const uint* packedXY, uint tidBegin, uint tidCount, uint winWidth, float* outVar);
 
 // ---- helper kernels (hpt_helpers.hip) ---------------------------------------------------------------------------------------------------
 __global__ void packXYKernel(uint* out, int W, int H, uint ts);

@@ -114,7 +114,7 @@ double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::
 } } // namespace hpt::host
 using namespace hpt::host;
 
-enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_KMLT, T_DENOISE, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
+enum TimeSlot { T_PATH_TRACE, T_NAIVE, T_DR, T_FROM_RAYS, T_CAST_SINGLE_RAY, T_RAY_TRACE, T_PATH_TRACE_QMC, T_RAY_TRACE_DR, T_VJP, T_KMLT, T_DENOISE, T_DENOISE_VAR, T_SLOT_COUNT };   // (hpt_get_execution_time maps the reference's names to them)
 
 struct hpt_ctx
 {
@@ -195,6 +195,7 @@ struct hpt_ctx
   uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
   DevBuf<float> dFrame, dRecord, dRef, dData, dGrad, dLoss; DevBuf<double> dLossAcc;
   DevBuf<float4> dDenoiseN, dDenoiseA, dDenoiseC[2];     // DenoiseFrame (hpt_denoise.hip): the guide planes and the two ping-pong colour planes; grown on demand
+  DevBuf<float>  dDenoiseV[2];                           // DenoiseFrameVar: the two ping-pong variance planes (it shares the four above with DenoiseFrame)
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   // wavefront schedule (hpt_wavefront.hip): the pixels of a call are cut into groups, each with its own path pool, ray queue and
   // stream, so that the tail of one group's trace pass overlaps the other groups' work
@@ -2654,6 +2655,39 @@ try {
 }
 catch (...) { return hptGuard(c, "hpt_adaptive_resolve"); }
 
+// The variance plane of DenoiseFrameVar from the records: one float per pixel of the window, in pixel order
+static int adaptiveVarianceCheck(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const void* moments, const void* outVar)
+{
+  if (!moments) return c->fail(HPT_ERR_ARG, "AdaptiveVariance: moments is null");
+  if (!outVar) return c->fail(HPT_ERR_ARG, "AdaptiveVariance: outVar is null");
+  return adaptiveWindowCheck(c, "AdaptiveVariance", tidBegin, tidCount);
+}
+extern "C" int hpt_adaptive_variance_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const hpt_pixel_moments* momentsDev, float* outVarDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveVarianceCheck(c, tidBegin, tidCount, momentsDev, outVarDev)) return rc;
+  if (tidCount == 0) return HPT_OK;
+  adaptiveVarianceKernel<<<dim3((tidCount + 255u) / 256u), dim3(256), 0, (hipStream_t)stream>>>((const PixelMoments*)momentsDev, c->dPackedXY.p, tidBegin, tidCount,
+                                                                                                 (uint)c->S.winWidth, outVarDev);
+  HIPCHK(c, hipGetLastError());
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_variance_dev"); }
+extern "C" int hpt_adaptive_variance(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, const hpt_pixel_moments* moments, float* outVar)
+try {
+  if (!c) return HPT_ERR_ARG;
+  (void)hipSetDevice(c->device);
+  if (int rc = adaptiveVarianceCheck(c, tidBegin, tidCount, moments, outVar)) return rc;
+  const size_t n = (size_t)c->packedCount;
+  DevBuf<float> dOut;                                            // (the caller's plane goes up first: pixels outside the window keep their contents)
+  return roundTrip(c, nullptr, KERNEL_UNTIMED,
+                   [&]() -> int { HIPCHK(c, dOut.upload(outVar, n)); return adaptiveUploadWindow(c, tidBegin, tidCount, nullptr, moments); },
+                   [&]() -> int { return hpt_adaptive_variance_dev(c, tidBegin, tidCount, (const hpt_pixel_moments*)c->dAdMomentsIn.p, dOut.p, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(outVar, dOut.p, n * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+catch (...) { return hptGuard(c, "hpt_adaptive_variance"); }
+
 extern "C" int hpt_path_trace_block_adaptive(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* out, const hpt_adaptive_params* params,
                                              uint32_t maxRounds, hpt_pixel_moments* moments, hpt_adaptive_info* info)
 try {
@@ -2723,9 +2757,10 @@ catch (...) { return hptGuard(c, "hpt_eval_gbuffer"); }
 // ---- DenoiseFrame (no counterpart in the reference; DESIGN.md 2.12, hpt_denoise.hip) -------------------------------------------------------------
 static_assert(sizeof(hpt_denoise_params) == 28, "hpt_denoise_params is 7 dwords");
 // The refusals both forms share; each names its argument. `a`, `b`: the two frames of n pixels that must not overlap.
-static int denoiseCheck(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer, const hpt_denoise_params* p, const float* out)
+static int denoiseCheck(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer, const hpt_denoise_params* p, const float* out,
+                        const char* what = "DenoiseFrame")
 {
-  const std::string w("DenoiseFrame: ");
+  const std::string w = std::string(what) + ": ";
   if (!color) return c->fail(HPT_ERR_ARG, w + "color is null");
   if (!gbuffer) return c->fail(HPT_ERR_ARG, w + "gbuffer is null");
   if (!p) return c->fail(HPT_ERR_ARG, w + "params is null");
@@ -2800,6 +2835,92 @@ try {
                    [&]() -> int { HIPCHK(c, hipMemcpy(out, dOut.p, n * 4 * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
 }
 catch (...) { return hptGuard(c, "hpt_denoise_frame"); }
+
+// ---- DenoiseFrameVar: the variance-guided form; it shares the scratch planes N, A, C with DenoiseFrame and adds V ---------------------
+static_assert(sizeof(hpt_denoise_var_params) == 16, "hpt_denoise_var_params is 4 dwords");
+static bool overlaps(const void* a, size_t na, const void* b, size_t nb) { const char* x = (const char*)a; const char* y = (const char*)b; return x < y + nb && y < x + na; }
+static int denoiseVarCheck(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer, const float* variance,
+                           const hpt_denoise_params* p, const hpt_denoise_var_params* vp, const float* out, const float* outVar)
+{
+  if (int rc = denoiseCheck(c, width, height, color, gbuffer, p, out, "DenoiseFrameVar")) return rc;
+  const std::string w("DenoiseFrameVar: ");
+  if (!variance) return c->fail(HPT_ERR_ARG, w + "variance is null");
+  if (!vp) return c->fail(HPT_ERR_ARG, w + "var_params is null");
+  if (!(vp->sigmaLum >= 0.0f) || !(vp->sigmaLum <= 3.402823466e38f)) return c->fail(HPT_ERR_ARG, w + "sigmaLum must be finite and not negative");
+  if (!(vp->varFloor > 0.0f) || !(vp->varFloor <= 3.402823466e38f)) return c->fail(HPT_ERR_ARG, w + "varFloor must be finite and above 0 (it keeps the stop's denominator away from 0)");
+  if (vp->reserved != 0u) return c->fail(HPT_ERR_ARG, w + "reserved must be 0");
+  if (p->sigmaColor != 0.0f) return c->fail(HPT_ERR_ARG, w + "sigmaColor must be 0 (the luminance stop of sigmaLum stands in its place)");
+  const size_t n = (size_t)width * height;
+  if (overlaps(out, n * 16, variance, n * 4)) return c->fail(HPT_ERR_ARG, w + "out aliases variance");
+  if (outVar) {
+    if (overlaps(outVar, n * 4, color, n * 16)) return c->fail(HPT_ERR_ARG, w + "outVar aliases color");
+    if (overlaps(outVar, n * 4, gbuffer, n * sizeof(hpt_gbuffer_pixel))) return c->fail(HPT_ERR_ARG, w + "outVar aliases gbuffer");
+    if (overlaps(outVar, n * 4, variance, n * 4)) return c->fail(HPT_ERR_ARG, w + "outVar aliases variance");
+    if (overlaps(outVar, n * 4, out, n * 16)) return c->fail(HPT_ERR_ARG, w + "outVar aliases out");
+  }
+  return HPT_OK;
+}
+template <bool LAST> static void denoiseVarPass(const DenoiseVarJob& job, dim3 grid, hipStream_t st)
+{
+  if (job.d.step == 1u) denoiseVarPassKernel<LAST, 1><<<grid, dim3(256), 0, st>>>(job);          // steps 1 and 2 read their taps from an LDS tile
+  else if (job.d.step == 2u) denoiseVarPassKernel<LAST, 2><<<grid, dim3(256), 0, st>>>(job);
+  else denoiseVarPassKernel<LAST, 0><<<grid, dim3(256), 0, st>>>(job);
+}
+// Device-pointer form: pack, then `iterations` passes between the ping-pong planes of colour and variance; one event pair around them. Asynchronous on stream.
+extern "C" int hpt_denoise_frame_var_dev(hpt_ctx* c, uint32_t width, uint32_t height, const float* colorDev, const hpt_gbuffer_pixel* gbufferDev, const float* varianceDev,
+                                         const hpt_denoise_params* p, const hpt_denoise_var_params* vp, float* outDev, float* outVarDev, void* stream)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = denoiseVarCheck(c, width, height, colorDev, gbufferDev, varianceDev, p, vp, outDev, outVarDev)) return rc;
+  (void)hipSetDevice(c->device);
+  hipStream_t st = (hipStream_t)stream;
+  const size_t n = (size_t)width * height;
+  HIPCHK(c, c->dDenoiseN.alloc(n)); HIPCHK(c, c->dDenoiseA.alloc(n)); HIPCHK(c, c->dDenoiseC[0].alloc(n)); HIPCHK(c, c->dDenoiseV[0].alloc(n));
+  if (p->iterations > 1u) { HIPCHK(c, c->dDenoiseC[1].alloc(n)); HIPCHK(c, c->dDenoiseV[1].alloc(n)); }
+  DenoiseVarJob job; std::memset(&job, 0, sizeof(job));
+  job.d.color = (const float4*)colorDev; job.d.gbuffer = (const GBufferPixel*)gbufferDev;
+  job.d.planeN = c->dDenoiseN.p; job.d.planeA = c->dDenoiseA.p;
+  job.d.pixels = n; job.d.width = width; job.d.height = height;
+  job.d.normalSquarings = p->normalSquarings; job.d.flags = p->flags; job.d.normConst = p->normConst;
+  job.d.terms = (p->sigmaDepth != 0.0f ? 1u : 0u) | (p->sigmaAlbedo != 0.0f ? 4u : 0u);
+  job.d.sigmaAlbedo2 = p->sigmaAlbedo * p->sigmaAlbedo;
+  job.variance = varianceDev; job.outVar = outVarDev;
+  job.sigmaLum2 = vp->sigmaLum * vp->sigmaLum; job.varFloor = vp->varFloor; job.prefilter = vp->prefilter; job.useLum = vp->sigmaLum != 0.0f ? 1u : 0u;
+  HIPCHK(c, hipEventRecord(c->ev0, st));
+  job.d.cin = c->dDenoiseC[0].p; job.vin = c->dDenoiseV[0].p;
+  denoiseVarPackKernel<<<dim3((uint)((n + 255u) / 256u)), dim3(256), 0, st>>>(job);
+  const dim3 grid((width + 31u) / 32u, (height + 7u) / 8u);
+  for (uint32_t i = 0; i < p->iterations; i++) {
+    const bool last = i + 1u == p->iterations;
+    job.d.step = 1u << i;
+    job.d.sigmaDepthStep = p->sigmaDepth * float(job.d.step);
+    job.d.cin = c->dDenoiseC[i & 1u].p; job.vin = c->dDenoiseV[i & 1u].p;
+    job.d.cout = last ? (float4*)outDev : c->dDenoiseC[(i & 1u) ^ 1u].p;
+    job.vout = last ? nullptr : c->dDenoiseV[(i & 1u) ^ 1u].p;
+    if (last) denoiseVarPass<true>(job, grid, st); else denoiseVarPass<false>(job, grid, st);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipEventRecord(c->ev1, st));
+  return HPT_OK;
+}
+catch (...) { return hptGuard(c, "hpt_denoise_frame_var_dev"); }
+// Host-pointer form: the frame, the records and the variances go up, the filtered frame (and variance) come back
+extern "C" int hpt_denoise_frame_var(hpt_ctx* c, uint32_t width, uint32_t height, const float* color, const hpt_gbuffer_pixel* gbuffer, const float* variance,
+                                     const hpt_denoise_params* p, const hpt_denoise_var_params* vp, float* out, float* outVar)
+try {
+  if (!c) return HPT_ERR_ARG;
+  if (int rc = denoiseVarCheck(c, width, height, color, gbuffer, variance, p, vp, out, outVar)) return rc;
+  (void)hipSetDevice(c->device);
+  const size_t n = (size_t)width * height;
+  DevBuf<float> dColor, dVar, dOut, dOutVar; DevBuf<hpt_gbuffer_pixel> dGb;
+  return roundTrip(c, c->tSlots[T_DENOISE_VAR], KERNEL_EVENTS,
+                   [&]() -> int { HIPCHK(c, dColor.upload(color, n * 4)); HIPCHK(c, dGb.upload(gbuffer, n)); HIPCHK(c, dVar.upload(variance, n)); HIPCHK(c, dOut.alloc(n * 4));
+                                  if (outVar) HIPCHK(c, dOutVar.alloc(n)); return HPT_OK; },
+                   [&]() -> int { return hpt_denoise_frame_var_dev(c, width, height, dColor.p, dGb.p, dVar.p, p, vp, dOut.p, outVar ? dOutVar.p : nullptr, nullptr); },
+                   [&]() -> int { HIPCHK(c, hipMemcpy(out, dOut.p, n * 4 * sizeof(float), hipMemcpyDeviceToHost));
+                                  if (outVar) HIPCHK(c, hipMemcpy(outVar, dOutVar.p, n * sizeof(float), hipMemcpyDeviceToHost)); return HPT_OK; });
+}
+catch (...) { return hptGuard(c, "hpt_denoise_frame_var"); }
 
 // ---- CastSingleRayBlock / RayTraceBlock (integrator_pt.h:254, 263; integrator_rt.cpp:420-461; integrator_pt_host.cpp:29-36, 75-90) ----------------
 // channels of RayTraceBlock: 1 and 2 are refused (the reference writes three floats at that stride: over the next pixel and, for the last
@@ -3889,6 +4010,7 @@ static const struct { const char* name; const char* alias; TimeSlot slot; } TIME
   { "PathTraceVJP", nullptr, T_VJP },                                     // no counterpart: PathTraceDR's slots for the VJP form
   { "RayTraceDR", nullptr, T_RAY_TRACE_DR },                              // shadowPtTime (integrator_dr.cpp:441)
   { "DenoiseFrame", nullptr, T_DENOISE },                                 // no counterpart
+  { "DenoiseFrameVar", nullptr, T_DENOISE_VAR },
 };
 extern "C" int hpt_get_execution_time(hpt_ctx* c, const char* name, float out[4])
 try {

@@ -201,6 +201,24 @@ public:
     report(rc, "DenoiseFrame");
     return rc == HPT_OK;
   }
+  // DenoiseFrameVar (include/hydra_hip.h): DenoiseFrame with a luminance stop scaled by `variance` (width * height floats, e.g. from
+  // AdaptiveVariance) in place of the colour stop; params.sigmaColor must be 0. outVar: null, or width * height floats for the filtered variance.
+  bool DenoiseFrameVar(uint32_t width, uint32_t height, const float* color4f, const GBufferPixel* gbuffer, const float* variance, const hpt_denoise_params& params,
+                       const hpt_denoise_var_params& varParams, float* out4f, float* outVar = nullptr)
+  {
+    if (!m_ctx) return false;
+    const int rc = hpt_denoise_frame_var(m_ctx, width, height, color4f, reinterpret_cast<const hpt_gbuffer_pixel*>(gbuffer), variance, &params, &varParams, out4f, outVar);
+    report(rc, "DenoiseFrameVar");
+    return rc == HPT_OK;
+  }
+  // AdaptiveVariance: the variance plane DenoiseFrameVar reads, from the records of PathTraceBlockAdaptive, for the first tid pixels of m_packedXY
+  bool AdaptiveVariance(uint32_t tid, const hpt_pixel_moments* moments, float* outVar)
+  {
+    if (!m_ctx) return false;
+    const int rc = hpt_adaptive_variance(m_ctx, 0, tid, moments, outVar);
+    report(rc, "AdaptiveVariance");
+    return rc == HPT_OK;
+  }
   // PathTraceBlockAdaptive (no counterpart in the reference; include/hydra_hip.h): PathTraceBlock with the passes placed where the
   // pixels' luminance statistics ask for them. out_color receives the un-normalised sums; moments (winWidth * winHeight entries, or null) the per-pixel records, whose
   // `passes` hpt_adaptive_resolve divides by. Returns false on an error.

@@ -277,6 +277,13 @@ int  hpt_adaptive_plan_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, c
 int  hpt_adaptive_resolve(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frame, const hpt_pixel_moments* moments, float* out);
 int  hpt_adaptive_resolve_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, const float* frameDev, const hpt_pixel_moments* momentsDev,
                               float* outDev, void* stream);
+/* The variance plane hpt_denoise_frame_var reads: outVar[y * winWidth + x] of every pixel of the window = the estimated variance of the pixel's
+ * mean luminance, from its record {sumY, sumY2, n}: 0 without passes or with a sum that is not finite (such a pixel's colour is not finite
+ * either and the filter rebuilds it); sumY * sumY for n = 1 (one sample shows no spread: 100 % relative error); otherwise
+ * max(sumY2 / n - mean * mean, 0) / (n - 1) with mean = sumY / n, in f32 in this order. outVar: winWidth * winHeight floats; pixels outside the
+ * window are not written. Needs PackXYBlock; HPT_ERR_ARG with a message for a null pointer or a window past the packed range, nothing written. */
+int  hpt_adaptive_variance(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, const hpt_pixel_moments* moments, float* outVar);
+int  hpt_adaptive_variance_dev(hpt_ctx* ctx, uint32_t tidBegin, uint32_t tidCount, const hpt_pixel_moments* momentsDev, float* outVarDev, void* stream);
 /* The loop, everything resident on the device: the window's records are zeroed, round 0 renders minPasses everywhere; then, up to maxRounds times:
  * plan, read the totals back, stop when nothing is asked for, render with the counts. out_color receives the un-normalised sums, as from
  * PathTraceBlock (hpt_adaptive_resolve divides them). moments may be NULL: the records then live in an array the context owns. Synchronous
@@ -327,6 +334,32 @@ int  hpt_denoise_frame(hpt_ctx* ctx, uint32_t width, uint32_t height, const floa
  * time of the pack kernel and the passes together. */
 int  hpt_denoise_frame_dev(hpt_ctx* ctx, uint32_t width, uint32_t height, const float* color4fDev, const hpt_gbuffer_pixel* gbufferDev,
                            const hpt_denoise_params* params, float* out4fDev, void* stream);
+
+/* DenoiseFrameVar: DenoiseFrame with the fixed colour stop replaced by a luminance stop scaled by each pixel's own estimated variance (SVGF,
+ * Schied et al. 2017), fed by the records of adaptive sampling. DESIGN.md 2.12b defines it operation by operation and
+ * tests/denoise_var_reference.py restates it in numpy float32, bit for bit. Everything of DenoiseFrame holds (taps, id and non-finite stops,
+ * normal, depth and albedo terms, demodulation, alpha) except that params->sigmaColor must be 0; in its place
+ *   x_l = (Y(c_p) - Y(c_q))^2 / (sigmaLum^2 * vbar_p + varFloor),  Y = (0.2126 r + 0.7152 g) + 0.0722 b,
+ * where vbar_p is the pixel's variance (prefilter != 0: its 3 x 3 binomial mean at unit spacing). The variance plane is scaled like the colours
+ * (normConst^2; under demodulation divided by the square of the floored albedo's luminance), travels through the passes as
+ * sum(w^2 v_q) / (sum w)^2 and comes back in outVar.
+ *   sigmaLum   width of the luminance stop in standard deviations; 0 switches the term off
+ *   varFloor   added to the stop's denominator, above 0: what keeps it away from 0 where the variance is 0
+ *   prefilter  0 or not 0;  reserved  0
+ * The C interface has no defaults; the Python front end's were chosen on the 4-spp Cornell box (profiles/denoise_var.md). */
+typedef struct hpt_denoise_var_params { float sigmaLum; float varFloor; uint32_t prefilter; uint32_t reserved; } hpt_denoise_var_params;
+/* variance: width * height floats in pixel order (hpt_adaptive_variance's for a full window); an entry that is not finite or not above 0
+ * counts as 0. outVar: NULL, or width * height floats that receive the filtered variance. The other arguments as hpt_denoise_frame. Host
+ * pointers; needs a created context only. HPT_ERR_ARG with a message that names DenoiseFrameVar and the argument, nothing written: every refusal of
+ * hpt_denoise_frame; a null variance or var_params; sigmaLum negative or not finite; varFloor not finite or not above 0; reserved not 0;
+ * sigmaColor not 0; out4f overlapping color4f or variance; outVar overlapping color4f, gbuffer, variance or out4f.
+ * hpt_get_execution_time("DenoiseFrameVar") gives its four slots. It shares DenoiseFrame's scratch planes and adds two of one float per pixel. */
+int  hpt_denoise_frame_var(hpt_ctx* ctx, uint32_t width, uint32_t height, const float* color4f, const hpt_gbuffer_pixel* gbuffer, const float* variance,
+                           const hpt_denoise_params* params, const hpt_denoise_var_params* var_params, float* out4f, float* outVar);
+/* The same with the arrays resident in device memory (both parameter records stay host pointers); asynchronous on stream.
+ * hpt_last_kernel_ms gives the time of the pack kernel and the passes together. */
+int  hpt_denoise_frame_var_dev(hpt_ctx* ctx, uint32_t width, uint32_t height, const float* color4fDev, const hpt_gbuffer_pixel* gbufferDev, const float* varianceDev,
+                               const hpt_denoise_params* params, const hpt_denoise_var_params* var_params, float* out4fDev, float* outVarDev, void* stream);
 
 /* ---- primary-ray preview and Whitted ray tracing (integrator_rt.cpp) ------------------------------------------------- */
 /* Integrator::CastSingleRayBlock(tid, out_color, a_passNum) (integrator_pt.h:254, integrator_pt_host.cpp:29-36, integrator_rt.cpp:33-53,
