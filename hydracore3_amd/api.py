@@ -912,6 +912,9 @@ class HipIntegrator:
         self._chk(self.L.hpt_image2d4f_regularizer(self.h, data.shape[1], data.shape[0], data.ctypes.data, grad.ctypes.data))
 
     def set_option(self, name: str, value: int):
+        """hpt_set_option (include/hydra_hip.h lists the names). Among them "adaptive_wavefront": 0 (default) the adaptive calls - PathTraceBlockCounts
+        and every round of PathTraceBlockAdaptive - run the megakernel; 1 each goes to the wavefront schedule where a PathTraceBlock of as many pixels
+        as it has counts above 0 would (set_schedule). Frames, generators and moments are the same bit for bit; a count above 0xFFFFFF is refused there."""
         self._chk(self.L.hpt_set_option(self.h, name.encode(), value))
         if name == "qmc_spectral":
             self._qmc_spectral = bool(value)     # PathTraceBlockQMC then takes frames of more than 4 channels

@@ -156,12 +156,16 @@ struct WfJob
   float* outColor;
   Rng*   gens;
   const uint* packedXY;
-  // differentiable rendering (wfShadeKernel<DR = true>): a_refImg, a_data, a_dataGrad, loss accumulator, adjoint records [bounce][field][slot]
-  const float* refImg; const float* data; float* grad; float* lossAccum; float* record;
+  // differentiable rendering (wfShadeKernel<DR = true>): a_refImg, a_data, a_dataGrad, loss accumulator, adjoint records [bounce][field][slot];
+  // the adaptive forward call (wfShadeKernel<.., ADAPT>, wfInitCountsKernel; no DR call runs them) keeps its two arrays in the storage of two of
+  // these pointers, as Job does: passCounts (null: passNum for every pixel) and moments (null: no statistics), both indexed by absolute tid
+  union { const float* refImg; const uint* passCounts; }; const float* data; union { float* grad; PixelMoments* moments; }; float* lossAccum; float* record;
   const float* adjImg; uint vjp;  // PathTraceVJP: as in Job
   union { uint drLightFirst; uint drEnvPlaneOn; };   // (wfShadeKernel<.., ENV>, where no light is registered: the env plane of the record exists)
   uint drLightCount, drLightOff;                 // light-colour gradients (wfShadeKernel<.., LGRAD>): DrLights; count 0 otherwise
 };
+static_assert(sizeof(WfJob) == 128, "WfJob is a by-value argument of every shade kernel: its size and layout stay");
+static const uint WF_MAX_PASSES = 0xFFFFFFu;         // passes of a pixel per call: what bits 8..31 of the status word hold
 
 #ifndef HPT_WF_SHADE_FULL_WAVES
 #define HPT_WF_SHADE_FULL_WAVES 3      // the shade kernel with every BSDF branch: 1 M-triangle interior forced onto it 209 (4 waves) -> 214 Mpaths/s (profiles/ab_wfs.sh)
@@ -201,6 +205,15 @@ HPT_DEV void blockAppend(uint* counter, bool qNear, bool qShad, uint& posNear, u
 }
 
 __global__ void wfInitKernel(WfPool P, uint n, uint passNum);
+// Adaptive sampling under the wavefront schedule ("Wavefront form").
+// wfInitCountsKernel: wfInitKernel with the slot's own pass count - slot s of job.itemCount serves the tid the shade kernel maps it to and starts
+// with job.passCounts[tid] passes (null: job.passNum); a slot whose tid lies past job.tidEnd gets none.
+__global__ void __launch_bounds__(256) wfInitCountsKernel(WfPool P, const WfJob job);
+// WfCountsSummary: what the host has to know of the counts before it writes anything - the largest, how many are above 0 (the call's active
+// pixels) and how many exceed WF_MAX_PASSES. wfCountsSummaryKernel: one lane per work item of the call (job.itemBase .. + job.itemCount, item -> tid
+// as in the shade kernel); wave shuffles, then one integer atomic per block and field into *out (zeroed before).
+struct WfCountsSummary { uint maxCount, active, over; };
+__global__ void __launch_bounds__(256) wfCountsSummaryKernel(const WfJob job, WfCountsSummary* out);
 #ifndef HPT_STREAM_WAVES
 #define HPT_STREAM_WAVES 5
 #endif
@@ -209,7 +222,9 @@ __global__ void __launch_bounds__(256, HPT_STREAM_WAVES) streamKernel(const DevS
                                                                       uint* stackOverflow, uint gridLanes);
 template <int SCOPE>                                                    // spectral rendering under the wavefront schedule (hpt_spectral.hip)
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) wfShadeSpecKernel(const DevScene S, const WfPool P, const WfJob job);
-template <bool DR, bool LEAN, bool MOTION = false, bool FILM = false, bool LGRAD = false, bool ENV = false>   // FILM: shadeVertex<FILM> (thin films, hpt_film.h); LGRAD (with DR): light-colour gradients; ENV (with DR): environment maps
+// FILM: shadeVertex<FILM> (thin films, hpt_film.h); LGRAD (with DR): light-colour gradients; ENV (with DR): environment maps;
+// ADAPT (forward, without FILM): the luminance moments of WfJob::moments at kernel_ContributeToImage (the per-pixel pass counts are the slots' initial status)
+template <bool DR, bool LEAN, bool MOTION = false, bool FILM = false, bool LGRAD = false, bool ENV = false, bool ADAPT = false>
 __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const WfPool P, const WfJob job);
 template <bool DEEP, bool FLAT, bool STATS, bool MOTION = false, bool WIDE = false>   // WIDE: walk DevScene::nodes4 (4-wide compressed nodes) instead of the BVH2
 __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScene S, const WfPool P, uint iter, uint refillBelow, uint grace,

@@ -1075,6 +1075,16 @@ HPT_DEV V3 environmentRadiance(const DevScene& S, V3 rdir, float misPdf, uint fl
   return color;
 }
 
+// Adaptive sampling (the ADAPT instantiations of both schedules): the luminance of the sample kernel_ContributeToImage has just
+// added to the frame, from the very values added (c = accum * camRespoceRGB; Rec. 709 weights; the one value of a one-channel frame), in f32 and
+// in this order. A non-finite sample gives a non-finite luminance, which the record adds as it is, as the frame does.
+HPT_DEV float adaptSampleLuminance(const DevScene& S, uint channels, V3 accum, V3 c)
+{
+  if (channels == 1) return accum.x * S.exposureMult;
+  const float r = S.exposureMult * c.x, g = S.exposureMult * c.y, b = S.exposureMult * c.z;
+  return (0.2126f * r + 0.7152f * g) + 0.0722f * b;
+}
+
 // RemapMaterialId (integrator_pt_mat.cpp:530-573)
 HPT_DEV uint remapMaterialId(const DevScene& S, uint a_mId, uint a_instId)
 {

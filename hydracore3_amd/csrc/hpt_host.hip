@@ -186,6 +186,8 @@ struct hpt_ctx
   // adaptive sampling (hpt_adaptive.hip): the loop's pass counts [tid], the planner's need image [pixel] and totals, the records of a
   // loop whose caller keeps none, the host forms' copies of the caller's arrays; all grown on first use, none allocated per round
   DevBuf<uint> dAdCounts, dAdNeed, dAdCountsIn; DevBuf<AdaptiveInfo> dAdInfo; DevBuf<PixelMoments> dAdMoments, dAdMomentsIn;
+  bool adaptiveWavefront = false;                        // hpt_set_option("adaptive_wavefront", 1): an adaptive call takes the wavefront schedule where a PathTraceBlock of its active pixels would
+  DevBuf<WfCountsSummary> dAdSummary;                    // ... and the 12 bytes of its counts summary (wfCountsSummaryKernel)
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
@@ -1939,8 +1941,11 @@ static bool drEnvReads(const hpt_ctx* c, uint texId)
   for (const uint t : c->hLightTex) if (t == texId) return true;
   return false;
 }
-static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
+// adaptMax: null, or the adaptive call's largest pass count (1 .. WF_MAX_PASSES, from the counts summary or the loop's bound): Job::passCounts /
+// moments are set, the slots start with their own counts (wfInitCountsKernel) and the ADAPT shade kernels run
+static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1, const uint* adaptMax = nullptr)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
 {
+  const bool adapt = adaptMax != nullptr;                       // (forward RGB from the camera without thin films: adaptiveRefusal)
   const bool spec = specScope >= 0;
   const bool drEnv = dr && drEnvironmentCall(c);               // (launch_path_trace has made the refusals)
   const bool envPlane = drEnv && drEnvMapRegistered(c);
@@ -1951,6 +1956,11 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
       if (specScope == 3) wfShadeSpecKernel<3><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else if (specScope == 2) wfShadeSpecKernel<2><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else wfShadeSpecKernel<1><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
+    }
+    else if (adapt) {
+      if (c->S.motion)         wfShadeKernel<false, false, true, false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
+      else if (c->leanMaterials && !c->forceFull && c->S.lensCount == 0u) wfShadeKernel<false, true, false, false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
+      else                     wfShadeKernel<false, false, false, false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     }
     else if (drEnv)            wfShadeKernel<true, true, false, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
     else if (dr && wj.drLightCount != 0u) wfShadeKernel<true, true, false, false, true><<<sg, dim3(256), 0, gs>>>(c->S, P, wj);
@@ -1991,6 +2001,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   wj.passNum = job.passNum; wj.channels = job.channels; wj.outColor = job.outColor; wj.gens = job.gens; wj.packedXY = job.packedXY;
   wj.drSkipNonFinite = job.drSkipNonFinite;
   wj.refImg = job.refImg; wj.data = job.data; wj.grad = job.grad; wj.lossAccum = job.lossAccum; wj.record = nullptr;
+  if (adapt) { wj.passCounts = job.passCounts; wj.moments = job.moments; }   // (the same storage in both structs: hpt_decl.h)
   wj.adjImg = job.adjImg; wj.vjp = job.vjp;
   const bool drLights = dr && c->diffLightCount != 0u;        // (launch_path_trace has checked the registration against the scene)
   wj.drLightFirst = drLights ? job.drLightFirst : 0u; wj.drLightCount = drLights ? job.drLightCount : 0u; wj.drLightOff = drLights ? job.drLightOff : 0u;
@@ -1998,7 +2009,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   // every path takes at most traceDepth shade passes after the one that generated it; the pass that ends it (or the next one, when a
   // shadow ray was outstanding) also generates the pixel's next path
   // safety net only (the loop ends when a round queues no ray): pixels whose rays were suspended sit rounds out, so there is no tight bound
-  const unsigned long long iterCap = c->wfIterCap ? c->wfIterCap : 64ull * ((unsigned long long)job.passNum * (c->S.traceDepth + 2ull) + 4ull);
+  const unsigned long long iterCap = c->wfIterCap ? c->wfIterCap : 64ull * ((unsigned long long)(adapt ? *adaptMax : job.passNum) * (c->S.traceDepth + 2ull) + 4ull);
   c->lastWfIters = 0;
   unsigned long long capLeft = 0;                  // rays still queued when a group ran into iterCap
   const bool drLoss = dr && job.vjp == 0u;                  // (PathTraceVJP computes no loss: the slots stay zero and are not reduced)
@@ -2033,7 +2044,8 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
     P.susp[0] = g.u[7].p; P.susp[1] = g.u[8].p; P.maxSusp = (uint)maxSusp; P.suspStack = wfStackNeeded(c);
     HIPCHK(c, hipStreamWaitEvent(g.stream, c->wfFork, 0));
     HIPCHK(c, hipMemsetAsync(P.ctr, 0, 2 * WF_CTR_WORDS * sizeof(uint), g.stream));
-    wfInitKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, g.itemCount, job.passNum);
+    if (adapt) { wj.itemBase = g.itemBase; wj.itemCount = g.itemCount; wfInitCountsKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, wj); }
+    else wfInitKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, g.itemCount, job.passNum);
   }
   // ---- rounds: one shade + trace pass per live group, groups interleaved so that their kernels overlap on the device ----
   while (live > 0) {
@@ -2140,7 +2152,8 @@ static int sliceErrorCheck(hpt_ctx* c)
   return c->fail(HPT_ERR_STATE, "PathTraceBlock with pass slices: a lane waited for the slice before its own beyond the poll limit; the frame of that call is incomplete");
 }
 
-// Adaptive sampling serves forward RGB calls from the camera on the megakernel's ADAPT instantiations. What has none is refused by this one check:
+// Adaptive sampling serves forward RGB calls from the camera on the megakernel's ADAPT instantiations and, under "adaptive_wavefront", on the wavefront
+// schedule's (wfShadeKernel<.., ADAPT>). What has neither is refused by this one check, whichever form would run:
 // launch_path_trace makes it for every adaptive call, and the loop makes it once more before it touches the caller's records.
 static int adaptiveRefusal(hpt_ctx* c, bool naive, bool inRays)
 {
@@ -2150,7 +2163,26 @@ static int adaptiveRefusal(hpt_ctx* c, bool naive, bool inRays)
   return HPT_OK;
 }
 
-static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st, bool adapt = false)   // adapt: Job::passCounts / moments are set (the ADAPT kernels)
+// The wavefront form of an adaptive call ("adaptive_wavefront") is chosen, sized and refused on three numbers of its counts. The
+// loop knows them from its own plan; the bare counts entry has them counted on the device and reads the 12 bytes back on `st` - before anything
+// of the caller's is written, and in a schedule that synchronises with the host throughout anyway (its progress ring).
+static int adaptiveCountsSummary(hpt_ctx* c, const Job& job, hipStream_t st, WfCountsSummary& sum)
+{
+  if (job.passCounts == nullptr) { sum.maxCount = job.passNum; sum.active = job.passNum != 0u ? job.tidCount : 0u; sum.over = job.passNum > WF_MAX_PASSES ? 1u : 0u; return HPT_OK; }
+  WfJob wj; std::memset(&wj, 0, sizeof(wj));
+  wj.itemBase = 0u; wj.itemCount = job.tidCount; wj.tidBegin = job.tidBegin; wj.tidChunk = job.tidChunk; wj.tidStride = job.tidStride; wj.tidEnd = job.tidEnd;
+  wj.passCounts = job.passCounts;
+  HIPCHK(c, c->dAdSummary.alloc(1));
+  HIPCHK(c, hipMemsetAsync(c->dAdSummary.p, 0, sizeof(WfCountsSummary), st));
+  wfCountsSummaryKernel<<<dim3((job.tidCount + 255u) / 256u), dim3(256), 0, st>>>(wj, c->dAdSummary.p);
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&sum, c->dAdSummary.p, sizeof(WfCountsSummary), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return HPT_OK;
+}
+
+// adapt: Job::passCounts / moments are set (the ADAPT kernels); adaptKnown: the loop's summary of its counts (null: counted here when it is needed)
+static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st, bool adapt = false, const WfCountsSummary* adaptKnown = nullptr)
 {
   const bool inRays = job.inRayPos != nullptr;
   c->lastPassSlice = 0u;
@@ -2262,7 +2294,16 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   // item count fits the queue's 32-bit head with room for every lane's last draw.
   const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
   const bool streamCall = !adapt && c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u;
-  const bool waveCall = !adapt && !streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount);
+  // An adaptive call stays on the megakernel unless "adaptive_wavefront" is set; then it goes where a PathTraceBlock of as many pixels as it has
+  // counts above 0 would (under schedule 4, whose kernel does not serve it, the automatic rule). The counts are only looked at where the answer
+  // can be yes, i.e. where it is yes for the whole window.
+  WfCountsSummary adSum = { 0u, 0u, 0u };
+  bool adaptWave = false;
+  if (adapt && c->adaptiveWavefront && useWavefront(c, false, false, false, job.tidCount)) {
+    if (adaptKnown) adSum = *adaptKnown; else if (int rc = adaptiveCountsSummary(c, job, st, adSum)) return rc;
+    adaptWave = useWavefront(c, false, false, false, adSum.active);
+  }
+  const bool waveCall = adapt ? adaptWave : (!streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount));
   // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
   // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
   // 527 -> 630 at 512^2, PathTraceDR 428 -> 453) and heavy scenes in calls too small for the wavefront schedule (1 M triangles at 640 x 360: 145 -> 160);
@@ -2303,8 +2344,16 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     return launch_stream(c, job, st);
   }
   if (waveCall) {
+    if (adapt && adSum.over != 0u)                             // (nothing of the caller's has been written: frame, generators and moments keep every bit)
+      return c->fail(HPT_ERR_ARG, "adaptive sampling under the wavefront schedule: " + std::to_string(adSum.over) + " pass count(s) above 16777215 (0xFFFFFF), all that a pool slot's "
+                                  "status word holds; split the call, or render it with hpt_set_option(\"adaptive_wavefront\", 0)");
     c->lastSchedule = 2; c->lastWide = (wfWide(c) && !c->instrument) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
-    return launch_wavefront(c, job, st, dr);
+    if (adapt && adSum.maxCount == 0u) {                        // every count is 0: no round, nothing written
+      c->lastWfIters = 0;
+      HIPCHK(c, hipEventRecord(c->ev0, st)); HIPCHK(c, hipEventRecord(c->ev1, st));
+      return HPT_OK;
+    }
+    return launch_wavefront(c, job, st, dr, -1, adapt ? &adSum.maxCount : nullptr);
   }
   c->lastWide = (!stats && !motion && (HPT_FLAT_WIDE || c->S.megaWide != 0u) && c->S.flatMode != 0u && c->nodes4Count != 0u) ? 1u : 0u;
   c->lastDeep = megaStackNeeded(c) > (uint)LDS_STACK ? 1u : 0u;
@@ -2468,16 +2517,22 @@ catch (...) { return hptGuard(c, "hpt_naive_path_trace_block"); }
 // ---- adaptive sampling (hpt_adaptive.hip, the ADAPT instantiations of pathTraceKernel) ----------------------------------------
 static_assert(sizeof(hpt_pixel_moments) == sizeof(PixelMoments) && sizeof(hpt_adaptive_params) == sizeof(AdaptiveParams) && sizeof(hpt_adaptive_info) == sizeof(AdaptiveInfo),
               "the public records of adaptive sampling are the kernels' records");
+// known: what the caller knows of the counts - their largest (or a bound of it), how many are above 0, how many exceed WF_MAX_PASSES (the loop); null: nothing
+static int adaptiveCountsLaunch(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum, int naive,
+                                const uint32_t* passCountsDev, hpt_pixel_moments* momentsDev, void* stream, const WfCountsSummary* known)
+{
+  if (tidCount == 0 || (passNum == 0 && !passCountsDev)) return HPT_OK;
+  Job job; std::memset(&job, 0, sizeof(job));
+  job.tidBegin = tidBegin; job.tidCount = tidCount; job.passNum = passNum; job.channels = channels; job.outColor = outDev;
+  job.passCounts = passCountsDev; job.moments = (PixelMoments*)momentsDev;
+  return launch_path_trace(c, job, naive != 0, false, (hipStream_t)stream, true, known);
+}
 extern "C" int hpt_path_trace_block_counts_dev(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, uint32_t channels, float* outDev, uint32_t passNum, int naive,
                                                const uint32_t* passCountsDev, hpt_pixel_moments* momentsDev, void* stream)
 try {
   if (!c || !outDev) return HPT_ERR_ARG;
   (void)hipSetDevice(c->device);
-  if (tidCount == 0 || (passNum == 0 && !passCountsDev)) return HPT_OK;
-  Job job; std::memset(&job, 0, sizeof(job));
-  job.tidBegin = tidBegin; job.tidCount = tidCount; job.passNum = passNum; job.channels = channels; job.outColor = outDev;
-  job.passCounts = passCountsDev; job.moments = (PixelMoments*)momentsDev;
-  return launch_path_trace(c, job, naive != 0, false, (hipStream_t)stream, true);
+  return adaptiveCountsLaunch(c, tidBegin, tidCount, channels, outDev, passNum, naive, passCountsDev, momentsDev, stream, nullptr);
 }
 catch (...) { return hptGuard(c, "hpt_path_trace_block_counts_dev"); }
 
@@ -2516,8 +2571,14 @@ static int adaptivePlanLaunch(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, 
 }
 // What the loop refuses before it touches anything: the loop zeroes, plans and counts the contiguous window [tidBegin, tidBegin + tidCount), while a
 // render under hpt_set_tid_interleave with stride > 1 visits every stride-th chunk, far outside it - its counts would be read from words no planner wrote.
-static int adaptiveLoopCheck(hpt_ctx* c, uint32_t channels)
+// With "adaptive_wavefront" a round's counts must fit a pool slot's status word (WF_MAX_PASSES) wherever the schedule setting could send a round of this
+// window to the wavefront form; a round's largest count is bounded by minPasses (round 0) and min(step, maxPasses) (the planner's clip).
+static uint adaptiveRoundBound(const hpt_adaptive_params* p) { return std::min(p->step, p->maxPasses); }
+static int adaptiveLoopCheck(hpt_ctx* c, uint32_t channels, const hpt_adaptive_params* p, uint32_t tidCount)
 {
+  if (c->adaptiveWavefront && useWavefront(c, false, false, false, tidCount) && (p->minPasses > WF_MAX_PASSES || adaptiveRoundBound(p) > WF_MAX_PASSES))
+    return c->fail(HPT_ERR_ARG, "PathTraceBlockAdaptive under the wavefront schedule: minPasses and min(step, maxPasses) must not exceed 16777215 (0xFFFFFF), all that a pool "
+                                "slot's status word holds; lower them, or render with hpt_set_option(\"adaptive_wavefront\", 0)");
   if (c->tidStride > 1) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockAdaptive: the loop plans one contiguous tid window; under hpt_set_tid_interleave with stride > 1 drive "
                                                             "hpt_path_trace_block_counts_dev and hpt_adaptive_plan_dev yourself, or reset the interleave");
   if (int rc = adaptiveRefusal(c, false, false)) return rc;
@@ -2562,7 +2623,7 @@ try {
   (void)hipSetDevice(c->device);
   if (int rc = adaptiveParamsCheck(c, "PathTraceBlockAdaptive", params)) return rc;
   if (int rc = adaptiveWindowCheck(c, "PathTraceBlockAdaptive", tidBegin, tidCount)) return rc;
-  if (int rc = adaptiveLoopCheck(c, channels)) return rc;
+  if (int rc = adaptiveLoopCheck(c, channels, params, tidCount)) return rc;
   hipStream_t st = (hipStream_t)stream;
   AdaptiveInfo res; std::memset(&res, 0, sizeof(res));
   if (tidCount == 0) { std::memcpy(info, &res, sizeof(res)); return HPT_OK; }
@@ -2572,8 +2633,10 @@ try {
   HIPCHK(c, c->dAdInfo.alloc(1));
   HIPCHK(c, hipMemsetAsync(momentsDev + tidBegin, 0, (size_t)tidCount * sizeof(PixelMoments), st));
   float ms = 0.0f, kms = 0.0f;
-  // round 0: minPasses everywhere
-  if (int rc = hpt_path_trace_block_counts_dev(c, tidBegin, tidCount, channels, outDev, p.minPasses, 0, nullptr, momentsDev, stream)) return rc;
+  // round 0: minPasses everywhere. The schedule is chosen per round ("adaptive_wavefront"; the two forms are bit-identical) on the round's active
+  // pixels: the window here, later the plan's pixels above 0 - read back below anyway - with min(step, maxPasses) bounding the largest count
+  WfCountsSummary known = { p.minPasses, tidCount, 0u };
+  if (int rc = adaptiveCountsLaunch(c, tidBegin, tidCount, channels, outDev, p.minPasses, 0, nullptr, momentsDev, stream, &known)) return rc;
   res.rounds = 1u; res.passes = (unsigned long long)p.minPasses * tidCount;
   AdaptiveInfo plan; std::memset(&plan, 0, sizeof(plan));
   for (uint32_t round = 0; ; round++) {
@@ -2583,7 +2646,8 @@ try {
     if (int rc = sliceErrorCheck(c)) return rc;
     (void)hipEventElapsedTime(&kms, c->ev0, c->ev1); ms += kms;
     if (plan.passes == 0ull || round >= maxRounds) break;
-    if (int rc = hpt_path_trace_block_counts_dev(c, tidBegin, tidCount, channels, outDev, 0u, 0, c->dAdCounts.p, momentsDev, stream)) return rc;
+    known.maxCount = adaptiveRoundBound(params); known.active = plan.pixels;
+    if (int rc = adaptiveCountsLaunch(c, tidBegin, tidCount, channels, outDev, 0u, 0, c->dAdCounts.p, momentsDev, stream, &known)) return rc;
     res.rounds++; res.passes += plan.passes;
   }
   res.pixels = plan.pixels; res.maxPasses = plan.maxPasses; res.nonfinite = plan.nonfinite; res.deviceMs = ms;
@@ -2695,7 +2759,7 @@ try {
   (void)hipSetDevice(c->device);
   if (int rc = adaptiveParamsCheck(c, "PathTraceBlockAdaptive", params)) return rc;
   if (int rc = adaptiveWindowCheck(c, "PathTraceBlockAdaptive", tidBegin, tidCount)) return rc;
-  if (int rc = adaptiveLoopCheck(c, channels)) return rc;
+  if (int rc = adaptiveLoopCheck(c, channels, params, tidCount)) return rc;
   const size_t n = (size_t)c->packedCount * channels;
   HIPCHK(c, c->dFrame.upload(out, n));
   if (moments) HIPCHK(c, c->dAdMomentsIn.alloc(c->packedCount));
@@ -4089,6 +4153,7 @@ try {
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
   else if (k == "dr_environment") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_environment: 0 PathTraceDR / PathTraceVJP refuse scenes with an environment map or its sampling, 1 they render and differentiate them"); c->drEnvironment = value != 0; }
+  else if (k == "adaptive_wavefront") { if (value > 1) return c->fail(HPT_ERR_ARG, "adaptive_wavefront: 0 adaptive calls run the megakernel, 1 they take the wavefront schedule where a PathTraceBlock of their active pixels would"); c->adaptiveWavefront = value != 0; }
   else if (k == "kmlt_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "kmlt_spectral: 0 PathTraceBlockKMLT and the primary-sample-space pass refuse m_spectral_mode, 1 they run the spectral MLT kernels"); c->kmltSpectral = value != 0; }
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels

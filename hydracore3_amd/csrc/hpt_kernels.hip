@@ -339,12 +339,10 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
           else if (job.channels == 1) PIX(0) += accum.x * S.exposureMult;
           else { PIX(0) += S.exposureMult * c.x; PIX(1) += S.exposureMult * c.y; PIX(2) += S.exposureMult * c.z; }
           if constexpr (ADAPT) {
-            // the sample's luminance from the very values added above (Rec. 709 weights; the one value of a one-channel frame), in f32 and in
-            // this order; a non-finite sample is added as it is, as the frame adds it
+            // the sample's luminance from the very values added above (hpt_device.h: adaptSampleLuminance, shared with wfShadeKernel<.., ADAPT>);
+            // a non-finite sample is added as it is, as the frame adds it
             if (momentsOn) {
-              float y;
-              if (job.channels == 1) y = accum.x * S.exposureMult;
-              else { const float r = S.exposureMult * c.x, g = S.exposureMult * c.y, b = S.exposureMult * c.z; y = (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
+              const float y = adaptSampleLuminance(S, job.channels, accum, c);
               PIX_MOM(0) = __float_as_uint(__uint_as_float(PIX_MOM(0)) + y);
               PIX_MOM(1) = __float_as_uint(__uint_as_float(PIX_MOM(1)) + y * y);
               PIX_MOM(2) = PIX_MOM(2) + 1u;

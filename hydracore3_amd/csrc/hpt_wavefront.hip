@@ -21,24 +21,69 @@
 // the trace lanes supplied - stay on the megakernel (hpt_host.hip: useWavefront). The arithmetic per path is identical in both
 // schedules (same functions, same order, IEEE flags), so the two produce bit-identical frames; tests/test_gpu_parity.py holds
 // them to that. wfShadeKernel<DR = true> carries the differentiable integrator (adjoint records per slot, reverse sweep at path end).
+// Adaptive sampling ("Wavefront form"): the passes left already live per slot (status >> 8), so a per-pixel pass count is the
+// slot's initial status (wfInitCountsKernel) and a slot with none is never active; wfShadeKernel<.., ADAPT> adds each sample's luminance to the
+// pixel's moments where it contributes the sample; wfCountsSummaryKernel tells the host what it must know of the counts beforehand.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 
 namespace hpt {
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4)      // (small kernels: emitted once, with the shade kernels)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5)      // (small kernels: emitted once, with the shade kernels)
 __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 {
   const uint i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n) { P.status[i] = passNum << 8; P.inflight[i] = 0u; if (P.lossSlot) P.lossSlot[i] = 0.0f; }       // (the counters are zeroed by the host: the grid may be smaller than the counter block)
 }
+
+// ---- adaptive sampling ("Wavefront form") ---------------------------------------------------------------------------------
+// the tid of work item k, as wfShadeKernel maps it; false: the item lies past the frame and is dropped
+HPT_DEV bool wfItemTid(const WfJob& job, uint k, uint& tid)
+{
+  tid = job.tidBegin + (k / job.tidChunk) * job.tidChunk * job.tidStride + (k % job.tidChunk);
+  return tid < job.tidEnd;
+}
+// A per-pixel pass count is the slot's initial status: a slot with count 0 is never `active` and the shade kernel touches nothing of it. The host
+// has refused counts above WF_MAX_PASSES (wfCountsSummaryKernel), so the shift loses nothing.
+__global__ void __launch_bounds__(256) wfInitCountsKernel(WfPool P, const WfJob job)
+{
+  const uint s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= job.itemCount) return;
+  uint tid, passes = 0u;
+  if (wfItemTid(job, job.itemBase + s, tid)) passes = job.passCounts != nullptr ? job.passCounts[tid] : job.passNum;
+  P.status[s] = passes << 8; P.inflight[s] = 0u;
+}
+// the block's totals as in adaptivePlanKernel: the waves reduce with shuffles, lane 0 of the block folds the four partial results into *out with
+// one integer atomic per field
+__global__ void __launch_bounds__(256) wfCountsSummaryKernel(const WfJob job, WfCountsSummary* out)
+{
+  __shared__ uint waveMax[4], waveAct[4], waveOver[4];
+  const uint i = blockIdx.x * 256u + threadIdx.x;
+  uint n = 0u, tid;
+  if (i < job.itemCount && wfItemTid(job, job.itemBase + i, tid)) n = job.passCounts[tid];
+  uint mx = n, act = n > 0u ? 1u : 0u, over = n > WF_MAX_PASSES ? 1u : 0u;
+  for (int o = 32; o > 0; o >>= 1) {
+    act += __shfl_down(act, o); over += __shfl_down(over, o);
+    const uint other = __shfl_down(mx, o); mx = other > mx ? other : mx;
+  }
+  const uint wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63u) == 0u) { waveMax[wave] = mx; waveAct[wave] = act; waveOver[wave] = over; }
+  __syncthreads();
+  if (threadIdx.x == 0u) {
+    for (uint w = 1; w < 4u; w++) { act += waveAct[w]; over += waveOver[w]; mx = waveMax[w] > mx ? waveMax[w] : mx; }
+    if (mx != 0u) atomicMax(&out->maxCount, mx);
+    if (act != 0u) atomicAdd(&out->active, act);
+    if (over != 0u) atomicAdd(&out->over, over);
+  }
+}
 #endif
 
-template <bool DR, bool LEAN, bool MOTION, bool FILM, bool LGRAD, bool ENV>
+template <bool DR, bool LEAN, bool MOTION, bool FILM, bool LGRAD, bool ENV, bool ADAPT>
 __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const WfPool P, const WfJob job)
 {
   static_assert(!LGRAD || DR, "light-colour gradients: the DR shade kernel");
   static_assert(!ENV || (DR && !LGRAD), "environment maps in DR: the DR shade kernel, without light-colour gradients");
+  static_assert(!ADAPT || (!DR && !FILM), "adaptive sampling: the forward shade kernels without thin films");
   __shared__ uint drStage[DR ? 4 * DR_STAGE_DWORDS : 1];                   // the waves' staging areas of the cooperative gradient scatter (drReverseSweep)
   // light-colour gradients (LGRAD): the workgroup's bins, flushed at the end of this pass, and the light plane of the adjoint record (hpt_shade.h)
   float* lightBins = drLightBins<LGRAD>();
@@ -162,6 +207,16 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
       const V3 c = accum * ld3(S.camRespoceRGB);
       if (job.channels == 1) job.outColor[pixel] += accum.x * S.exposureMult;
       else { float* o = job.outColor + (size_t)pixel * job.channels; o[0] += S.exposureMult * c.x; o[1] += S.exposureMult * c.y; o[2] += S.exposureMult * c.z; }
+      if constexpr (ADAPT) {
+        // the pixel's record, in the megakernel's words (hpt_device.h: adaptSampleLuminance): a slot's samples finish in pass order - it regenerates
+        // only below, after this contribution - so the sums are the megakernel's bit for bit
+        if (job.moments != nullptr) {
+          const float y = adaptSampleLuminance(S, job.channels, accum, c);
+          PixelMoments m = job.moments[tid];
+          m.sumY = m.sumY + y; m.sumY2 = m.sumY2 + y * y; m.passes = m.passes + 1u; m.reserved = 0u;
+          job.moments[tid] = m;
+        }
+      }
     }
     if (!alive && !ending && passes != 0u) {                                 // kernel_InitEyeRay2: next pass of this pixel
       passes--;
@@ -205,7 +260,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   if (LGRAD) drLightFlush(lightBins, job.grad, lightReg);
 }
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5)
 // DR: sum of the per-slot losses in double, one atomic per block; wfLossFinishKernel adds the total to the caller's float
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc)
 {
@@ -476,7 +531,13 @@ __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScen
 
 // ---- explicit instantiations (the host launches them through the declarations in hpt_decl.h) -----------------------------------------------
 #ifndef HPT_WF_INST
-#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients; 4: the shade kernel over environment maps
+#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients; 4: the shade kernel over environment maps; 5: the shade kernels of adaptive sampling
+#endif
+#if HPT_WF_INST == 0 || HPT_WF_INST == 5
+// adaptive sampling (hpt_set_option "adaptive_wavefront"): the three forward kernels an adaptive call can reach
+template __global__ void wfShadeKernel<false, true, false, false, false, false, true>(const DevScene, const WfPool, const WfJob);    // lean
+template __global__ void wfShadeKernel<false, false, false, false, false, false, true>(const DevScene, const WfPool, const WfJob);   // every BSDF branch
+template __global__ void wfShadeKernel<false, false, true, false, false, false, true>(const DevScene, const WfPool, const WfJob);    // moving instances
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 1
 template __global__ void wfShadeKernel<true, true>(const DevScene, const WfPool, const WfJob);

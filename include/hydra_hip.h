@@ -700,6 +700,16 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               comes back in a_dataGrad (hpt_put_diff_tex2d). Still HPT_ERR_UNSUPPORTED: a camera back plate (the replay has none),
  *               hpt_put_diff_lights on the same context, an explicit block-local schedule (the automatic choice avoids it), the instrumented
  *               probe, spectral, lens and motion scenes. Scenes without a map run the kernels they always ran. Any other value: HPT_ERR_ARG.
+ * Which schedule serves adaptive sampling (results never depend on it):
+ *   "adaptive_wavefront"  0 (default): hpt_path_trace_block_counts[_dev] and every round of hpt_path_trace_block_adaptive[_dev] run the megakernel
+ *               whatever hpt_set_schedule says. 1: each such call goes to the wavefront schedule exactly when a PathTraceBlock of as many pixels
+ *               as the call has pass counts above 0 would - schedule 0: the automatic rule, 2: always, 1 and 3: never, 4: the automatic rule - and
+ *               hpt_get_last_launch reports what ran. Frame, m_randomGens and moments are bit for bit the megakernel's. The bare counts entry
+ *               counts its array on the device first (12 bytes read back before anything is written); the loop decides per round from its
+ *               own plan. A pool slot holds 24 bits of passes: a call that would run the wavefront form with a count above 16777215 (0xFFFFFF),
+ *               and a loop whose minPasses or min(step, maxPasses) exceeds it, return HPT_ERR_ARG and write nothing. Counts that are all 0
+ *               return HPT_OK and write nothing. What adaptive sampling refuses (spectral mode, thin films, the naive integrator, input rays,
+ *               the instrumented probe) it refuses under either value. Any other value: HPT_ERR_ARG.
  * Diagnostic switches (these DO change which kernels run or what they compute; never set in production):
  *   "dr_skip_nonfinite"     PathTraceDR: 1 = a sample whose radiance is not finite contributes neither colour, loss nor gradient (what an
  *                           optimisation loop wants: one NaN poisons Adam's moments for good); 0 (default) = PixelLossPT as the reference
