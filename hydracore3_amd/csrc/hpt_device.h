@@ -68,6 +68,78 @@ HPT_DEV float absf(float a) { return __builtin_fabsf(a); }
 HPT_DEV float sqrtf_(float a) { return __builtin_sqrtf(a); }
 HPT_DEV bool finitef(float a) { return absf(a) <= HPT_FLT_MAX; }     // false for NaN and +-inf
 
+// ---- IEEE division without the compiler's scale / fixup wrapper (profiles/exact_div.md) ---------------------------------------------
+// The toolchain expands an f32 division into v_div_scale x 2, v_rcp, six fma-class steps, v_div_fmas and v_div_fixup. For operands well
+// inside the normal range both v_div_scale return their operand unscaled with VCC clear, v_div_fmas is then a plain fma and v_div_fixup
+// passes the quotient through, so the SAME rcp + fma chain without the three wrappers gives the same bits. The helpers replay that chain
+// when every active lane of the wave is in range (one wave-uniform branch) and fall back to the plain expression otherwise.
+//   rcpIeee: biased exponent of x in [64, 191] (2^-63 <= |x| < 2^65); the compiler's wrapper is the identity for [32, 252]
+//   divIeee: biased exponents of a and b in [96, 159] (2^-31 <= |v| < 2^33), so their difference is within +-63; the wrapper is the
+//            identity when b is in [1, 252], a is over 23, a - b is under 96 and the quotient is normal
+// Both ranges are a power of two of exponents wide: (bits << 1) - (lo << 24) drops the sign and is below (width << 24) exactly inside.
+#ifndef HPT_EXACT_DIV_FAST
+#define HPT_EXACT_DIV_FAST 1              // 0: rcpIeee / divIeee are the plain expressions (A/B switch and escape hatch)
+#endif
+#define HPT_HDF __host__ __device__ __forceinline__
+HPT_HDF uint exactDivBits(const float x) { return __builtin_bit_cast(uint, x); }
+HPT_HDF uint rcpIeeeOff(const float x) { return (exactDivBits(x) << 1) - (64u << 24); }      // in range: below 128 << 24
+HPT_HDF uint divIeeeOff(const float x) { return (exactDivBits(x) << 1) - (96u << 24); }      // in range: below 64 << 24
+HPT_HDF bool rcpIeeeInRange(const float x) { return rcpIeeeOff(x) < (128u << 24); }
+HPT_HDF bool rcpIeeeInRange(const float x, const float y) { return (rcpIeeeOff(x) | rcpIeeeOff(y)) < (128u << 24); }
+HPT_HDF bool divIeeeInRange(const float a, const float b) { return (divIeeeOff(a) | divIeeeOff(b)) < (64u << 24); }
+HPT_HDF float rcpSeed(const float x)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_rcpf(x);
+#else
+  return 1.0f / x;                        // host stand-in (the probe's host build checks the guard, not the chain)
+#endif
+}
+HPT_HDF bool waveAll(const bool p)
+{
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __builtin_amdgcn_ballot_w64(!p) == 0ull;
+#else
+  return p;
+#endif
+}
+// the compiler's chain for 1 / x: the numerator is 1, so its quotient product 1 * r is r itself
+HPT_HDF float rcpIeeeChain(const float x)
+{
+  const float r0 = rcpSeed(x);
+  const float r = __builtin_fmaf(__builtin_fmaf(-x, r0, 1.0f), r0, r0);
+  const float q = __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
+  return __builtin_fmaf(__builtin_fmaf(-x, q, 1.0f), r, q);
+}
+// r: the denominator's refined reciprocal (one Newton step on the seed), shared by quotients over one denominator
+HPT_HDF float divIeeeChain(const float a, const float b, const float r)
+{
+  const float q0 = a * r;
+  const float q1 = __builtin_fmaf(__builtin_fmaf(-b, q0, a), r, q0);
+  return __builtin_fmaf(__builtin_fmaf(-b, q1, a), r, q1);
+}
+HPT_HDF float divIeeeRefine(const float b) { const float r0 = rcpSeed(b); return __builtin_fmaf(__builtin_fmaf(-b, r0, 1.0f), r0, r0); }
+HPT_HDF float rcpIeee(const float x, bool& fast)
+{
+  fast = HPT_EXACT_DIV_FAST && waveAll(rcpIeeeInRange(x));
+  if (fast) return rcpIeeeChain(x);
+  return 1.0f / x;
+}
+HPT_HDF float rcpIeee(const float x) { bool fast; return rcpIeee(x, fast); }
+// two reciprocals behind one branch (the sweep's triangle pairs)
+HPT_HDF void rcpIeee2(const float x, const float y, float& rx, float& ry)
+{
+  if (HPT_EXACT_DIV_FAST && waveAll(rcpIeeeInRange(x, y))) { rx = rcpIeeeChain(x); ry = rcpIeeeChain(y); }
+  else { rx = 1.0f / x; ry = 1.0f / y; }
+}
+HPT_HDF float divIeee(const float a, const float b, bool& fast)
+{
+  fast = HPT_EXACT_DIV_FAST && waveAll(divIeeeInRange(a, b));
+  if (fast) return divIeeeChain(a, b, divIeeeRefine(b));
+  return a / b;
+}
+HPT_HDF float divIeee(const float a, const float b) { bool fast; return divIeee(a, b, fast); }
+
 // column-major 4x4 (LiteMath float4x4): element (row,col) = m[col*4+row]
 HPT_DEV V4 mul4x4(const float* m, V4 v)
 {
@@ -1455,13 +1527,14 @@ typedef __attribute__((address_space(4))) const u32x4n cuint4;
 HPT_DEV float4 ldc4(const cfloat4* p) { const f32x4n v = *p; return make_float4(v.x, v.y, v.z, v.w); }
 // The sweep visits (instance, primitive) pairs in increasing order (DevScene::sweepTris holds each instance's records sorted by primitive
 // id), so the tie rule of triangleTest - at equal distance the lower (instId, primId) wins - reduces to "the first one found stays".
-HPT_DEV void triangleTestInOrder(const float4 a, const float4 b, const float4 c, const V3 o, const V3 d, const float tnear, const uint inst,
+// (triangleDet: the determinant alone, so that a pair's two reciprocals share one guard - rcpIeee2; the tests repeat the expression)
+HPT_DEV float triangleDet(const float4 b, const float4 c, const V3 d) { return dot(v3(b.x, b.y, b.z), cross(d, v3(c.x, c.y, c.z))); }
+HPT_DEV void triangleTestInOrder(const float4 a, const float4 b, const float4 c, const V3 o, const V3 d, const float tnear, const uint inst, const float inv,
                                  float& bestT, uint& bestPrim, uint& bestInst, float& bestU, float& bestV, bool& found)
 {
   const V3 e1 = v3(b.x, b.y, b.z), e2 = v3(c.x, c.y, c.z);
   const V3 pvec = cross(d, e2);
-  const float det = dot(e1, pvec);
-  const float inv = 1.0f / det;
+  const float det = dot(e1, pvec);                                         // inv = 1 / det, bit for bit (rcpIeee2)
   const V3 tvec = o - v3(a.x, a.y, a.z);
   const float uu = dot(tvec, pvec) * inv;
   const V3 qvec = cross(tvec, e1);
@@ -1473,12 +1546,11 @@ HPT_DEV void triangleTestInOrder(const float4 a, const float4 b, const float4 c,
   if (ok) { bestT = tt; bestPrim = __float_as_uint(a.w); bestInst = inst; bestU = uu; bestV = vv; found = true; }
 }
 // the same test for occlusion queries: any triangle with t in [tnear, tfar] ends the search, so nothing but the flag is kept
-HPT_DEV bool triangleOccludes(const float4 a, const float4 b, const float4 c, const V3 o, const V3 d, const float tnear, const float tfar)
+HPT_DEV bool triangleOccludes(const float4 a, const float4 b, const float4 c, const V3 o, const V3 d, const float tnear, const float tfar, const float inv)
 {
   const V3 e1 = v3(b.x, b.y, b.z), e2 = v3(c.x, c.y, c.z);
   const V3 pvec = cross(d, e2);
   const float det = dot(e1, pvec);
-  const float inv = 1.0f / det;
   const V3 tvec = o - v3(a.x, a.y, a.z);
   const float uu = dot(tvec, pvec) * inv;
   const V3 qvec = cross(tvec, e1);
@@ -1563,13 +1635,14 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
         const float4* tp = tv + 6u * k;
         const float4 a0 = tp[0], b0 = tp[1], c0 = tp[2], a1 = tp[3], b1 = tp[4], c1 = tp[5];
         if (STATS) { st.tris += 2; if (firstActiveLane()) { st.waveTriIters += 2; st.wavePairTrips[ANY ? 1 : 0]++; } }
+        float inv0, inv1; rcpIeee2(triangleDet(b0, c0, d), triangleDet(b1, c1, d), inv0, inv1);
         if (ANY) {
-          found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar);
-          found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar);
+          found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar, inv0);
+          found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar, inv1);
           if (found) mask = 0u;
         } else {
-          triangleTestInOrder(a0, b0, c0, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
-          triangleTestInOrder(a1, b1, c1, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+          triangleTestInOrder(a0, b0, c0, o, d, tnear, i, inv0, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+          triangleTestInOrder(a1, b1, c1, o, d, tnear, i, inv1, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
         }
       }
       if (ANY && __ballot(!found) == 0ull) return true;                    // every lane of the wave that traces a ray has its occluder
@@ -1592,14 +1665,15 @@ HPT_DEV bool traceSweep(const DevScene& S, const V3 wo, const V3 wd, const float
       // six scalar loads, one wait: two triangles per trip
       const float4 a0 = ldc4(tp), b0 = ldc4(tp + 1), c0 = ldc4(tp + 2), a1 = ldc4(tp + 3), b1 = ldc4(tp + 4), c1 = ldc4(tp + 5);
       if (STATS) { st.tris += 2; if (firstActiveLane()) { st.waveTriIters += 2; st.wavePairTrips[ANY ? 1 : 0]++; } }
+      float inv0, inv1; rcpIeee2(triangleDet(b0, c0, d), triangleDet(b1, c1, d), inv0, inv1);
       if (ANY) {
-        found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar);
-        found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar);
+        found |= triangleOccludes(a0, b0, c0, o, d, tnear, tfar, inv0);
+        found |= triangleOccludes(a1, b1, c1, o, d, tnear, tfar, inv1);
         if (__ballot(!found) == 0ull) return true;                         // every lane of the wave that traces a ray has its occluder
         continue;
       }
-      triangleTestInOrder(a0, b0, c0, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
-      triangleTestInOrder(a1, b1, c1, o, d, tnear, i, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+      triangleTestInOrder(a0, b0, c0, o, d, tnear, i, inv0, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
+      triangleTestInOrder(a1, b1, c1, o, d, tnear, i, inv1, hit.t, hit.prim, hit.inst, hit.u, hit.v, found);
       if (ANY && __ballot(!found) == 0ull) return true;                    // every lane of the wave that traces a ray has its occluder
     }
   }
