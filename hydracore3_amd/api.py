@@ -914,7 +914,11 @@ class HipIntegrator:
     def set_option(self, name: str, value: int):
         """hpt_set_option (include/hydra_hip.h lists the names). Among them "adaptive_wavefront": 0 (default) the adaptive calls - PathTraceBlockCounts
         and every round of PathTraceBlockAdaptive - run the megakernel; 1 each goes to the wavefront schedule where a PathTraceBlock of as many pixels
-        as it has counts above 0 would (set_schedule). Frames, generators and moments are the same bit for bit; a count above 0xFFFFFF is refused there."""
+        as it has counts above 0 would (set_schedule). Frames, generators and moments are the same bit for bit; a count above 0xFFFFFF is refused there.
+        "adaptive_spectral": 0 (default) the adaptive calls refuse a spectral context; 1 they are served there (thin films, dispersion and moving instances
+        included; 1, 3 or 4 channels, no wavelength layers): a pixel given k passes is a uniform spectral PathTraceBlock pixel of k passes bit for bit, and
+        the records take the luminance of what each sample adds to the frame, so AdaptivePlan, AdaptiveResolve, AdaptiveVariance and denoise_var work on
+        them unchanged. Together with "adaptive_wavefront" such calls take the wavefront schedule under the same rule."""
         self._chk(self.L.hpt_set_option(self.h, name.encode(), value))
         if name == "qmc_spectral":
             self._qmc_spectral = bool(value)     # PathTraceBlockQMC then takes frames of more than 4 channels

@@ -90,7 +90,8 @@ __global__ void HPT_PT_BOUNDS(DR, MODE) pathTraceKernel(const DevScene S, const 
 #ifndef HPT_SPEC_WIDE_WAVES
 #define HPT_SPEC_WIDE_WAVES 3   // ... scope 2
 #endif
-template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>   // SCOPE 0: the reference's spectral fixtures' needs; 1: + gltf; 2: + glass / blends / normal maps / environment maps / lens; 3: the same at 4 waves per SIMD
+// ADAPT: per-pixel pass counts (Job::passCounts) and luminance moments (Job::moments), as in pathTraceKernel: PathTraceBlock from the camera only
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE, bool ADAPT = false>   // SCOPE 0: the reference's spectral fixtures' needs; 1: + gltf; 2: + glass / blends / normal maps / environment maps / lens; 3: the same at 4 waves per SIMD
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceSpectralKernel(const DevScene S, const Job job);
 
 template <bool DEEP, bool FLAT, bool WIDE, int SCOPE>   // the same integrator under the block-local schedule (work queue, LDS ray pool, ray replacement; hpt_spectral.hip)
@@ -220,7 +221,7 @@ __global__ void __launch_bounds__(256) wfCountsSummaryKernel(const WfJob job, Wf
 template <bool DEEP>                                                    // block-owned streaming form of the wavefront schedule (hpt_stream.hip; schedule 4)
 __global__ void __launch_bounds__(256, HPT_STREAM_WAVES) streamKernel(const DevScene S, const WfPool P, const WfJob job, uint slotsPerBlock, uint refillBelow, uint* blockQueues,
                                                                       uint* stackOverflow, uint gridLanes);
-template <int SCOPE>                                                    // spectral rendering under the wavefront schedule (hpt_spectral.hip)
+template <int SCOPE, bool ADAPT = false>                                // spectral rendering under the wavefront schedule (hpt_spectral.hip); ADAPT: the moments of WfJob::moments, as in wfShadeKernel
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) wfShadeSpecKernel(const DevScene S, const WfPool P, const WfJob job);
 // FILM: shadeVertex<FILM> (thin films, hpt_film.h); LGRAD (with DR): light-colour gradients; ENV (with DR): environment maps;
 // ADAPT (forward, without FILM): the luminance moments of WfJob::moments at kernel_ContributeToImage (the per-pixel pass counts are the slots' initial status)

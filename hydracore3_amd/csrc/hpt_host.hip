@@ -186,6 +186,7 @@ struct hpt_ctx
   // adaptive sampling (hpt_adaptive.hip): the loop's pass counts [tid], the planner's need image [pixel] and totals, the records of a
   // loop whose caller keeps none, the host forms' copies of the caller's arrays; all grown on first use, none allocated per round
   DevBuf<uint> dAdCounts, dAdNeed, dAdCountsIn; DevBuf<AdaptiveInfo> dAdInfo; DevBuf<PixelMoments> dAdMoments, dAdMomentsIn;
+  bool adaptiveSpectral = false;                         // hpt_set_option("adaptive_spectral", 1): adaptive calls are served under m_spectral_mode (the ADAPT instantiations of hpt_spectral.hip)
   bool adaptiveWavefront = false;                        // hpt_set_option("adaptive_wavefront", 1): an adaptive call takes the wavefront schedule where a PathTraceBlock of its active pixels would
   DevBuf<WfCountsSummary> dAdSummary;                    // ... and the 12 bytes of its counts summary (wfCountsSummaryKernel)
   DevBuf<uint> dQmcTable;                                // the Niederreiter table of PathTraceBlockQMC: uploaded at the first call, 1364 bytes
@@ -1821,17 +1822,23 @@ static void launchBlock(const DevScene& S, const Job& job, int blocks, hipStream
   else            { if (deep) pathTraceBlockKernel<DR, LEAN, true, false, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); else pathTraceBlockKernel<DR, LEAN, false, false, false, VJP><<<g, b, 0, st>>>(S, job, refillBelow, nodeMin); }
 }
 
-template <int WIDE>
+template <int WIDE, bool ADAPT = false>                       // ADAPT: per-pixel pass counts and moments ("adaptive_spectral")
 static void launchSpectral(const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
 {
   const dim3 sg(blocks), sb(256);
   if (S.motion) {                                              // moving instances (never a sweep scene)
-    if (S.flatMode) { if (deep) pathTraceSpectralKernel<true, true, false, true, WIDE><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, true, false, true, WIDE><<<sg, sb, 0, st>>>(S, job); }
-    else            { if (deep) pathTraceSpectralKernel<true, false, false, true, WIDE><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, false, false, true, WIDE><<<sg, sb, 0, st>>>(S, job); }
+    if (S.flatMode) { if (deep) pathTraceSpectralKernel<true, true, false, true, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, true, false, true, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); }
+    else            { if (deep) pathTraceSpectralKernel<true, false, false, true, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, false, false, true, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); }
   }
-  else if (S.sweep)     pathTraceSpectralKernel<false, false, true, false, WIDE><<<sg, sb, 0, st>>>(S, job);
-  else if (S.flatMode)  { if (deep) pathTraceSpectralKernel<true, true, false, false, WIDE><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, true, false, false, WIDE><<<sg, sb, 0, st>>>(S, job); }
-  else                  { if (deep) pathTraceSpectralKernel<true, false, false, false, WIDE><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, false, false, false, WIDE><<<sg, sb, 0, st>>>(S, job); }
+  else if (S.sweep)     pathTraceSpectralKernel<false, false, true, false, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job);
+  else if (S.flatMode)  { if (deep) pathTraceSpectralKernel<true, true, false, false, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, true, false, false, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); }
+  else                  { if (deep) pathTraceSpectralKernel<true, false, false, false, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); else pathTraceSpectralKernel<false, false, false, false, WIDE, ADAPT><<<sg, sb, 0, st>>>(S, job); }
+}
+template <bool ADAPT>
+static void launchSpectralScope(int scope, const DevScene& S, const Job& job, int blocks, hipStream_t st, bool deep)
+{
+  if (scope == 3) launchSpectral<3, ADAPT>(S, job, blocks, st, deep);
+  else if (scope == 2) launchSpectral<2, ADAPT>(S, job, blocks, st, deep); else if (scope == 1) launchSpectral<1, ADAPT>(S, job, blocks, st, deep); else launchSpectral<0, ADAPT>(S, job, blocks, st, deep);
 }
 
 template <int SCOPE>
@@ -1945,14 +1952,19 @@ static bool drEnvReads(const hpt_ctx* c, uint texId)
 // moments are set, the slots start with their own counts (wfInitCountsKernel) and the ADAPT shade kernels run
 static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1, const uint* adaptMax = nullptr)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
 {
-  const bool adapt = adaptMax != nullptr;                       // (forward RGB from the camera without thin films: adaptiveRefusal)
+  const bool adapt = adaptMax != nullptr;                       // (forward calls from the camera, RGB without thin films or spectral: adaptiveRefusal)
   const bool spec = specScope >= 0;
   const bool drEnv = dr && drEnvironmentCall(c);               // (launch_path_trace has made the refusals)
   const bool envPlane = drEnv && drEnvMapRegistered(c);
   DevScene Sw = c->S;
   if (spec) Sw.shadeTris = nullptr;                  // the spectral shade kernel fetches its surface through the primitive id: the trace pass must report that
   auto launchShade = [&](const dim3 sg, hipStream_t gs, const WfPool& P, const WfJob& wj) {
-    if (spec) {
+    if (spec && adapt) {
+      if (specScope == 3) wfShadeSpecKernel<3, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
+      else if (specScope == 2) wfShadeSpecKernel<2, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
+      else wfShadeSpecKernel<1, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
+    }
+    else if (spec) {
       if (specScope == 3) wfShadeSpecKernel<3><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else if (specScope == 2) wfShadeSpecKernel<2><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else wfShadeSpecKernel<1><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
@@ -2152,13 +2164,24 @@ static int sliceErrorCheck(hpt_ctx* c)
   return c->fail(HPT_ERR_STATE, "PathTraceBlock with pass slices: a lane waited for the slice before its own beyond the poll limit; the frame of that call is incomplete");
 }
 
+// Where wfShadeSpecKernel applies at all: PathTraceBlock from the camera on static, non-sweep scenes with a trace depth (no naive / input-ray /
+// moving-instance variant: those keep their kernels). An adaptive call under "adaptive_wavefront" can take the wavefront form only where this holds.
+static bool spectralWaveApplies(const hpt_ctx* c, bool naive, bool inRays)
+{ return !inRays && !naive && c->S.motion == 0u && c->S.sweep == 0u && c->S.traceDepth > 0u && !c->instrument; }
+// ... and whether any adaptive call of this context can be sent to the wavefront schedule (the 24-bit limit of the loop holds only there)
+static bool adaptiveWaveReachable(hpt_ctx* c, uint tidCount)
+{ return c->adaptiveWavefront && useWavefront(c, false, false, false, tidCount) && (c->S.spectralMode == 0u || spectralWaveApplies(c, false, false)); }
+
 // Adaptive sampling serves forward RGB calls from the camera on the megakernel's ADAPT instantiations and, under "adaptive_wavefront", on the wavefront
-// schedule's (wfShadeKernel<.., ADAPT>). What has neither is refused by this one check, whichever form would run:
+// schedule's (wfShadeKernel<.., ADAPT>); under "adaptive_spectral" also contexts in spectral mode, thin films among them, on the ADAPT instantiations of
+// pathTraceSpectralKernel and wfShadeSpecKernel - but not their wavelength layers (channels > 4), over which a moment has no definition. What has
+// no kernel is refused by this one check, whichever form would run:
 // launch_path_trace makes it for every adaptive call, and the loop makes it once more before it touches the caller's records.
-static int adaptiveRefusal(hpt_ctx* c, bool naive, bool inRays)
+static int adaptiveRefusal(hpt_ctx* c, bool naive, bool inRays, uint channels)
 {
-  const char* why = c->S.spectralMode != 0u ? "m_spectral_mode" : (c->hasFilm ? "scenes with thin films" : (naive ? "the naive integrator" :
-                    (inRays ? "input rays" : (c->instrument ? "the instrumented probe" : nullptr))));
+  const bool spec = c->S.spectralMode != 0u;
+  const char* why = (spec && !c->adaptiveSpectral) ? "m_spectral_mode" : ((c->hasFilm && !spec) ? "scenes with thin films" : (naive ? "the naive integrator" :
+                    (inRays ? "input rays" : (c->instrument ? "the instrumented probe" : ((spec && channels > 4u) ? "wavelength layers (channels > 4)" : nullptr)))));
   if (why) return c->fail(HPT_ERR_UNSUPPORTED, std::string("adaptive sampling (per-pixel pass counts): not served for ") + why + " (DESIGN.md 2.13)");
   return HPT_OK;
 }
@@ -2181,13 +2204,29 @@ static int adaptiveCountsSummary(hpt_ctx* c, const Job& job, hipStream_t st, WfC
   return HPT_OK;
 }
 
+// Whether an adaptive call takes the wavefront form ("adaptive_wavefront"): where a PathTraceBlock of as many pixels as it has counts above 0 would. The
+// counts are only looked at where the answer can be yes, i.e. where it is yes for the whole window.
+static int adaptiveWaveChoice(hpt_ctx* c, const Job& job, hipStream_t st, const WfCountsSummary* known, WfCountsSummary& sum, bool& wave)
+{
+  wave = false;
+  if (!c->adaptiveWavefront || !useWavefront(c, false, false, false, job.tidCount)) return HPT_OK;
+  if (known) sum = *known; else if (int rc = adaptiveCountsSummary(c, job, st, sum)) return rc;
+  wave = useWavefront(c, false, false, false, sum.active);
+  return HPT_OK;
+}
+static int adaptiveOverRefusal(hpt_ctx* c, const WfCountsSummary& sum)     // (nothing of the caller's has been written: frame, generators and moments keep every bit)
+{
+  return c->fail(HPT_ERR_ARG, "adaptive sampling under the wavefront schedule: " + std::to_string(sum.over) + " pass count(s) above 16777215 (0xFFFFFF), all that a pool slot's "
+                              "status word holds; split the call, or render it with hpt_set_option(\"adaptive_wavefront\", 0)");
+}
+
 // adapt: Job::passCounts / moments are set (the ADAPT kernels); adaptKnown: the loop's summary of its counts (null: counted here when it is needed)
 static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStream_t st, bool adapt = false, const WfCountsSummary* adaptKnown = nullptr)
 {
   const bool inRays = job.inRayPos != nullptr;
   c->lastPassSlice = 0u;
   if (int rc = sliceErrorCheck(c)) return rc;
-  if (adapt) { if (int rc = adaptiveRefusal(c, naive, inRays)) return rc; }
+  if (adapt) { if (int rc = adaptiveRefusal(c, naive, inRays, job.channels)) return rc; }
   if (!c->sceneUploaded || !c->paramsSet) return c->fail(HPT_ERR_STATE, "PathTraceBlock before CommitDeviceData / UpdateMembersPlainData");
   if (!inRays && c->packedCount != (uint)(c->S.winWidth * c->S.winHeight)) return c->fail(HPT_ERR_STATE, "PathTraceBlock before PackXYBlock");
   job.tidStride = c->tidStride > 1 ? c->tidStride : 1u;
@@ -2245,14 +2284,26 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     // Schedule: scenes whose rays walk a real tree (SAH estimate >= 8: the reference's spectral fixture, interiors) run the block-local kernel -
     // persistent blocks on the work queue, rays repacked per block, the 4-wide tree on heavy scenes; the others, input-ray batches, moving
     // instances and sweep scenes keep the one-thread-per-pixel kernel. hpt_set_schedule(1) / (3) force either.
-    const bool specBlock = !inRays && c->S.motion == 0u && c->S.sweep == 0u && (c->S.traceDepth > 0u || naive) &&
+    const bool specBlock = !adapt && !inRays && c->S.motion == 0u && c->S.sweep == 0u && (c->S.traceDepth > 0u || naive) &&
                            (c->schedule == 3 || (c->schedule == 0 && c->sahVisits >= BLOCK_SAH_VISITS));
     // ... and heavy scenes in calls with enough pixels the wavefront schedule (wfShadeSpecKernel + the shared trace kernel), as their RGB rendering does
-    const bool specWave = !inRays && !naive && c->S.motion == 0u && c->S.sweep == 0u && c->S.traceDepth > 0u && !c->instrument &&
-                          (c->schedule == 2 || (c->schedule == 0 && c->sahVisits >= HEAVY_SAH_VISITS && job.tidCount >= WF_AUTO_PIXELS));
+    // An adaptive call ("adaptive_spectral") keeps the one-thread-per-pixel kernel unless "adaptive_wavefront" sends it to the wavefront schedule under the
+    // RGB form's rule (adaptiveWaveChoice), where wfShadeSpecKernel applies at all
+    const bool specWaveApplies = spectralWaveApplies(c, naive, inRays);
+    WfCountsSummary adSum = { 0u, 0u, 0u };
+    bool adaptWave = false;
+    if (adapt && specWaveApplies) { if (int rc = adaptiveWaveChoice(c, job, st, adaptKnown, adSum, adaptWave)) return rc; }
+    const bool specWave = adapt ? adaptWave : (specWaveApplies &&
+                          (c->schedule == 2 || (c->schedule == 0 && c->sahVisits >= HEAVY_SAH_VISITS && job.tidCount >= WF_AUTO_PIXELS)));
     if (specWave) {
+      if (adapt && adSum.over != 0u) return adaptiveOverRefusal(c, adSum);
       c->lastSchedule = 2; c->lastWide = wfWide(c) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u; c->lastShadeRecords = 0u;
-      return launch_wavefront(c, job, st, false, scope == 0 ? 1 : scope);
+      if (adapt && adSum.maxCount == 0u) {                      // every count is 0: no round, nothing written
+        c->lastWfIters = 0;
+        HIPCHK(c, hipEventRecord(c->ev0, st)); HIPCHK(c, hipEventRecord(c->ev1, st));
+        return HPT_OK;
+      }
+      return launch_wavefront(c, job, st, false, scope == 0 ? 1 : scope, adapt ? &adSum.maxCount : nullptr);
     }
     if (specBlock) {
       const bool bwide = c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u;
@@ -2277,8 +2328,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     return launchFrame(c, (size_t)sblocks * 256, st, [&]() {
       c->lastSchedule = 1; c->lastWide = (c->S.megaWide != 0u && c->S.flatMode != 0u && c->nodes4Count != 0u && c->S.motion == 0u) ? 1u : 0u; c->lastDeep = sdeep ? 1u : 0u; c->lastShadeRecords = 0u;
       job.stackOverflow = c->dStackOvf.p; job.gridLanes = (uint)sblocks * 256u;
-      if (scope == 3) launchSpectral<3>(c->S, job, sblocks, st, sdeep);
-      else if (scope == 2) launchSpectral<2>(c->S, job, sblocks, st, sdeep); else if (scope == 1) launchSpectral<1>(c->S, job, sblocks, st, sdeep); else launchSpectral<0>(c->S, job, sblocks, st, sdeep);
+      if (adapt) launchSpectralScope<true>(scope, c->S, job, sblocks, st, sdeep); else launchSpectralScope<false>(scope, c->S, job, sblocks, st, sdeep);
     });
   }
   { const int rcS = ensureShadeTris(c, st); if (rcS != HPT_OK) return rcS; }
@@ -2295,14 +2345,10 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
   const bool stats = c->instrument;                            // (the DR probe exists as a megakernel only: hpt_kernels.hip, group 15)
   const bool streamCall = !adapt && c->schedule == 4 && !inRays && !naive && !dr && !stats && !motion && !film && c->leanMaterials && !c->forceFull && c->S.lensCount == 0u && wfWide(c) && c->S.traceDepth > 0u;
   // An adaptive call stays on the megakernel unless "adaptive_wavefront" is set; then it goes where a PathTraceBlock of as many pixels as it has
-  // counts above 0 would (under schedule 4, whose kernel does not serve it, the automatic rule). The counts are only looked at where the answer
-  // can be yes, i.e. where it is yes for the whole window.
+  // counts above 0 would (under schedule 4, whose kernel does not serve it, the automatic rule): adaptiveWaveChoice.
   WfCountsSummary adSum = { 0u, 0u, 0u };
   bool adaptWave = false;
-  if (adapt && c->adaptiveWavefront && useWavefront(c, false, false, false, job.tidCount)) {
-    if (adaptKnown) adSum = *adaptKnown; else if (int rc = adaptiveCountsSummary(c, job, st, adSum)) return rc;
-    adaptWave = useWavefront(c, false, false, false, adSum.active);
-  }
+  if (adapt) { if (int rc = adaptiveWaveChoice(c, job, st, adaptKnown, adSum, adaptWave)) return rc; }
   const bool waveCall = adapt ? adaptWave : (!streamCall && !inRays && useWavefront(c, naive, dr, stats && c->schedule != 2, job.tidCount));
   // schedule 3: the megakernel with block-local ray repacking (hpt_block.hip) - PathTrace and PathTraceDR on the BVH2 of either layout
   // automatic: gltf / emissive scenes (and PathTraceDR) whose rays walk a real tree - the test_228 class (SAH estimate 10: 696 -> 735 Mpaths/s at 1024^2,
@@ -2344,9 +2390,7 @@ static int launch_path_trace(hpt_ctx* c, Job& job, bool naive, bool dr, hipStrea
     return launch_stream(c, job, st);
   }
   if (waveCall) {
-    if (adapt && adSum.over != 0u)                             // (nothing of the caller's has been written: frame, generators and moments keep every bit)
-      return c->fail(HPT_ERR_ARG, "adaptive sampling under the wavefront schedule: " + std::to_string(adSum.over) + " pass count(s) above 16777215 (0xFFFFFF), all that a pool slot's "
-                                  "status word holds; split the call, or render it with hpt_set_option(\"adaptive_wavefront\", 0)");
+    if (adapt && adSum.over != 0u) return adaptiveOverRefusal(c, adSum);
     c->lastSchedule = 2; c->lastWide = (wfWide(c) && !c->instrument) ? 1u : 0u; c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
     if (adapt && adSum.maxCount == 0u) {                        // every count is 0: no round, nothing written
       c->lastWfIters = 0;
@@ -2576,12 +2620,14 @@ static int adaptivePlanLaunch(hpt_ctx* c, uint32_t tidBegin, uint32_t tidCount, 
 static uint adaptiveRoundBound(const hpt_adaptive_params* p) { return std::min(p->step, p->maxPasses); }
 static int adaptiveLoopCheck(hpt_ctx* c, uint32_t channels, const hpt_adaptive_params* p, uint32_t tidCount)
 {
-  if (c->adaptiveWavefront && useWavefront(c, false, false, false, tidCount) && (p->minPasses > WF_MAX_PASSES || adaptiveRoundBound(p) > WF_MAX_PASSES))
+  if (adaptiveWaveReachable(c, tidCount) && (p->minPasses > WF_MAX_PASSES || adaptiveRoundBound(p) > WF_MAX_PASSES))
     return c->fail(HPT_ERR_ARG, "PathTraceBlockAdaptive under the wavefront schedule: minPasses and min(step, maxPasses) must not exceed 16777215 (0xFFFFFF), all that a pool "
                                 "slot's status word holds; lower them, or render with hpt_set_option(\"adaptive_wavefront\", 0)");
   if (c->tidStride > 1) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockAdaptive: the loop plans one contiguous tid window; under hpt_set_tid_interleave with stride > 1 drive "
                                                             "hpt_path_trace_block_counts_dev and hpt_adaptive_plan_dev yourself, or reset the interleave");
-  if (int rc = adaptiveRefusal(c, false, false)) return rc;
+  if (int rc = adaptiveRefusal(c, false, false, channels)) return rc;
+  if (c->S.spectralMode != 0u && c->hasFilm && !c->filmTablesSpectral)      // (launch_path_trace's check, made here before the records are zeroed)
+    return c->fail(HPT_ERR_ARG, "thin film: m_precomp_thin_films was precomputed for RGB rendering (LoadScene sizes the tables by m_spectral_mode)");
   if (!c->sceneUploaded) return c->fail(HPT_ERR_STATE, "PathTraceBlockAdaptive before CommitDeviceData");
   if (c->dGens.n < (size_t)c->packedCount) return c->fail(HPT_ERR_STATE, "PathTraceBlockAdaptive: m_randomGens smaller than the thread range (InitRandomGens)");
   if (channels != 1u && channels != 3u && channels != 4u) return c->fail(HPT_ERR_UNSUPPORTED, "PathTraceBlockAdaptive: 1, 3 or 4 channels");
@@ -4154,6 +4200,7 @@ try {
   else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
   else if (k == "dr_environment") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_environment: 0 PathTraceDR / PathTraceVJP refuse scenes with an environment map or its sampling, 1 they render and differentiate them"); c->drEnvironment = value != 0; }
   else if (k == "adaptive_wavefront") { if (value > 1) return c->fail(HPT_ERR_ARG, "adaptive_wavefront: 0 adaptive calls run the megakernel, 1 they take the wavefront schedule where a PathTraceBlock of their active pixels would"); c->adaptiveWavefront = value != 0; }
+  else if (k == "adaptive_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "adaptive_spectral: 0 the adaptive calls refuse m_spectral_mode, 1 they run the spectral ADAPT kernels"); c->adaptiveSpectral = value != 0; }
   else if (k == "kmlt_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "kmlt_spectral: 0 PathTraceBlockKMLT and the primary-sample-space pass refuse m_spectral_mode, 1 they run the spectral MLT kernels"); c->kmltSpectral = value != 0; }
   else if (k == "kmlt_chains") { if (value < 1 || value > (1 << 28)) return c->fail(HPT_ERR_ARG, "kmlt_chains: 1 .. 2^28 Markov chains (chain c seeds RandomGenInit(7 c + 1))"); c->kmltChains = (uint)value; }
   else if (k == "force_full_materials") c->forceFull = value != 0;                     // diagnostic: never pick the lean (gltf + emissive) kernels

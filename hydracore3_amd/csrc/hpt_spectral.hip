@@ -507,6 +507,15 @@ HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3&
   }
 }
 
+// Adaptive sampling under m_spectral_mode (hpt_set_option "adaptive_spectral"; DESIGN.md 2.13, "Spectral form"): the sample kernel_ContributeToImage has
+// just added to the frame goes into the pixel's record - exposure * rgb after SpectralCamRespoceToRGB, or the one value of a one-channel frame,
+// through the RGB kernels' adaptSampleLuminance (hpt_device.h). Shared by the ADAPT instantiations of pathTraceSpectralKernel and wfShadeSpecKernel.
+HPT_DEV void adaptAddSpecSample(const DevScene& S, uint channels, V4 accum, V3 rgb, PixelMoments& m)
+{
+  const float y = adaptSampleLuminance(S, channels, v3(accum.x, accum.y, accum.z), rgb);
+  m.sumY = m.sumY + y; m.sumY2 = m.sumY2 + y * y; m.passes = m.passes + 1u; m.reserved = 0u;
+}
+
 // One thread per pixel of the call, its passes one after the other (the pixel's generator continues from pass to pass as in the RGB kernels).
 // SCOPE: what the scene needs (the host looks at the materials a hit can reach, the lights, the camera): 0 = what the reference's spectral fixtures
 // use (diffuse, conductor, plastic, dielectric, thin films, analytic lights, a sky spectrum); 1 = + gltf surfaces (legacy hydra_material scenes);
@@ -514,11 +523,18 @@ HPT_DEV void shadeVertexSpec(const DevScene& S, const HitRec& hit, V3& rpos, V3&
 // test_spectral 446 Mpaths/s in scope 0 against 322 with everything compiled in; the Cornell box under spectral mode 2153 in scope 1 against
 // 1488 in scope 2 (scopes 0 / 1 are built for 4 waves per SIMD, scope 2 for 3 - and once more for 4, template value 3, for scenes with few
 // material types: legacy_materials 1283 -> 1425, while typed_materials loses 6 % there).
-template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE_>
+// ADAPT (adaptive sampling, translation units of their own): a lane takes Job::passCounts[tid] passes (null: passNum); a pixel with count 0 is neither
+// loaded nor stored; every sample goes into the pixel's record Job::moments[tid] (null: no statistics), which waits in LDS beside the traversal
+// stack while the lane walks - the path state leaves no register for two sums held across the traversals. The host has refused input rays, the
+// naive integrator and wavelength layers for these instantiations (adaptiveRefusal), so they hold none of that code.
+template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE_, bool ADAPT>
 __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceSpectralKernel(const DevScene S, const Job job)
 {
   constexpr int SCOPE = SCOPE_ == 3 ? 2 : SCOPE_;                            // (3 = scope 2 built for 4 waves per SIMD: scenes with few material types)
-  __shared__ uint stackMem[LDS_STACK * 256];
+  constexpr int STACK_ROWS = (SWEEP && ADAPT) ? 0 : LDS_STACK;                // (the sweep walks no stack: its parents use no LDS at all, so the record's rows are the whole array there)
+  __shared__ uint stackMem[(STACK_ROWS + (ADAPT ? 3 : 0)) * 256];
+#define PIX_MOM(k)  stackMem[(STACK_ROWS + (k)) * 256 + threadIdx.x]         // ADAPT: bits of sumY, bits of sumY2, passes
+  const bool momentsOn = ADAPT && job.moments != nullptr;
   const uint glane = blockIdx.x * 256u + threadIdx.x;
   TravStack stk; stk.lds = &stackMem[threadIdx.x]; stk.ovf = job.stackOverflow + glane; stk.ovfStride = job.gridLanes;
   TravStats st; st.nodes = st.tris = st.insts = st.waveNodeIters = st.waveTriIters = 0;
@@ -529,12 +545,19 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   Rng gen; gen.sx = gen.sy = 0;
   uint XY = 0, pixel = 0;
   float pix[4] = { 0.0f, 0.0f, 0.0f, 0.0f };
-  const bool inRays = job.inRayPos != nullptr;                               // PathTraceFromInputRays (integrator_pt.cpp:159-199, 659-676, 761-798): the caller's rays and wavelengths, raw samples out
+  const bool inRays = !ADAPT && job.inRayPos != nullptr;                     // PathTraceFromInputRays (integrator_pt.cpp:159-199, 659-676, 761-798): the caller's rays and wavelengths, raw samples out
+  uint ownPasses = 0u;                                                       // ADAPT: the pixel's own count; 0 = the lane has no pixel
+  if constexpr (ADAPT) {
+    if (valid) { ownPasses = job.passCounts != nullptr ? job.passCounts[tid] : job.passNum; valid = ownPasses != 0u; }
+  }
   if (valid) {
     XY = inRays ? (tid < job.packedCount ? job.packedXY[tid] : 0u) : job.packedXY[tid]; gen = job.gens[tid];
     pixel = inRays ? tid : ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
     if (job.channels == 1) pix[0] = job.outColor[pixel];
     else if (job.channels <= 4) { const float* o = job.outColor + (size_t)pixel * job.channels; pix[0] = o[0]; pix[1] = o[1]; pix[2] = o[2]; if (inRays && job.channels == 4) pix[3] = o[3]; }
+    if constexpr (ADAPT) {
+      if (momentsOn) { const PixelMoments m = job.moments[tid]; PIX_MOM(0) = __float_as_uint(m.sumY); PIX_MOM(1) = __float_as_uint(m.sumY2); PIX_MOM(2) = m.passes; }
+    }
   }
   // In-place regeneration, as in the RGB megakernel but without its work queue: a lane whose path has ended starts its pixel's next pass at
   // the top of the loop instead of waiting for the longest path of the wave, so every trip traces a ray for (nearly) all lanes.
@@ -542,7 +565,7 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   V4 waves = v4s(0.0f), accum = v4s(0.0f), thr = v4s(1.0f);
   float misPdf = 1.0f, misIor = 1.0f;                                        // MisData: matSamplePdf, ior (the medium the ray travels in)
   float pathTime = 0.0f;                                                     // motion blur: the path's time (MOTION variants only)
-  uint flags = 0, bounce = 0, passesLeft = valid ? job.passNum : 0u;
+  uint flags = 0, bounce = 0, passesLeft = valid ? (ADAPT ? ownPasses : job.passNum) : 0u;
   bool alive = false;
   while (true) {
     if (!alive && passesLeft != 0u) {
@@ -564,7 +587,7 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
       alive = true;
     }
     if (!__any(alive)) break;
-    const bool naive = job.naive != 0u;                                      // NaivePathTrace (integrator_pt.cpp:681-717): no light sampling, one more bounce
+    const bool naive = !ADAPT && job.naive != 0u;                            // NaivePathTrace (integrator_pt.cpp:681-717): no light sampling, one more bounce
     const uint maxBounce = naive ? S.traceDepth + 1u : S.traceDepth;
     if (maxBounce != 0u) {                                                   // (depth 0: the path is its camera ray and ends below)
       HitRec hit; hit.inst = 0xFFFFFFFFu; hit.prim = 0; hit.t = 0; hit.u = hit.v = 0;
@@ -591,9 +614,10 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
         if (S.integratorType == INTEGRATOR_STUPID_PT) accum = thr * env; else accum = accum + thr * env;
       }
       // kernel_ContributeToImage (integrator_pt.cpp:598-657), spectral; input rays: kernel_CopyColorToOutput, the raw samples (:659-676)
+      V3 sampleRgb = v3(0, 0, 0);                                            // ADAPT: what the three-component branch adds, before the exposure
       if (inRays) { pix[0] += accum.x; pix[1] += accum.y; pix[2] += accum.z; pix[3] += accum.w; }
       else if (job.channels == 1) pix[0] += accum.x * S.exposureMult;
-      else if (job.channels > 4) {                                           // "always spectral rendering": one layer of W x H per wavelength bin
+      else if (!ADAPT && job.channels > 4) {                                 // "always spectral rendering": one layer of W x H per wavelength bin
         const V4 color = accum * S.exposureMult;
         for (int i = 0; i < 4; i++) {
           const float t = (comp(waves, i) - LAMBDA_MIN) / (LAMBDA_MAX - LAMBDA_MIN);
@@ -601,14 +625,25 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
           job.outColor[(size_t)channelId * (size_t)(S.winWidth * S.winHeight) + pixel] += comp(color, i);   // the pixel is this thread's alone
         }
       }
-      else { const V3 rgb = spectralCamResponseToRGB(S, accum, waves, flags); pix[0] += S.exposureMult * rgb.x; pix[1] += S.exposureMult * rgb.y; pix[2] += S.exposureMult * rgb.z; }
+      else { const V3 rgb = spectralCamResponseToRGB(S, accum, waves, flags); pix[0] += S.exposureMult * rgb.x; pix[1] += S.exposureMult * rgb.y; pix[2] += S.exposureMult * rgb.z; sampleRgb = rgb; }
+      if constexpr (ADAPT) {
+        if (momentsOn) {
+          PixelMoments m; m.sumY = __uint_as_float(PIX_MOM(0)); m.sumY2 = __uint_as_float(PIX_MOM(1)); m.passes = PIX_MOM(2);
+          adaptAddSpecSample(S, job.channels, accum, sampleRgb, m);
+          PIX_MOM(0) = __float_as_uint(m.sumY); PIX_MOM(1) = __float_as_uint(m.sumY2); PIX_MOM(2) = m.passes;
+        }
+      }
     }
   }
   if (valid) {
     if (job.channels == 1) job.outColor[pixel] = pix[0];
     else if (job.channels <= 4) { float* o = job.outColor + (size_t)pixel * job.channels; o[0] = pix[0]; o[1] = pix[1]; o[2] = pix[2]; if (inRays && job.channels == 4) o[3] = pix[3]; }
     job.gens[tid] = gen;
+    if constexpr (ADAPT) {
+      if (momentsOn) { PixelMoments m; m.sumY = __uint_as_float(PIX_MOM(0)); m.sumY2 = __uint_as_float(PIX_MOM(1)); m.passes = PIX_MOM(2); m.reserved = 0u; job.moments[tid] = m; }
+    }
   }
+#undef PIX_MOM
 }
 
 // ---- IntegratorQMC::PathTraceBlock under m_spectral_mode (mlt/integrator_qmc.cpp; `hydra --qmc --spectral`) ---------------------------------------
@@ -1014,7 +1049,9 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
 // the queue the shared trace kernel (hpt_wavefront.hip: wfTraceKernel, the 4-wide tree with ray replacement) drains. Four samples per radiance-valued word:
 // WfPool::thr / acc / contrib are used in full, the wavelengths and (flags, bounce) have arrays of their own. Same arithmetic in the same order as the
 // plain kernel: bit-identical frames (tests/test_gpu_spectral.py). PathTraceBlock only (no naive / input-ray / moving-instance variant: those keep their kernels).
-template <int SCOPE_>
+// ADAPT (adaptive sampling; the per-pixel pass counts are the slots' initial status, wfInitCountsKernel): each sample goes into WfJob::moments[tid] where it
+// is contributed - a slot's samples finish in pass order, so the sums are the plain kernel's bit for bit; no wavelength layers (adaptiveRefusal).
+template <int SCOPE_, bool ADAPT>
 __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) wfShadeSpecKernel(const DevScene S, const WfPool P, const WfJob job)
 {
   constexpr int SCOPE = SCOPE_ == 3 ? 2 : SCOPE_;
@@ -1075,8 +1112,9 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
       }
       // kernel_ContributeToImage (integrator_pt.cpp:598-657), spectral: the pixel is this slot's alone
       const uint pixel = ((XY & 0xFFFF0000u) >> 16) * (uint)S.winWidth + (XY & 0x0000FFFFu);
+      V3 sampleRgb = v3(0, 0, 0);                                            // ADAPT: what the three-component branch adds, before the exposure
       if (job.channels == 1) job.outColor[pixel] += accum.x * S.exposureMult;
-      else if (job.channels > 4) {
+      else if (!ADAPT && job.channels > 4) {
         const V4 color = accum * S.exposureMult;
         for (int i = 0; i < 4; i++) {
           const float t = (comp(waves, i) - LAMBDA_MIN) / (LAMBDA_MAX - LAMBDA_MIN);
@@ -1084,7 +1122,10 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
           job.outColor[(size_t)channelId * (size_t)(S.winWidth * S.winHeight) + pixel] += comp(color, i);
         }
       }
-      else { const V3 rgb = spectralCamResponseToRGB(S, accum, waves, flags); float* o = job.outColor + (size_t)pixel * job.channels; o[0] += S.exposureMult * rgb.x; o[1] += S.exposureMult * rgb.y; o[2] += S.exposureMult * rgb.z; }
+      else { const V3 rgb = spectralCamResponseToRGB(S, accum, waves, flags); float* o = job.outColor + (size_t)pixel * job.channels; o[0] += S.exposureMult * rgb.x; o[1] += S.exposureMult * rgb.y; o[2] += S.exposureMult * rgb.z; sampleRgb = rgb; }
+      if constexpr (ADAPT) {
+        if (job.moments != nullptr) { PixelMoments m = job.moments[tid]; adaptAddSpecSample(S, job.channels, accum, sampleRgb, m); job.moments[tid] = m; }
+      }
     }
     if (!alive && !ending && passes != 0u) {                                 // next pass of the pixel: GetRandomNumbersLens, then GetRandomNumbersSpec (integrator_pt.cpp:114-118)
       passes--;
@@ -1117,7 +1158,8 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
 }
 
 // one translation unit per scope (-DHPT_SPEC_INST=1 / 2 / 3 / 4: scope 0 / 1 / 2 / 2 at 4 waves; 5 / 6 / 7 / 8: the QMC kernel of those scopes;
-// 9 / 10 / 11 / 12: the primary-sample-space pass and the MLT chains of those scopes; 0: all), see __graft_entry__.build
+// 9 / 10 / 11 / 12: the primary-sample-space pass and the MLT chains of those scopes; 13 / 14 / 15 / 16: the ADAPT kernels of those scopes, both
+// schedules; 0: all), see __graft_entry__.build
 #ifndef HPT_SPEC_INST
 #define HPT_SPEC_INST 0
 #endif
@@ -1138,6 +1180,16 @@ __global__ void __launch_bounds__(256, SCOPE_ == 2 ? HPT_SPEC_WIDE_WAVES : HPT_S
   template __global__ void pathTraceSpectralKernel<true,  false, false, true,  SCOPE>(const DevScene, const Job); \
   template __global__ void pathTraceSpectralKernel<false, true,  false, true,  SCOPE>(const DevScene, const Job); \
   template __global__ void pathTraceSpectralKernel<true,  true,  false, true,  SCOPE>(const DevScene, const Job);
+#define HPT_SPEC_ADAPT(SCOPE)   /* adaptive sampling: the same traversal variants with per-pixel pass counts and moments */ \
+  template __global__ void pathTraceSpectralKernel<false, false, false, false, SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<true,  false, false, false, SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<false, true,  false, false, SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<true,  true,  false, false, SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<false, false, true,  false, SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<false, false, false, true,  SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<true,  false, false, true,  SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<false, true,  false, true,  SCOPE, true>(const DevScene, const Job); \
+  template __global__ void pathTraceSpectralKernel<true,  true,  false, true,  SCOPE, true>(const DevScene, const Job);
 #define HPT_SPEC_QMC(SCOPE)   /* the traversal variants of HPT_SPEC: DEEP x FLAT, SWEEP, MOTION */ \
   template __global__ void pathTraceQmcSpectralKernel<false, false, false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
   template __global__ void pathTraceQmcSpectralKernel<true,  false, false, false, SCOPE>(const DevScene, const Job, const QmcJob); \
@@ -1180,6 +1232,21 @@ HPT_SPEC_QMC(2)
 #endif
 #if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 8
 HPT_SPEC_QMC(3)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 13
+HPT_SPEC_ADAPT(0)
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 14
+HPT_SPEC_ADAPT(1)
+template __global__ void wfShadeSpecKernel<1, true>(const DevScene, const WfPool, const WfJob);
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 15
+HPT_SPEC_ADAPT(2)
+template __global__ void wfShadeSpecKernel<2, true>(const DevScene, const WfPool, const WfJob);
+#endif
+#if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 16
+HPT_SPEC_ADAPT(3)
+template __global__ void wfShadeSpecKernel<3, true>(const DevScene, const WfPool, const WfJob);
 #endif
 #if HPT_SPEC_INST == 0 || HPT_SPEC_INST == 1
 HPT_SPEC(0)

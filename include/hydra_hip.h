@@ -708,8 +708,20 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               counts its array on the device first (12 bytes read back before anything is written); the loop decides per round from its
  *               own plan. A pool slot holds 24 bits of passes: a call that would run the wavefront form with a count above 16777215 (0xFFFFFF),
  *               and a loop whose minPasses or min(step, maxPasses) exceeds it, return HPT_ERR_ARG and write nothing. Counts that are all 0
- *               return HPT_OK and write nothing. What adaptive sampling refuses (spectral mode, thin films, the naive integrator, input rays,
- *               the instrumented probe) it refuses under either value. Any other value: HPT_ERR_ARG.
+ *               return HPT_OK and write nothing. What adaptive sampling refuses (spectral mode without "adaptive_spectral", thin films in RGB
+ *               scenes, the naive integrator, input rays, the instrumented probe) it refuses under either value. Any other value: HPT_ERR_ARG.
+ * Adaptive sampling under m_spectral_mode (off by default, as "qmc_spectral" and "kmlt_spectral" are):
+ *   "adaptive_spectral"  0 (default): hpt_path_trace_block_counts[_dev] and hpt_path_trace_block_adaptive[_dev] refuse a context in spectral mode
+ *               (HPT_ERR_UNSUPPORTED, nothing written). 1: they are served there, thin-film, dispersive and moving-instance scenes included: a pixel
+ *               given k passes ends, frame and m_randomGens, bit for bit as a uniform spectral hpt_path_trace_block of k passes leaves it, a
+ *               pixel with count 0 keeps every bit, and a record receives per sample the Rec. 709 luminance of the three values added to the
+ *               frame (exposure * rgb after the camera response; the one value added with channels == 1), f32 in pass order.
+ *               hpt_adaptive_plan / _resolve / _variance and hpt_denoise_frame_var read such records as they read RGB ones. The calls run the
+ *               one-thread-per-pixel spectral kernel whatever hpt_set_schedule says (hpt_get_last_launch: schedule 1); with "adaptive_wavefront" 1
+ *               as well they take the wavefront schedule under the rule stated there, where the spectral wavefront kernels apply (no moving
+ *               instances, no sweep layout, trace depth above 0), with the same 24-bit limit and the same bits. Still HPT_ERR_UNSUPPORTED with
+ *               nothing written: the naive integrator, input rays, the instrumented probe, channels > 4 (a moment over wavelength layers
+ *               has no definition) and thin films in an RGB scene. Any other value: HPT_ERR_ARG.
  * Diagnostic switches (these DO change which kernels run or what they compute; never set in production):
  *   "dr_skip_nonfinite"     PathTraceDR: 1 = a sample whose radiance is not finite contributes neither colour, loss nor gradient (what an
  *                           optimisation loop wants: one NaN poisons Adam's moments for good); 0 (default) = PixelLossPT as the reference
