@@ -918,7 +918,11 @@ class HipIntegrator:
         "adaptive_spectral": 0 (default) the adaptive calls refuse a spectral context; 1 they are served there (thin films, dispersion and moving instances
         included; 1, 3 or 4 channels, no wavelength layers): a pixel given k passes is a uniform spectral PathTraceBlock pixel of k passes bit for bit, and
         the records take the luminance of what each sample adds to the frame, so AdaptivePlan, AdaptiveResolve, AdaptiveVariance and denoise_var work on
-        them unchanged. Together with "adaptive_wavefront" such calls take the wavefront schedule under the same rule."""
+        them unchanged. Together with "adaptive_wavefront" such calls take the wavefront schedule under the same rule.
+        "qmc_wavefront": 0 (default) PathTraceBlockQMC / render_qmc (and PathTraceBlockKMLT's FB_DIRECT forward) run the megakernel; 1 the call goes to
+        the wavefront schedule where a PathTraceBlock of as many pixels as it has generator slots with work would (set_schedule). Sample records and
+        generators are the same bit for bit; spectral, sweep-layout, thin-film, depth-0 and instrumented calls keep the megakernel; a call whose slot 0
+        would run more than 0xFFFFFF samples is refused there."""
         self._chk(self.L.hpt_set_option(self.h, name.encode(), value))
         if name == "qmc_spectral":
             self._qmc_spectral = bool(value)     # PathTraceBlockQMC then takes frames of more than 4 channels

@@ -338,6 +338,13 @@ struct QmcRands
 // the stack overflow area and tidCount = min(N, S) generator slots with work
 template <bool DEEP, bool FLAT, bool MOTION, bool SWEEP>
 __global__ void __launch_bounds__(256, HPT_FILM_WAVES) pathTraceQmcKernel(const DevScene S, const Job job, const QmcJob q);
+// The same sample loop under the wavefront schedule (hpt_wavefront.hip; hpt_set_option "qmc_wavefront"): pool slot s of the launch serves generator
+// slot itemBase + s. wfInitQmcKernel gives it its number of samples, (samples - 1 - slot) / gensCount + 1 <= WF_MAX_PASSES, as its pass count;
+// wfShadeQmcKernel is wfShadeKernel's pass with pathTraceQmcKernel's sample start, QmcRands and path end (RGB without thin films, traceDepth > 0;
+// packedCount: entries of WfJob::packedXY, read for the camera back plate only). MOTION: moving instances.
+__global__ void __launch_bounds__(256) wfInitQmcKernel(WfPool P, uint itemBase, uint itemCount, uint samples, uint gensCount);
+template <bool MOTION>
+__global__ void __launch_bounds__(256, HPT_WF_SHADE_FULL_WAVES) wfShadeQmcKernel(const DevScene S, const WfPool P, const WfJob job, const QmcJob q, const uint packedCount);
 // the same sample loop on four wavelengths per path (hpt_spectral.hip); SCOPE and its launch bounds as pathTraceSpectralKernel
 template <bool DEEP, bool FLAT, bool SWEEP, bool MOTION, int SCOPE>
 __global__ void __launch_bounds__(256, SCOPE == 2 ? HPT_SPEC_WIDE_WAVES : HPT_SPEC_WAVES) pathTraceQmcSpectralKernel(const DevScene S, const Job job, const QmcJob q);

@@ -193,6 +193,7 @@ struct hpt_ctx
   // PathTraceBlockKMLT (hpt_kmlt.hip): the chains' current and proposed vectors [slot][chain], the per-chain sums, the four statistics
   DevBuf<float> dKmltCur, dKmltProp; DevBuf<double> dKmltAccum, dKmltStats; DevBuf<uint> dKmltLarge, dKmltAccept;
   bool qmcSpectral = false;                              // hpt_set_option("qmc_spectral", 1): PathTraceBlockQMC serves m_spectral_mode (pathTraceQmcSpectralKernel) instead of refusing it
+  bool qmcWavefront = false;                             // hpt_set_option("qmc_wavefront", 1): PathTraceBlockQMC takes the wavefront schedule (wfShadeQmcKernel) where a PathTraceBlock of as many pixels as it has generator slots would
   bool kmltSpectral = false;                             // hpt_set_option("kmlt_spectral", 1): PathTraceBlockKMLT and the PSS pass serve m_spectral_mode (kmltChainSpectralKernel / pathTracePssSpectralKernel)
   uint kmltChains = 0;                                   // hpt_set_option("kmlt_chains", n): 0 = one chain per lane of the resident grid
   uint kmltLastChains = 0;                               // chains of the last PathTraceBlockKMLT call: whose sums a normalise-only call reads
@@ -1950,16 +1951,23 @@ static bool drEnvReads(const hpt_ctx* c, uint texId)
 }
 // adaptMax: null, or the adaptive call's largest pass count (1 .. WF_MAX_PASSES, from the counts summary or the loop's bound): Job::passCounts /
 // moments are set, the slots start with their own counts (wfInitCountsKernel) and the ADAPT shade kernels run
-static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1, const uint* adaptMax = nullptr)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
+// qmc: null, or PathTraceBlockQMC's job ("qmc_wavefront"; hpt_path_trace_qmc_block_dev2 has made the refusals): the work items are the generator slots
+// 0 .. job.tidCount, each starting with its own number of samples (wfInitQmcKernel), and wfShadeQmcKernel runs
+static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr, int specScope = -1, const uint* adaptMax = nullptr, const QmcJob* qmc = nullptr)   // specScope >= 0: spectral rendering (wfShadeSpecKernel<scope>)
 {
   const bool adapt = adaptMax != nullptr;                       // (forward calls from the camera, RGB without thin films or spectral: adaptiveRefusal)
   const bool spec = specScope >= 0;
   const bool drEnv = dr && drEnvironmentCall(c);               // (launch_path_trace has made the refusals)
   const bool envPlane = drEnv && drEnvMapRegistered(c);
   DevScene Sw = c->S;
-  if (spec) Sw.shadeTris = nullptr;                  // the spectral shade kernel fetches its surface through the primitive id: the trace pass must report that
+  if (spec || qmc) Sw.shadeTris = nullptr;           // the spectral and the QMC shade kernels fetch their surface through the primitive id: the trace pass must report that
+  const uint passesMax = qmc ? (qmc->samples - 1u) / qmc->gensCount + 1u : (adapt ? *adaptMax : job.passNum);   // the largest pass count of a slot
   auto launchShade = [&](const dim3 sg, hipStream_t gs, const WfPool& P, const WfJob& wj) {
-    if (spec && adapt) {
+    if (qmc) {
+      if (c->S.motion) wfShadeQmcKernel<true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj, *qmc, job.packedCount);
+      else             wfShadeQmcKernel<false><<<sg, dim3(256), 0, gs>>>(Sw, P, wj, *qmc, job.packedCount);
+    }
+    else if (spec && adapt) {
       if (specScope == 3) wfShadeSpecKernel<3, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else if (specScope == 2) wfShadeSpecKernel<2, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
       else wfShadeSpecKernel<1, true><<<sg, dim3(256), 0, gs>>>(Sw, P, wj);
@@ -2021,7 +2029,7 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
   // every path takes at most traceDepth shade passes after the one that generated it; the pass that ends it (or the next one, when a
   // shadow ray was outstanding) also generates the pixel's next path
   // safety net only (the loop ends when a round queues no ray): pixels whose rays were suspended sit rounds out, so there is no tight bound
-  const unsigned long long iterCap = c->wfIterCap ? c->wfIterCap : 64ull * ((unsigned long long)(adapt ? *adaptMax : job.passNum) * (c->S.traceDepth + 2ull) + 4ull);
+  const unsigned long long iterCap = c->wfIterCap ? c->wfIterCap : 64ull * ((unsigned long long)passesMax * (c->S.traceDepth + 2ull) + 4ull);
   c->lastWfIters = 0;
   unsigned long long capLeft = 0;                  // rays still queued when a group ran into iterCap
   const bool drLoss = dr && job.vjp == 0u;                  // (PathTraceVJP computes no loss: the slots stay zero and are not reduced)
@@ -2056,7 +2064,8 @@ static int launch_wavefront(hpt_ctx* c, const Job& job, hipStream_t st, bool dr,
     P.susp[0] = g.u[7].p; P.susp[1] = g.u[8].p; P.maxSusp = (uint)maxSusp; P.suspStack = wfStackNeeded(c);
     HIPCHK(c, hipStreamWaitEvent(g.stream, c->wfFork, 0));
     HIPCHK(c, hipMemsetAsync(P.ctr, 0, 2 * WF_CTR_WORDS * sizeof(uint), g.stream));
-    if (adapt) { wj.itemBase = g.itemBase; wj.itemCount = g.itemCount; wfInitCountsKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, wj); }
+    if (qmc) wfInitQmcKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, g.itemBase, g.itemCount, qmc->samples, qmc->gensCount);
+    else if (adapt) { wj.itemBase = g.itemBase; wj.itemCount = g.itemCount; wfInitCountsKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, wj); }
     else wfInitKernel<<<dim3((g.itemCount + 255u) / 256u), dim3(256), 0, g.stream>>>(P, g.itemCount, job.passNum);
   }
   // ---- rounds: one shade + trace pass per live group, groups interleaved so that their kernels overlap on the device ----
@@ -3497,6 +3506,16 @@ try {
   hipStream_t st = (hipStream_t)stream;
   const uint32_t samples = hpt_qmc_sample_count(pixelsNum, passNum);
   if (samples == 0u) return HPT_OK;
+  // "qmc_wavefront" ("Wavefront form"): the generator slots with work are the pool's slots, so the call goes where a PathTraceBlock of
+  // that many pixels would; what wfShadeQmcKernel does not serve keeps the megakernel. A slot's samples are its pass count in the status word: more
+  // than that holds is refused here, before the table, the queue, the frame, the records or a generator is touched.
+  const uint slots = std::min(c->gensCount, samples);
+  const bool wave = c->qmcWavefront && c->S.spectralMode == 0u && c->S.sweep == 0u && !c->hasFilm && c->S.traceDepth > 0u && !c->instrument &&
+                    useWavefront(c, false, false, false, slots);
+  if (wave && (samples - 1u) / c->gensCount + 1u > WF_MAX_PASSES)
+    return c->fail(HPT_ERR_ARG, "PathTraceBlockQMC under the wavefront schedule: generator slot 0 would run " + std::to_string((samples - 1u) / c->gensCount + 1u) +
+                                " samples, above 16777215 (0xFFFFFF), all that a pool slot's status word holds; use more generators, split the call, or render it with "
+                                "hpt_set_option(\"qmc_wavefront\", 0)");
   if (c->dQmcTable.n == 0) {                                               // qmc::init in IntegratorQMC's constructor
     uint32_t table[341];
     hpt_qmc::buildTable(table);
@@ -3514,6 +3533,12 @@ try {
   Job job; std::memset(&job, 0, sizeof(job));
   job.tidCount = std::min(n, samples); job.passNum = passNum; job.channels = channels; job.outColor = outDev;
   job.gens = c->dGens.p; job.packedXY = c->dPackedXY.p; job.packedCount = c->packedCount;
+  if (wave) {                                                              // work item k is generator slot k: one contiguous window
+    job.tidBegin = 0u; job.tidChunk = 0x40000000u; job.tidStride = 1u; job.tidEnd = job.tidCount;
+    c->lastSchedule = 2; c->lastShadeRecords = 0u; c->lastWide = wfWide(c) ? 1u : 0u;
+    c->lastDeep = (c->lastWide ? c->stackNeeded4 : c->stackNeeded) > (uint)LDS_STACK ? 1u : 0u;
+    return launch_wavefront(c, job, st, false, -1, nullptr, &q);
+  }
   const int scope = spectral ? spectralScope(c) : 0;
   const int grid = !spectral ? gridBlocks(c, false, true) : spectralGridBlocks(c, scope);
   const int blocks = (int)std::min<size_t>((size_t)grid, ((size_t)job.tidCount + 255) / 256);
@@ -4198,6 +4223,7 @@ try {
   else if (k == "device_build_quality") { if (value > 4) return c->fail(HPT_ERR_ARG, "device_build_quality: 0 the plain linear BVH, 1..4 treelet restructuring passes of every device build"); c->deviceBuildQuality = value; c->accelCommitted = false; c->flatRefittable = c->tlUpdatable = false; }
   else if (k == "wide_nodes") { c->wideEnabled = value != 0; c->S.megaWide = (c->wideEnabled && c->nodes4Count != 0u && c->S.flatMode != 0u && c->sahVisits >= HEAVY_SAH_VISITS) ? 1u : 0u; }   // both users of the tree, at once                             // 0: the wavefront trace kernel walks the BVH2 instead of the 4-wide compressed tree (A/B, diagnosis)
   else if (k == "qmc_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "qmc_spectral: 0 PathTraceBlockQMC refuses m_spectral_mode, 1 it runs the spectral QMC kernel"); c->qmcSpectral = value != 0; }
+  else if (k == "qmc_wavefront") { if (value < 0 || value > 1) return c->fail(HPT_ERR_ARG, "qmc_wavefront: 0 PathTraceBlockQMC runs the megakernel, 1 it takes the wavefront schedule where a PathTraceBlock of as many pixels as it has generator slots would"); c->qmcWavefront = value != 0; }
   else if (k == "dr_environment") { if (value > 1) return c->fail(HPT_ERR_ARG, "dr_environment: 0 PathTraceDR / PathTraceVJP refuse scenes with an environment map or its sampling, 1 they render and differentiate them"); c->drEnvironment = value != 0; }
   else if (k == "adaptive_wavefront") { if (value > 1) return c->fail(HPT_ERR_ARG, "adaptive_wavefront: 0 adaptive calls run the megakernel, 1 they take the wavefront schedule where a PathTraceBlock of their active pixels would"); c->adaptiveWavefront = value != 0; }
   else if (k == "adaptive_spectral") { if (value > 1) return c->fail(HPT_ERR_ARG, "adaptive_spectral: 0 the adaptive calls refuse m_spectral_mode, 1 they run the spectral ADAPT kernels"); c->adaptiveSpectral = value != 0; }

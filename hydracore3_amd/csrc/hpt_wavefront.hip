@@ -24,12 +24,13 @@
 // Adaptive sampling ("Wavefront form"): the passes left already live per slot (status >> 8), so a per-pixel pass count is the
 // slot's initial status (wfInitCountsKernel) and a slot with none is never active; wfShadeKernel<.., ADAPT> adds each sample's luminance to the
 // pixel's moments where it contributes the sample; wfCountsSummaryKernel tells the host what it must know of the counts beforehand.
+// QMC path tracing ("Wavefront form"): wfShadeQmcKernel is pathTraceQmcKernel's per-sample step on a pool of generator slots.
 #include <hip/hip_runtime.h>
 #include "hpt_decl.h"
 
 namespace hpt {
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5)      // (small kernels: emitted once, with the shade kernels)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5 && HPT_WF_INST != 6 && HPT_WF_INST != 7)      // (small kernels: emitted once, with the shade kernels)
 __global__ void wfInitKernel(WfPool P, uint n, uint passNum)
 {
   const uint i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -260,7 +261,7 @@ __global__ void HPT_WFS_BOUNDS(DR, LEAN) wfShadeKernel(const DevScene S, const W
   if (LGRAD) drLightFlush(lightBins, job.grad, lightReg);
 }
 
-#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5)
+#if !defined(HPT_WF_INST) || (HPT_WF_INST != 2 && HPT_WF_INST != 3 && HPT_WF_INST != 4 && HPT_WF_INST != 5 && HPT_WF_INST != 6 && HPT_WF_INST != 7)
 // DR: sum of the per-slot losses in double, one atomic per block; wfLossFinishKernel adds the total to the caller's float
 __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot, uint n, double* acc)
 {
@@ -274,6 +275,134 @@ __global__ void __launch_bounds__(256) wfLossReduceKernel(const float* lossSlot,
 }
 __global__ void wfLossFinishKernel(const double* acc, float* loss) { *loss += (float)*acc; }
 #endif
+
+// ---- QMC path tracing (hpt_set_option "qmc_wavefront"; DESIGN.md 2.8, "Wavefront form") ------------------------------------------------------
+// pathTraceQmcKernel (hpt_qmc.hip) laid over wfShadeKernel: a pool slot is a GENERATOR SLOT g = itemBase + s < min(N, S), not a pixel. Its passes
+// are its samples g, g + N, g + 2N, ... < S, run in that order on the one generator, so the status word's count is the slot's number of samples
+// (wfInitQmcKernel) and the sample in flight follows from the count: with `last` = (S - 1 - g) / N, the samples of the slot less one, and `passes`
+// samples still to start, it is g + (last - passes) * N <= S - 1 - no sum is formed that could pass 2^32, as with the megakernel's `more` test.
+// The pixel is a function of the sample index alone (dimensions 0 and 1) and is recomputed where the path ends; nothing but WfPool is kept per slot.
+#if !defined(HPT_WF_INST) || HPT_WF_INST == 0 || HPT_WF_INST == 6
+__global__ void __launch_bounds__(256) wfInitQmcKernel(WfPool P, uint itemBase, uint itemCount, uint samples, uint gensCount)
+{
+  const uint s = blockIdx.x * 256u + threadIdx.x;
+  if (s >= itemCount) return;
+  P.status[s] = ((samples - 1u - (itemBase + s)) / gensCount + 1u) << 8;     // (the host has refused a call whose slot 0 has more than WF_MAX_PASSES)
+  P.inflight[s] = 0u;
+}
+#endif
+
+template <bool MOTION>
+__global__ void __launch_bounds__(256, HPT_WF_SHADE_FULL_WAVES) wfShadeQmcKernel(const DevScene S, const WfPool P, const WfJob job, const QmcJob q, const uint packedCount)
+{
+  const uint s = blockIdx.x * 256u + threadIdx.x;
+  uint* ctr = P.ctr + WF_CTR_WORDS * (job.iter & 1u);
+  if (s <= WF_RANGES) P.ctr[WF_CTR_WORDS * ((job.iter + 1u) & 1u) + 32u * s] = 0u;   // counters of the NEXT round (its trace pass is long done)
+
+  bool valid = s < job.itemCount;
+  const uint g = job.itemBase + s;                                          // the generator slot (< min(N, S) where valid)
+  if (valid && ldP(&P.inflight[s]) != 0u) valid = false;                   // a suspended ray of this slot is still being traced: it sits this round out
+  const uint st = valid ? ldP(&P.status[s]) : 0u;
+  uint passes = st >> 8;
+  bool alive = (st & WF_ALIVE) != 0u, pend = (st & WF_PEND) != 0u, ending = (st & WF_ENDING) != 0u;
+  const bool active = valid && (alive || pend || ending || passes != 0u);
+  bool wantShadow = false;
+
+  if (active) {
+    Rng gen = ldP(&job.gens[g]);
+    const uint last = (q.samples - 1u - g) / q.gensCount;
+    uint smp = (alive || ending) ? g + (last - passes) * q.gensCount : 0u;  // the sample in flight
+    V3 accum = v3(0, 0, 0), thr = v3(1, 1, 1), rpos = v3(0, 0, 0), rdir = v3(0, 0, 1);
+    float misPdf = 1.0f, misIor = 1.0f; uint flags = 0, bounce = 0;
+    float pathTime = 0.0f;
+    if (MOTION && alive) pathTime = ldP(&P.time[s]);
+    if (alive || ending) { const float4 a = ldP(&P.acc[s]); accum = v3(a.x, a.y, a.z); bounce = __float_as_uint(a.w); }
+    // (6) the shadow ray traced since the last visit: add the candidate contribution in the megakernel's order
+    if (pend) {
+      if (ldP(&P.occl[s]) == 0u) { const float4 c = ldP(&P.contrib[s]); accum = accum + v3(c.x, c.y, c.z); }
+      pend = false;
+    }
+    bool finalize = ending;                                                // path ended last time, only its shadow ray was outstanding
+    ending = false;
+    V3 shPos = v3(0, 0, 0), shDir = v3(0, 0, 1), contrib = v3(0, 0, 0); float shFar = 0.0f;
+
+    if (alive) {                                                             // (5) surface, light sample, BSDF sample
+      const float4 ro = ldP(&P.rayO[s]), rd = ldP(&P.rayD[s]), t4 = ldP(&P.thr[s]), h4 = ldP(&P.hit[s]);
+      rpos = v3(ro.x, ro.y, ro.z); misPdf = ro.w; rdir = v3(rd.x, rd.y, rd.z); misIor = rd.w;
+      thr = v3(t4.x, t4.y, t4.z); flags = __float_as_uint(t4.w);
+      HitRec hit; hit.t = h4.x; hit.u = h4.y; hit.v = h4.z; hit.prim = __float_as_uint(h4.w); hit.inst = ldP(&P.hitInst[s]);
+      V3 recA, recS, recdA, recdS, tailR; Taps recTaps; uint recTex = 0xFFFFFFFFu;       // (the DR record: unused here)
+      QmcRands rs; rs.table = q.table; rs.s = smp; rs.matDim = q.matDim; rs.lgtDim = q.lgtDim;
+      const bool didBounce = shadeVertex<false, false, false, MOTION, false, QmcRands>(S, nullptr, hit, rpos, rdir, accum, thr, misPdf, misIor, flags, bounce, gen,
+                                                                                    wantShadow, shPos, shDir, shFar, contrib, recA, recS, recdA, recdS, recTaps, recTex, tailR, pathTime, rs);
+      if (didBounce) bounce++;
+      if ((flags & RAY_FLAG_IS_DEAD) != 0 || bounce >= S.traceDepth) {
+        // (7) kernel_HitEnvironment: a ray that left the scene has no shadow ray outstanding, so the term is added here, after every contribution.
+        // The camera back plate reads m_packedXY[tid] with tid = the sample index; past the vector's end: 0
+        if ((flags & RAY_FLAG_OUT_OF_SCENE) != 0) {
+          const uint backXY = (S.envCamBackId != 0xFFFFFFFFu && smp < packedCount) ? job.packedXY[smp] : 0u;
+          const V3 env = environmentRadiance(S, rdir, misPdf, flags, backXY);
+          if (S.integratorType == INTEGRATOR_STUPID_PT) accum = thr * env; else accum = accum + thr * env;
+        }
+        alive = false;
+        if (wantShadow) ending = true; else finalize = true;
+      }
+    }
+    if (finalize) {                                                          // IntegratorQMC::kernel_ContributeToImage
+      (void)rng_float4(gen);                                               // GetRandomNumbersLens once more before *gen is stored (integrator_qmc.cpp:225-226)
+      const V3 c = accum * ld3(S.camRespoceRGB);
+      const V3 rgb = v3(S.exposureMult * c.x, S.exposureMult * c.y, S.exposureMult * c.z);
+      const float mono = 0.2126f * rgb.x + 0.7152f * rgb.y + 0.0722f * rgb.z;
+      uint x = (uint)(qmcFloat(q.table, smp, 0u) * float(S.winWidth)), y = (uint)(qmcFloat(q.table, smp, 1u) * float(S.winHeight));   // the pixel, as step (3) derived it
+      if (x >= (uint)(S.winWidth - 1)) x = (uint)(S.winWidth - 1);
+      if (y >= (uint)(S.winHeight - 1)) y = (uint)(S.winHeight - 1);
+      const uint pixel = y * (uint)S.winWidth + x;
+      if (job.outColor != nullptr) {
+        if (job.channels == 1u) atomicAdd(job.outColor + pixel, mono);
+        else {
+          float* o = job.outColor + (size_t)pixel * job.channels;
+          atomicAdd(o + 0, rgb.x); atomicAdd(o + 1, rgb.y); atomicAdd(o + 2, rgb.z);
+        }
+      }
+      if (q.sampleColor != nullptr) {
+        q.sampleColor[smp] = (job.channels == 1u) ? make_float4(mono, 0.0f, 0.0f, 0.0f) : make_float4(rgb.x, rgb.y, rgb.z, 0.0f);
+        q.samplePixel[smp] = pixel;
+      }
+    }
+    if (!alive && !ending && passes != 0u) {                                 // (3) the slot's next sample (kernel_InitEyeRay2 with IntegratorQMC::SampleCameraRay)
+      passes--;
+      smp = g + (last - passes) * q.gensCount;
+      accum = v3(0, 0, 0); thr = v3(1, 1, 1); flags = 0; bounce = 0; misPdf = 1.0f; misIor = 1.0f;
+      V4 lens = rng_float4(gen);                                           // GetRandomNumbersLens: the pseudo float4 first, then the overwrites
+      lens.x = qmcFloat(q.table, smp, 0u);
+      lens.y = qmcFloat(q.table, smp, 1u);
+      if ((S.camLensRadius > 0.0f || S.lensCount != 0u) && q.dofDim != 0u) { lens.z = qmcFloat(q.table, smp, 2u); lens.w = qmcFloat(q.table, smp, 3u); }
+      cameraRayAt<true>(S, lens.x, lens.y, lens, rpos, rdir);
+      if (MOTION) { pathTime = (q.motionDim != 0u) ? qmcFloat(q.table, smp, q.motionDim) : rng_float1(gen); stP(&P.time[s], pathTime); }   // GetRandomNumbersTime
+      alive = true;
+    }
+    stP(&job.gens[g], gen);
+    if (alive) {
+      stP(&P.rayO[s], make_float4(rpos.x, rpos.y, rpos.z, misPdf));
+      stP(&P.rayD[s], make_float4(rdir.x, rdir.y, rdir.z, misIor));
+      stP(&P.thr[s], make_float4(thr.x, thr.y, thr.z, __uint_as_float(flags)));
+    }
+    if (alive || ending) stP(&P.acc[s], make_float4(accum.x, accum.y, accum.z, __uint_as_float(bounce)));
+    if (wantShadow) {
+      stP(&P.shO[s], make_float4(shPos.x, shPos.y, shPos.z, shFar));
+      stP(&P.shD[s], make_float4(shDir.x, shDir.y, shDir.z, 0.0f));
+      stP(&P.contrib[s], make_float4(contrib.x, contrib.y, contrib.z, 0.0f));
+    }
+    stP(&P.status[s], (passes << 8) | (alive ? WF_ALIVE : 0u) | (wantShadow ? WF_PEND : 0u) | (ending ? WF_ENDING : 0u));
+  }
+  // ray compaction: ballot + prefix sum, one atomic per block
+  const bool qNear = active && alive, qShad = active && wantShadow;
+  uint kn, ks;
+  blockAppend(&ctr[0], qNear, qShad, kn, ks);
+  uint* rayQ = P.rayQ[job.iter & 1u];
+  if (qNear) stP(&rayQ[kn], s);
+  if (qShad) stP(&rayQ[ks], s | 0x80000000u);
+}
 
 // ---- persistent traversal with ray replacement -------------------------------------------------------------------------------
 #ifndef HPT_WF_XCD_RANGES
@@ -531,7 +660,7 @@ __global__ void __launch_bounds__(256, HPT_WF_WAVES) wfTraceKernel(const DevScen
 
 // ---- explicit instantiations (the host launches them through the declarations in hpt_decl.h) -----------------------------------------------
 #ifndef HPT_WF_INST
-#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients; 4: the shade kernel over environment maps; 5: the shade kernels of adaptive sampling
+#define HPT_WF_INST 0          // 0: everything in one translation unit; 1: shade kernels only; 2: trace kernels only; 3: the shade kernel with light-colour gradients; 4: the shade kernel over environment maps; 5: the shade kernels of adaptive sampling; 6 / 7: the shade kernels of QMC path tracing
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 5
 // adaptive sampling (hpt_set_option "adaptive_wavefront"): the three forward kernels an adaptive call can reach
@@ -552,6 +681,13 @@ template __global__ void wfShadeKernel<true, true, false, false, true>(const Dev
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 4
 template __global__ void wfShadeKernel<true, true, false, false, false, true>(const DevScene, const WfPool, const WfJob);   // environment maps in DR (hpt_set_option "dr_environment")
+#endif
+// QMC path tracing (hpt_set_option "qmc_wavefront"): every BSDF branch (6, with wfInitQmcKernel) and moving instances (7)
+#if HPT_WF_INST == 0 || HPT_WF_INST == 6
+template __global__ void wfShadeQmcKernel<false>(const DevScene, const WfPool, const WfJob, const QmcJob, const uint);
+#endif
+#if HPT_WF_INST == 0 || HPT_WF_INST == 7
+template __global__ void wfShadeQmcKernel<true>(const DevScene, const WfPool, const WfJob, const QmcJob, const uint);
 #endif
 #if HPT_WF_INST == 0 || HPT_WF_INST == 2
 #define HPT_WFT(DEEP, FLAT, STATS) template __global__ void wfTraceKernel<DEEP, FLAT, STATS>(const DevScene, const WfPool, uint, uint, uint, uint*, uint, Counters*);

@@ -402,7 +402,8 @@ int  hpt_qmc_layout(int dof, int spectral, int motion, uint32_t out[5]);
  * Samples s, s + N, s + 2N ... run in that order on generator s % N (what the reference computes on one thread: DESIGN.md 7); the sum
  * into a pixel is made with float atomics, so the frame is reproducible to rounding only. HPT_ERR_UNSUPPORTED for channels 2 and,
  * unless the option "qmc_spectral" is set (below), with m_spectral_mode on and for channels above 4; HPT_ERR_ARG for a null context or buffer and before InitRandomGens (N = 0); HPT_ERR_STATE before
- * CommitDeviceData, UpdateMembersPlainData or PackXYBlock. Megakernel schedule only. hpt_get_execution_time("PathTraceBlockQMC") gives its four slots.
+ * CommitDeviceData, UpdateMembersPlainData or PackXYBlock. The megakernel schedule, unless the option "qmc_wavefront" (below) sends the call to the
+ * wavefront schedule. hpt_get_execution_time("PathTraceBlockQMC") gives its four slots.
  * Spectral QMC (`hydra --qmc --spectral`) is opt-in: after hpt_set_option(ctx, "qmc_spectral", 1) a context with m_spectral_mode on is served
  * instead of refused (with m_spectral_mode off nothing changes). A sample then carries four wavelengths, SampleWavelengths of dimension
  * m_qmcSpdDim (hpt_qmc_layout; taken after the time sample), and SpectralCamRespoceToRGB(accumColor, wavelengths, rayFlags) takes the place of
@@ -700,6 +701,16 @@ int  hpt_set_schedule(hpt_ctx* ctx, int schedule, int refillBelow, int traceBloc
  *               comes back in a_dataGrad (hpt_put_diff_tex2d). Still HPT_ERR_UNSUPPORTED: a camera back plate (the replay has none),
  *               hpt_put_diff_lights on the same context, an explicit block-local schedule (the automatic choice avoids it), the instrumented
  *               probe, spectral, lens and motion scenes. Scenes without a map run the kernels they always ran. Any other value: HPT_ERR_ARG.
+ * Which schedule serves QMC path tracing (sample records and m_randomGens never depend on it; the frame is an atomic sum under either):
+ *   "qmc_wavefront"  0 (default): hpt_path_trace_qmc_block[_dev, _dev2] - and the FB_DIRECT forward of hpt_path_trace_kmlt_block[_dev] - run the
+ *               megakernel whatever hpt_set_schedule says. 1: such a call goes to the wavefront schedule exactly when a PathTraceBlock of as many
+ *               pixels as it has generator slots with work, min(N, S) with S = hpt_qmc_sample_count(pixelsNum, passNum), would - schedule 0: the
+ *               automatic rule, 2: always, 1 and 3: never, 4: the automatic rule. A pool slot is a generator slot and runs its samples g, g + N,
+ *               ... in order, so every sample record and every generator is the megakernel's bit for bit. Kept on the megakernel, silently and
+ *               with the same results: m_spectral_mode ("qmc_spectral" included), the triangle-sweep layout, RGB scenes with thin films, trace
+ *               depth 0 and instrumented contexts. hpt_get_last_launch and hpt_get_schedule report what ran. A call that would take the wavefront
+ *               form and whose slot 0 has more than 16777215 (0xFFFFFF) samples - what a pool slot's status word holds - returns HPT_ERR_ARG
+ *               and writes nothing. What the entry refuses it refuses under either value. Any other value: HPT_ERR_ARG.
  * Which schedule serves adaptive sampling (results never depend on it):
  *   "adaptive_wavefront"  0 (default): hpt_path_trace_block_counts[_dev] and every round of hpt_path_trace_block_adaptive[_dev] run the megakernel
  *               whatever hpt_set_schedule says. 1: each such call goes to the wavefront schedule exactly when a PathTraceBlock of as many pixels
