@@ -813,7 +813,9 @@ HPT_DEV V3 refract2(V3 dir, V3 n, float relativeIor)
 HPT_DEV float fresnel2(V3 v, V3 n, float ior)
 {
   const float cosi = dot(v, n);
-  const float sint = sqrtf_(1.0f - cosi * cosi) / ior;
+  // (the reference takes sqrt(1 - cosi^2) as it is, cmat_glass.h:218: at normal incidence a cosine one bit above 1 makes it NaN, every comparison with
+  //  the NaN reflectance fails and the glass never reflects such a ray - a quarter of the head-on rays; tests/test_specular_gpu.py)
+  const float sint = sqrtf_(smax(1.0f - cosi * cosi, 0.0f)) / ior;
   if (sint > 1.0f) return 1.0f;
   const float cost = sqrtf_(1.0f - sint * sint);
   const float Rp = (ior * cosi - cost) / (ior * cosi + cost);

@@ -648,7 +648,7 @@ static inline f3 refract2(f3 dir, f3 n, float relativeIor)
 static inline float fresnel2(f3 v, f3 n, float ior)
 {
   const float cosi = dot(v, n);
-  const float sint = std::sqrt(1.0f - cosi * cosi) / ior;
+  const float sint = std::sqrt(std::max(1.0f - cosi * cosi, 0.0f)) / ior;   // (cmat_glass.h:218 without the clamp: NaN for a cosine one bit above 1, as in hpt_device.h)
   if (sint > 1.0f) return 1.0f;
   const float cost = std::sqrt(1.0f - sint * sint);
   const float Rp = (ior * cosi - cost) / (ior * cosi + cost);
